@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode-step throughput of the Mustafar sparse-attention path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--layers 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--layers 32] [--full] [--dump-outputs DIR]
 
 One "step" = one decode step of the attention path over all layers (32): per layer the key SpMV over the
 compressed cache, the dense window scores, scale + fp32 softmax, the value SpMV, the dense window p.V
@@ -16,7 +16,9 @@ no data-path collective; `value` = units of all ranks / max-over-ranks time ("sc
 torch.distributed.run the ranks come from the environment; a plain `python bench.py --gpus N` starts N fresh
 child processes itself (before this process touches the GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects, plus:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps of the headline leg, writes their last step's
+outputs if --dump-outputs is given (DIR/attn_out.npy: every layer's attention output, [layers, batch, q heads, head_dim], float32)
+and prints the line; the objects below are null in it.  --full adds `roofline`, `cpu_baseline` and:
   self_check     the timed call sequence against the two reference entry points, every layer, before the timed region
                  (a mismatch ends the run with a non-zero exit code and no line)
   roofline_fma_mix / roofline_mfma   the same measurement on the exact v_fma_mix engine / the opt-in matrix-pipe engine
@@ -89,7 +91,15 @@ def parse():
     ap.add_argument("--no-seq-sweep", action="store_true", help="skip the Llama-3-8B 70 % sweep over L = 4k / 16k / 32k (8k is the main result)")
     ap.add_argument("--no-graph", action="store_true", help="fused api without hipGraph capture of the step")
     ap.add_argument("--api", default="fused", choices=["fused", "native", "reference"], help="call sequence timed for `value`")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the self-check, per-kernel / roofline figures, the other call sequences, engines, legs and configs and the CPU baseline "
+                         "(the --no-* options leave parts of it out); a plain run times the headline leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ multi-GPU entry
@@ -158,6 +168,22 @@ def algorithmic_bytes(past, BH, which) -> int:
     return c[0].numel() * 8 + c[1].numel() * 4 + c[2].flat.numel() * 2 + BH * 128 * 2 + BH * T * 2
 
 
+DUMP_LIMIT_BYTES = 60 << 20   # what --dump-outputs writes at most (header included, under 64 MB)
+
+
+def dump_outputs(dirname, outs) -> None:
+    """--dump-outputs: the per-layer outputs of the last timed step as DIR/attn_out.npy, float32 [layers, batch, q heads, head_dim].
+    Past DUMP_LIMIT_BYTES a fixed, seeded sample of the flattened array (in index order) is written instead, as DIR/attn_out_sample.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    x = torch.stack([o.reshape(o.shape[0], o.shape[1], o.shape[-1]) for o in outs]).float().cpu().numpy()
+    name = "attn_out"
+    if x.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(x.size, DUMP_LIMIT_BYTES // x.itemsize, replace=False))
+        x, name = x.reshape(-1)[keep], "attn_out_sample"
+    np.save(os.path.join(dirname, name + ".npy"), x)
+
+
 class KernelTimer:
     """HIP events around every call of the two operators, recorded on torch's current stream -- the stream the
     C ABI launches on (unfused call sequences only; the fused one has kernel timestamps inside the library)."""
@@ -222,6 +248,8 @@ class Workload:
         self.alg_key = sum(algorithmic_bytes(p, self.BH, "key") for p in self.pasts) / layers
         self.alg_val = sum(algorithmic_bytes(p, self.BH, "value") for p in self.pasts) / layers
         self.extra = {}
+        self.keep_outputs = False   # True: the timed legs leave their last step's per-layer outputs in last_outputs (--dump-outputs)
+        self.last_outputs = None
 
     # -- call sequences ---------------------------------------------------------------------------------------------
     def one_step(self, state):
@@ -276,8 +304,9 @@ class Workload:
         del fused
         return worst
 
-    def timed_eager(self, api, steps, warmup):
-        """Eager call sequence `api`; per-kernel HIP events are recorded live inside the timed region."""
+    def timed_eager(self, api, steps, warmup, per_kernel=True):
+        """Eager call sequence `api`; per-kernel HIP events are recorded live inside the timed region.  per_kernel=False: no
+        instrumented pass after it (returns (dt, None))."""
         from mustafar_amd import _lib
         self.cfg.api, self.cfg.arena = api, api == "fused"
         # decode() never mutates a reference-layout past in place; the fused api appends to its windows and to its
@@ -287,7 +316,13 @@ class Workload:
             self.one_step(state)
         self.timer.reset()
         self.timer.enabled = False
-        dt = self.bracket(lambda: [self.one_step(state) for _ in range(steps)])
+        outs = []
+        dt = self.bracket(lambda: outs.extend([self.one_step(state) for _ in range(steps)]))
+        if self.keep_outputs:
+            self.last_outputs = [o.clone() for o in outs[-1]]
+        del outs
+        if not per_kernel:
+            return dt, None
         # kernel / call durations: the same steps once more, instrumented, OUTSIDE the timed region -- these call sequences are
         # host-bound, and an event pair around every launch costs them 10-15 % (round 3a timed them instrumented)
         nprof = min(steps, 10)
@@ -336,13 +371,14 @@ class Workload:
             a.drop_extents()
             b.drop_extents()
 
-    def timed_graph(self, steps, warmup, start_at_trigger_distance=None, device_t=False):
+    def timed_graph(self, steps, warmup, start_at_trigger_distance=None, device_t=False, per_kernel=True):
         """The fused call sequence of a whole step (all layers) captured ONCE into a hipGraph and replayed per step;
         a device-side counter grows the windows between replays.  A step that fires the 256-token compression
         trigger (model :324) runs eagerly; the graph of the steps behind it was captured ahead of it (the cache grows by extents:
         nothing a graph holds moves).  device_t=True: ONE graph for the whole leg -- the launches are sized for a capacity and read
         the compressed tokens in use from a device int (mustafar_decode_attention_extents: T_device); after the trigger step 256
-        are added to it and taken off the window counter."""
+        are added to it and taken off the window counter.  per_kernel=False: no eager profiling pass (nor consolidation timing)
+        after the timed replays (returns (dt, None))."""
         from mustafar_amd import _lib
         attn, qs, ks, vs, layers, dev, lib = self.attn, self.qs, self.ks, self.vs, self.layers, self.dev, self.lib
         state = self.fused_state()
@@ -366,13 +402,20 @@ class Workload:
 
         pool = torch.cuda.graph_pool_handle()   # one memory pool for every graph of this leg: a capture behind a trigger then finds
                                                 # the blocks of the graph it replaces instead of asking the driver for new ones (16 ms -> 0.7 ms)
+        outs_of = {}   # graph -> the output tensors its replays write (kept only when self.keep_outputs)
 
         def record(st):
             g = torch.cuda.CUDAGraph()
+            outs = []
             with torch.cuda.graph(g, pool=pool):
                 for l in range(layers):
-                    attn.decode_fused(qs[l], ks[l], vs[l], st[l], step_counter=counter, **kw_t)
+                    out = attn.decode_fused(qs[l], ks[l], vs[l], st[l], step_counter=counter, **kw_t)[0]
+                    if self.keep_outputs:
+                        outs.append(out)
+                    del out   # (not kept: the next layer's output takes the same block, as when nothing is dumped)
                 _lib.check(lib.mustafar_counter_add(torch.cuda.current_stream(dev).cuda_stream, counter.data_ptr(), 1), "counter_add")
+            if self.keep_outputs:
+                outs_of[g] = outs
             return g
 
         def capture():
@@ -407,6 +450,7 @@ class Workload:
                 torch.cuda.synchronize(dev)      # (the syncs bracket the trigger step for `trigger_step_ms`; they cost the leg < 0.1 %)
                 t0 = time.perf_counter()
                 box["g"].replay()
+                box["last"] = box["g"]
                 box["since"] += 1
                 for l in range(layers):
                     state[l] = attn.advance(state[l], box["since"])
@@ -437,6 +481,7 @@ class Workload:
                         fut = [attn.advance((p[0], copy_window(p[1]), p[2], copy_window(p[3]), p[4], p[5]), box["since"]) for p in state]
                         box["pool"] = attn.prepare_triggers(fut)
                 box["g"].replay()
+                box["last"] = box["g"]
                 box["since"] += 1
                 if inflight:   # at most `inflight` replays queued behind the one the GPU works on (MUSTAFAR_BENCH_INFLIGHT; see the note at `inflight`)
                     ev = ring[box["since"] % inflight]
@@ -452,6 +497,9 @@ class Workload:
         for _ in range(warmup):
             step()
         dt = self.bracket(lambda: [step() for _ in range(steps)])
+        if self.keep_outputs:
+            self.last_outputs = [o.clone() for o in outs_of[box["last"]]]
+        outs_of.clear()
         for l in range(layers):
             state[l] = attn.advance(state[l], box["since"])
         # KV bytes of the container as the timed region leaves it (BEFORE the eager profiling pass below, which may run into the next
@@ -462,13 +510,16 @@ class Workload:
                                                    + p[3].len * p[3].buf.shape[0] * p[3].buf.shape[1] * D * 2 for p in state))
         self.extra["kv_tokens_at_measurement"] = int(state[0][5])
         self.extra["dense_bytes_at_measurement"] = int(layers * 2 * self.batch * self.Hkv * state[0][5] * D * 2)
+        self.extra["triggers_in_timed_region"] = box["triggers"]
+        if not per_kernel:
+            del state
+            return dt, None
         # per-kernel durations: the same steps again, eagerly, right after the timed replays (kernel timestamps cannot be
         # taken between the nodes of a replayed graph); rocprofv3 over the replays themselves agrees (profiles/)
         nprof = min(steps, 10)
         kern = self.profile(lambda: [self.one_step(state) for _ in range(nprof)], nprof * layers)
         self.extra["eager_pass_ms_per_step"] = round(self.last_profile_wall_s / nprof * 1e3, 4)
         self.extra["finish_kernel_us"] = round(self.last_finish_us, 2)
-        self.extra["triggers_in_timed_region"] = box["triggers"]
         if box["triggers"] and hasattr(state[0][0], "consolidate") and state[0][0].extents:
             # what consolidation costs (a launch form that cannot read extents; a full table: 512 triggers): every layer's base + extents re-housed into one base
             torch.cuda.synchronize(dev)
@@ -733,23 +784,31 @@ def main():
     torch.cuda.reset_peak_memory_stats(dev)
     w = Workload(a.config, a.layers, dev, rank, world, dist, rehearse, timer, lib)
 
-    # ---- self-check of the call sequence about to be timed (untimed) ---------------------------------------------
-    excess = w.self_check()
-    if not excess <= 1.0:
-        raise SystemExit(f"bench.py: self-check FAILED: fused (arena) vs the two reference entry points differ by {excess:.2f}x the fp16 bound")
+    # ---- self-check of the call sequence about to be timed (untimed; --full) ----------------------------------------
+    excess = None
+    if a.full:
+        excess = w.self_check()
+        if not excess <= 1.0:
+            raise SystemExit(f"bench.py: self-check FAILED: fused (arena) vs the two reference entry points differ by {excess:.2f}x the fp16 bound")
 
     # ---- the timed region -----------------------------------------------------------------------------------------
     use_graph = a.api == "fused" and not a.no_graph
+    w.keep_outputs = a.dump_outputs is not None and rank == 0
     if use_graph:
-        dt, (key_us, val_us, n_kern) = w.timed_graph(a.steps, a.warmup)
+        dt, kern = w.timed_graph(a.steps, a.warmup, per_kernel=a.full)
     else:
-        dt, (key_us, val_us, n_kern) = w.timed_eager(a.api, a.steps, a.warmup)
+        dt, kern = w.timed_eager(a.api, a.steps, a.warmup, per_kernel=a.full)
+    key_us, val_us, n_kern = kern if kern is not None else (None, None, None)
+    w.keep_outputs = False
+    if w.last_outputs is not None:
+        dump_outputs(a.dump_outputs, w.last_outputs)
+        w.last_outputs = None
     main_extra = dict(w.extra)
 
     # ---- the rate the device HOLDS: >= 200 replays of the same step at fixed compressed length and window (no trigger, nothing grows).
     # The headline above is `--steps` replays (20 by default: a ~27-ms burst behind a synchronisation point); a generate is hundreds of steps.
     sustained = None
-    if use_graph and not a.no_trigger_leg:
+    if a.full and use_graph and not a.no_trigger_leg:
         nsus = 256
         dt_s, course = w.timed_sustained(nsus)
         sustained = {"value": round(world * w.batch * nsus / dt_s, 2), "unit": "tokens/s", "steps": nsus, "ms_per_step": round(dt_s / nsus * 1e3, 4),
@@ -761,7 +820,7 @@ def main():
                              "(in-kernel clock of both: profiles/r06_clocks.txt)"}
 
     others = {}
-    if not a.no_reference_api:
+    if a.full and not a.no_reference_api:
         for api in ("fused", "native", "reference"):
             if api == a.api and (api != "fused" or a.no_graph):
                 continue
@@ -787,7 +846,7 @@ def main():
     # `flags`): fma_mix = exact fp16 products (the round-1/2 default), mfma = the matrix pipe as a 4-wide FMA unit (opt-in; the
     # north_star leaves MFMA off)
     engine_legs, roofline_legs = {}, {}
-    if use_graph and w.Hq // w.Hkv >= 4 and (w.Hq // w.Hkv) % 4 == 0:
+    if a.full and use_graph and w.Hq // w.Hkv >= 4 and (w.Hq // w.Hkv) % 4 == 0:
         for eng, note in (("valu", "v_fma_mix_f32 per tile and head: exact fp16 x fp16 products, fp16 subnormals included"),
                           ("mfma", "v_mfma_f32_4x4x4_16B_f16 as a 4-wide FMA unit (nothing dense is built); opt-in, off by default")):
             w.cfg.engine = eng
@@ -806,7 +865,7 @@ def main():
 
     # ---- >= 256 consecutive steps: the 256-token compression trigger (prune + compress + in-place append) included --------
     trig = None
-    if use_graph and not a.no_trigger_leg:
+    if a.full and use_graph and not a.no_trigger_leg:
         nst = 256
         w.extra.pop("trigger_step_ms", None)
         w.rehearse_trigger()
@@ -826,7 +885,7 @@ def main():
     # ---- a whole generate of the reference harness: 600 new tokens (mem_spd_test.py:72-74 `output_length`) from this prompt length -- three
     # 256-token triggers at L = 8192, and two thirds of the steps at cache lengths off the grid of whole rounds of workgroups -----------------
     gen = None
-    if use_graph and not a.no_trigger_leg:
+    if a.full and use_graph and not a.no_trigger_leg:
         ngen = 600
         w.extra.pop("trigger_step_ms", None)
         dt_g, _ = w.timed_graph(ngen, 1)
@@ -839,14 +898,14 @@ def main():
 
     # ---- the other BASELINE configs as sub-results (N = 1) -----------------------------------------------------------
     label, Hq, Hkv, s, L, batch, T = w.label, w.Hq, w.Hkv, w.s, w.L, w.batch, w.T
-    roofline = w.roofline(key_us, val_us, n_kern) if rank == 0 else None
+    roofline = w.roofline(key_us, val_us, n_kern) if rank == 0 and a.full else None
     if roofline is not None and val_us == 0:
         # the same bytes against the STEP: layers x algorithmic bytes of the dominant launch / ms_per_step (row kernel, launch gaps and the dense
         # windows' time included in the denominator, nothing of them in the numerator)
         roofline["step_level_frac"] = round(w.layers * roofline["algorithmic_bytes_per_launch"] / (dt / a.steps) / 1e9 / HBM_PEAK_GBPS, 4)
     ref_kv, dense_bytes = w.ref_kv_bytes, w.dense_bytes
     sub = {}
-    if world == 1 and not a.no_other_configs and a.api == "fused" and not a.no_graph:
+    if a.full and world == 1 and not a.no_other_configs and a.api == "fused" and not a.no_graph:
         del w
         torch.cuda.empty_cache()
         for name in ("c2", "c4", "c5", "b1"):   # (c2's whole layer is under 64 MB: Infinity-Cache-sized, flagged in its entry; b1: the headline's geometry and length at batch 1 -- what single-user decode looks like; not a BASELINE config)
@@ -854,13 +913,13 @@ def main():
                 sub[name] = run_sub_config(name, a, dev, rank, world, dist, rehearse, timer, lib)
 
     prefill = None
-    if world == 1 and not a.no_other_configs and a.api == "fused":
+    if a.full and world == 1 and not a.no_other_configs and a.api == "fused":
         torch.cuda.empty_cache()
         prefill = prefill_compression_leg(dev, lib, Hkv, s, T, batch)
 
     # ---- the metric's axis: Llama-3-8B geometry, 70 % / 70 %, batch 8 at L = 4k / 8k / 16k / 32k (N = 1) ------------------------
     sweep = None
-    if world == 1 and not a.no_seq_sweep and a.api == "fused" and not a.no_graph and a.config == "c3":
+    if a.full and world == 1 and not a.no_seq_sweep and a.api == "fused" and not a.no_graph and a.config == "c3":
         pts = {}
         for name in SEQ_SWEEP:
             if name == "c3":    # the main result IS the 8k point
@@ -873,7 +932,7 @@ def main():
     # ---- off the grid of whole rounds of workgroups: c3's geometry at T = 8192 ... 8960 (every BASELINE point sits at T = 2^k - 256, just
     # under one resident round; a cache that has grown by a few 256-token extents does not) -----------------------------------------
     offgrid = None
-    if world == 1 and not a.no_seq_sweep and a.api == "fused" and not a.no_graph and a.config == "c3":
+    if a.full and world == 1 and not a.no_seq_sweep and a.api == "fused" and not a.no_graph and a.config == "c3":
         pts = {}
         for name in OFFGRID:
             p_ = run_seq_point(name, a, dev, rank, world, dist, rehearse, timer, lib)
@@ -889,7 +948,7 @@ def main():
 
     # ---- host-CPU dense baseline (oracle/dense_ref.py: the reference's dense pruned path), bounded sample --------
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         from oracle.dense_ref import time_dense_cpu
         keep = 1.0 - (max(1, int(s * D)) - 1) / D
         sample_layers = 1
@@ -906,12 +965,13 @@ def main():
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
         "config": {"workload": label, "id": a.config, "layers": a.layers, "q_heads": Hq, "kv_heads": Hkv, "head_dim": D,
                    "sparsity": s, "seq_len": L, "compressed_tokens": T, "batch_per_gpu": batch, "residual_length": R,
-                   "api": a.api, "api_note": API_NOTE[a.api] + ("; the whole step captured once in a hipGraph and replayed" if use_graph else "") + ("; structure run: " + roofline["kernel"] if a.api == "fused" else ""),
+                   "api": a.api, "api_note": API_NOTE[a.api] + ("; the whole step captured once in a hipGraph and replayed" if use_graph else "") + ("; structure run: " + roofline["kernel"] if a.api == "fused" and roofline else ""),
                    "fma_engine": "dot2 (v_dot2_f32_f16 on pairs of tiles in the GQA-4 one-pass launch, v_fma_mix_f32 elsewhere; MFMA off)",
                    "parallelism": f"replicas x{world}"},
+        "full": a.full,
         "self_check": {"passed": True, "excess_over_fp16_bound": round(excess, 3),
                        "what": "every layer's output of the timed call sequence (fused entry point, arena cache) vs the two reference entry "
-                               "points with PyTorch glue on the same inputs; bound = 2 ulp of the output scale + 1e-4"},
+                               "points with PyTorch glue on the same inputs; bound = 2 ulp of the output scale + 1e-4"} if excess is not None else None,
         "peak_kv_bytes": int(timed_kv), "peak_kv_bytes_note": "bytes IN USE of the container the timed leg ran on (arena rows + stream regions + windows), taken at the end of the "
                                                               "timed region; kv_bytes_reserved = what is allocated for it (arenas at 1.03 x their content, windows at capacity)",
         "kv_bytes_reserved": main_extra.get("arena_bytes_reserved"), "kv_bytes_reference_layout": int(ref_kv),

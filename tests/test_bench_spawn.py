@@ -31,3 +31,30 @@ def test_launcher_environment_must_agree_with_the_flag():
 def test_one_rank_needs_no_spawn():
     r = _run(["--gpus", "1"], MUSTAFAR_BENCH_DRYRUN="1")
     assert r.returncode == 0 and json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+def test_steps_must_be_at_least_one():
+    r = _run(["--gpus", "1", "--steps", "0"], MUSTAFAR_BENCH_DRYRUN="1")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_step_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: per-layer [B, Hq, 1, D] fp16 outputs -> DIR/attn_out.npy [layers, B, Hq, D] float32; past the size limit a
+    fixed seeded sample of the flattened array (the same one every run)."""
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randn(2, 4, 1, 128, generator=g).half() for _ in range(3)]
+    bench.dump_outputs(str(tmp_path / "full"), outs)
+    x = np.load(tmp_path / "full" / "attn_out.npy")
+    assert x.dtype == np.float32 and x.shape == (3, 2, 4, 128)
+    assert np.array_equal(x[1], outs[1][:, :, 0].float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1024)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    s1, s2 = np.load(tmp_path / "s1" / "attn_out_sample.npy"), np.load(tmp_path / "s2" / "attn_out_sample.npy")
+    assert s1.dtype == np.float32 and s1.nbytes <= 1024 and np.array_equal(s1, s2)
+    assert np.isin(s1, x).all()

@@ -4,7 +4,7 @@
 set -e -o pipefail
 TAG=${1:-r04b}; R=$(pwd); O=$R/gpurun_out/$TAG; rm -rf "$O"; mkdir -p "$O"
 nonempty() { [ -s "$1" ] || { echo "empty evidence file $1"; exit 1; }; }
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err; nonempty $O/bench_c3.json; echo "bench done"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_c3.json 2> $O/bench_c3.err; nonempty $O/bench_c3.json; echo "bench done"
 python3 tools/bench_compress.py c3 c4 2> $O/compress.err | grep cfg > $O/compress.txt; nonempty $O/compress.txt
 python3 tools/bench_append.py 2> $O/append.err | grep cfg > $O/append.txt; nonempty $O/append.txt
 python3 tools/bench_extent_append.py 2> $O/extent_append.err > $O/extent_append.txt; nonempty $O/extent_append.txt

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): tools/quick_bench.sh [cfgs]  -- fused + graph legs of both FMA engines, one line per config
 CFGS=${1:-"c3 c5"}
-B="--steps 20 --warmup 5 --no-cpu-baseline --no-reference-api --no-other-configs --no-trigger-leg"
+B="--full --steps 20 --warmup 5 --no-cpu-baseline --no-reference-api --no-other-configs --no-trigger-leg"
 for c in $CFGS; do
   python bench.py --config $c $B 2>/dev/null | python -c "
 import json,sys
