@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import oracle as orc
+from tests import exact_data as xd
 from tests.util import fp16_bound, make_cache
 
 pytestmark = pytest.mark.gpu
@@ -61,6 +62,7 @@ def _check_spmv(got, C16, Cd, sumabs, what):
 @pytest.mark.parametrize("groups,N,B,t,s,adv", [
     (1, 8, 2, 256, 0.7, False), (4, 8, 2, 256, 0.7, False), (4, 1, 3, 320, 0.5, False), (2, 1, 2, 64, 0.8, False),
     (1, 1, 1, 1024, 0.7, False), (4, 8, 1, 512, 0.8, True), (8, 1, 1, 192, 0.7, False), (3, 8, 2, 128, 0.7, False),
+    (5, 1, 2, 256, 0.7, False), (6, 8, 1, 192, 0.7, False), (7, 1, 2, 320, 0.8, False),
 ])
 def test_key_spmv_vs_oracle(pkg, groups, N, B, t, s, adv):
     mp, _ = pkg
@@ -78,6 +80,57 @@ def test_key_spmv_vs_oracle(pkg, groups, N, B, t, s, adv):
     _check_spmv(out, C16, Cd, sumabs, "key")
     if N == 8:
         assert not out[:, 1:].any(), "pad rows must be exact zeros"
+
+
+KEY_CASES = [(1, 8, 2, 256, 0.7), (4, 8, 2, 256, 0.7), (4, 1, 3, 320, 0.5), (2, 1, 2, 64, 0.8), (1, 1, 1, 1024, 0.7), (4, 8, 1, 512, 0.8),
+             (8, 1, 1, 192, 0.7), (3, 8, 2, 128, 0.7), (4, 8, 2, 64, 0.7), (5, 8, 2, 256, 0.7), (6, 1, 1, 192, 0.7), (7, 8, 2, 128, 0.8)]
+
+
+@pytest.mark.parametrize("groups,N,B,t,s", KEY_CASES)
+def test_key_spmv_bit_exact_on_dyadic_data(pkg, groups, N, B, t, s):
+    """Dyadic K and q (tests/exact_data.py): every partial sum is exact in fp32, so the fp16 result is unique and the HIP output equals
+    the oracle's bit for bit -- a lost or doubled product shows, however small.  All N rows of q are non-zero."""
+    mp, _ = pkg
+    rng = np.random.default_rng(300 + t + groups)
+    x = orc.prune_magnitude(xd.dyadic(rng, (B, t, 128), 5, 4), s)
+    bmp, idx, nzs = orc.convert_key_batched(x)
+    off = orc.nz_offset_from_idx(idx)
+    BH = B * groups
+    q = xd.dyadic(rng, (BH, N, 128), 5, 4)
+    for b in range(BH):
+        xd.assert_exact_budget(xd.units(q[b], 4), xd.units(x[b // groups], 4).T)
+    out = mp.mustafar_key_formulation(_t(bmp), _t(np.concatenate(nzs)), _t(idx), _t(off), _t(q), t, 128, BH, groups)
+    C16, Cd = orc.key_spmv(bmp, np.concatenate(nzs), idx, off, q, t, 128, BH, groups)
+    assert np.array_equal(Cd, np.stack([q[b].astype(np.float64) @ x[b // groups].astype(np.float64).T for b in range(BH)]))
+    got = out.cpu().numpy()
+    assert np.array_equal(got.astype(np.float64), C16.astype(np.float64)), f"{int((got != C16).sum())} scores differ from the exact ones"
+
+
+VALUE_CASES = [(1, 8, 2, 256, 0.7, 0), (4, 8, 2, 256, 0.7, 0), (4, 1, 3, 320, 0.5, 0), (2, 1, 2, 64, 0.8, 0), (1, 1, 1, 1024, 0.7, 1),
+               (4, 1, 1, 1024, 0.7, 3), (8, 1, 1, 192, 0.7, 2), (3, 8, 2, 128, 0.7, 1), (4, 8, 1, 1024, 0.7, 5), (4, 8, 2, 64, 0.7, 0),
+               (5, 8, 2, 256, 0.7, 2), (6, 1, 1, 512, 0.7, 0), (7, 8, 2, 320, 0.8, 1)]
+
+
+@pytest.mark.parametrize("groups,N,B,t,s,split", VALUE_CASES)
+def test_value_spmv_bit_exact_on_dyadic_data(pkg, groups, N, B, t, s, split):
+    """Dyadic V and probabilities j * 2^-12 (j <= 15): bit equality with the oracle, pad rows non-zero, the module's split_k values."""
+    mp, _ = pkg
+    rng = np.random.default_rng(400 + t + groups)
+    x = orc.prune_magnitude(xd.dyadic(rng, (B, t, 128), 5, 4), s)
+    bmp, idx, nzs = orc.convert_value_batched(x)
+    off = orc.nz_offset_from_idx(idx)
+    BH = B * groups
+    p = xd.dyadic_probs(rng, (BH, N, t), 12, 15)
+    if N == 8:
+        p[:, 3] = 0                                   # one pad row without a non-zero: exact zeros
+    for b in range(BH):
+        xd.assert_exact_budget(xd.units(p[b], 12), xd.units(x[b // groups], 4))
+    ws = torch.zeros(1, dtype=torch.float16, device=DEV)
+    out = mp.mustafar_value_formulation(_t(bmp), _t(np.concatenate(nzs)), _t(idx), _t(off), _t(p), ws, 128, t, BH, groups, split_k=split)
+    C16, Cd = orc.value_spmv(bmp, np.concatenate(nzs), idx, off, p, 128, t, BH, groups)
+    assert np.array_equal(Cd, np.stack([p[b].astype(np.float64) @ x[b // groups].astype(np.float64) for b in range(BH)]))
+    got = out.cpu().numpy()
+    assert np.array_equal(got.astype(np.float64), C16.astype(np.float64)), f"{int((got != C16).sum())} outputs differ from the exact ones"
 
 
 @pytest.mark.parametrize("groups", [1, 4])
@@ -105,6 +158,7 @@ def test_key_spmv_nonzero_pad_rows(pkg, groups):
     (2, 1, 2, 64, 0.8, 0, False), (1, 1, 1, 1024, 0.7, 1, False), (4, 1, 1, 1024, 0.7, 3, False),
     (4, 8, 1, 512, 0.8, 0, True), (8, 1, 1, 192, 0.7, 2, False), (3, 8, 2, 128, 0.7, 1, False),
     (4, 8, 1, 1024, 0.7, 5, False),
+    (5, 1, 2, 256, 0.7, 2, False), (6, 8, 1, 512, 0.7, 0, False), (7, 1, 2, 320, 0.8, 1, False),
 ])
 def test_value_spmv_vs_oracle(pkg, groups, N, B, t, s, split, adv):
     mp, _ = pkg
