@@ -90,6 +90,22 @@ KEY_CASES = [(1, 8, 2, 256, 0.7), (4, 8, 2, 256, 0.7), (4, 1, 3, 320, 0.5), (2, 
 def test_key_spmv_bit_exact_on_dyadic_data(pkg, groups, N, B, t, s):
     """Dyadic K and q (tests/exact_data.py): every partial sum is exact in fp32, so the fp16 result is unique and the HIP output equals
     the oracle's bit for bit -- a lost or doubled product shows, however small.  All N rows of q are non-zero."""
+    _key_dyadic(pkg, groups, N, B, t, s)
+
+
+# The same cases away from the usual operating point: 0.0 keeps all 128 values of a token (a staged chunk fills the whole 4 KiB window:
+# the matrix-pipe engine's upper half, spmv.hip stage_issue<SKIP>), 0.3 reaches into the upper half on most chunks, 0.9 / 0.99 leave
+# most tiles empty or with one or two values.  N = 1 and 8, groups 1 / 4 / 8.
+SPARSITIES = (0.0, 0.3, 0.9, 0.99)
+KEY_SPARSITY_CASES = [(g, n, b, t, s) for s in SPARSITIES for g, n, b, t in ((1, 1, 2, 256), (4, 8, 2, 256), (4, 1, 1, 512), (8, 8, 1, 192))]
+
+
+@pytest.mark.parametrize("groups,N,B,t,s", KEY_SPARSITY_CASES, ids=[f"s{c[4]}-g{c[0]}-N{c[1]}-t{c[3]}" for c in KEY_SPARSITY_CASES])
+def test_key_spmv_bit_exact_across_sparsities(pkg, groups, N, B, t, s):
+    _key_dyadic(pkg, groups, N, B, t, s)
+
+
+def _key_dyadic(pkg, groups, N, B, t, s):
     mp, _ = pkg
     rng = np.random.default_rng(300 + t + groups)
     x = orc.prune_magnitude(xd.dyadic(rng, (B, t, 128), 5, 4), s)
@@ -114,6 +130,20 @@ VALUE_CASES = [(1, 8, 2, 256, 0.7, 0), (4, 8, 2, 256, 0.7, 0), (4, 1, 3, 320, 0.
 @pytest.mark.parametrize("groups,N,B,t,s,split", VALUE_CASES)
 def test_value_spmv_bit_exact_on_dyadic_data(pkg, groups, N, B, t, s, split):
     """Dyadic V and probabilities j * 2^-12 (j <= 15): bit equality with the oracle, pad rows non-zero, the module's split_k values."""
+    _value_dyadic(pkg, groups, N, B, t, s, split)
+
+
+VALUE_SPARSITY_CASES = [(g, n, b, t, s, k) for s in SPARSITIES
+                        for g, n, b, t, k in ((1, 8, 2, 256, 0), (4, 1, 1, 1024, 3), (4, 8, 2, 512, 2), (8, 1, 1, 192, 0), (4, 1, 2, 320, 0))]
+
+
+@pytest.mark.parametrize("groups,N,B,t,s,split", VALUE_SPARSITY_CASES,
+                         ids=[f"s{c[4]}-g{c[0]}-N{c[1]}-t{c[3]}-split{c[5]}" for c in VALUE_SPARSITY_CASES])
+def test_value_spmv_bit_exact_across_sparsities(pkg, groups, N, B, t, s, split):
+    _value_dyadic(pkg, groups, N, B, t, s, split)
+
+
+def _value_dyadic(pkg, groups, N, B, t, s, split):
     mp, _ = pkg
     rng = np.random.default_rng(400 + t + groups)
     x = orc.prune_magnitude(xd.dyadic(rng, (B, t, 128), 5, 4), s)

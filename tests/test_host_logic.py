@@ -164,6 +164,29 @@ def test_kth_matches_reference_expression():
         assert kth_from_sparsity(s, 128) == want == orc.kth_from_sparsity(s, 128)
 
 
+def test_kth_is_the_truncated_product_over_a_sparsity_grid():
+    """model :97 truncates s * 128 as the float product comes out (0.7 * 128 = 89.6 -> 89, 0.29 * 128 = 37.12 -> 37, 0.95 * 128 =
+    121.6 -> 121): not a rounding, not a product of exact decimals."""
+    from mustafar_amd.compression import kth_from_sparsity
+    grid = [i / 100 for i in range(100)] + [0.29, 0.7, 0.95, 0.99, 0.999, 1 / 128, 127 / 128, 0.1 + 0.2]
+    for s in grid:
+        assert kth_from_sparsity(s, 128) == max(1, int(s * 128)) == orc.kth_from_sparsity(s, 128), s
+    for s, want in ((0.0, 1), (0.005, 1), (0.29, 37), (0.3, 38), (0.7, 89), (0.9, 115), (0.95, 121), (0.99, 126), (127 / 128, 127)):
+        assert kth_from_sparsity(s, 128) == want, s
+
+
+@pytest.mark.parametrize("kth,per_token", [(0, 136), (1, 136), (89, 48), (126, 11)])
+def test_expected_append_before_anything_is_measured(kth, per_token):
+    """An arena with fewer than 64 tokens sizes an append from what the prune rule keeps without ties, 128 - kth + 1 values per token
+    (every value for kth 0, rows already pruned), + 8 halfs of tile padding, + 4 % and 256 halfs: the size is the kth's, not another's."""
+    from mustafar_amd.cache import CompressedArena
+    a = CompressedArena.__new__(CompressedArena)        # (no device storage: nothing measured, only the estimate is asked for)
+    a.tokens = 0
+    for t in (64, 256, 4096):
+        assert a._expected_append(t, kth) == int(t * per_token * 1.04) + 256
+    assert a._expected_append(256, kth) >= 256 * (128 if kth <= 1 else 128 - kth + 1)
+
+
 @pytest.mark.parametrize("which", ["key", "value"])
 def test_cache_append_equals_one_shot_compression(which):
     """Property of the format + hook append (model :339-390): compress(A) ++ compress(B) == compress(A||B)."""

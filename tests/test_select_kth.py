@@ -21,6 +21,16 @@ def lib(tmp_path_factory):
     return L
 
 
+@pytest.fixture(scope="module")
+def devlib(tmp_path_factory):
+    """The device branch of the header (byte permutes instead of shift + select) built for the host with a model of v_perm_b32."""
+    out = str(tmp_path_factory.mktemp("selkth_dev") / "libselect_kth_device_emu.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", os.path.join(ROOT, "tests", "csrc", "select_kth_device_emu.cpp"), "-o", out])
+    L = ctypes.CDLL(out)
+    L.kth_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    return L
+
+
 def test_transpose_orientation(lib):
     rng = np.random.default_rng(0)
     a = rng.integers(0, 2 ** 32, 32, dtype=np.uint64).astype(np.uint32)
@@ -54,3 +64,18 @@ def test_kth_magnitude_matches_numpy(lib, kth):
     got = np.empty(x.shape[0], np.uint32)
     lib.kth_rows(words.ctypes.data, x.shape[0], kth, got.ctypes.data)
     assert np.array_equal(got, want)
+
+
+def test_device_branch_kth_matches_numpy_at_every_k(devlib):
+    """What the GPU build compiles (the perm stages, SERIAL both ways), at every k 1..128.  (Exchanging the selectors of the two
+    permutes of one stage, or the operands of one permute, only relabels which element sits at which bit of every plane -- the
+    search reads counts and intersections and gives the same result; a permute given a wrong selector does not.)"""
+    x = _rows()
+    mags = np.sort(x.view(np.uint16) & 0x7fff, axis=1)
+    words = np.ascontiguousarray(x.view(np.uint16)).view(np.uint32).reshape(x.shape[0], 64)
+    got = np.empty(x.shape[0], np.uint32)
+    for kth in range(1, 129):
+        for serial in (0, 1):
+            devlib.kth_rows(words.ctypes.data, x.shape[0], kth, serial, got.ctypes.data)
+            bad = np.nonzero(got != mags[:, kth - 1])[0]
+            assert not len(bad), f"kth {kth} serial {serial}: rows {bad[:8].tolist()}"
