@@ -14,7 +14,16 @@
  *   NZ_offset  u32 [B']              start of each head's stream in uint4 (16-byte) units
  *   K tile id = (token/64)*D + d            -> 64 consecutive tokens of channel d
  *   V tile id = (token/64)*D + (c/64)*64 + token%64 -> 64 consecutive channels of one token
- *   B' = batch * kv_heads, tiles = T*D/64, D = head_dim (this build: D == 128).
+ *   B' = batch * kv_heads, tiles = T*D/64, D = head_dim.
+ *
+ * Support by head_dim:
+ *   D == 128   every entry point.
+ *   D == 64    mustafar_prune_magnitude, the two-pass conversion (mustafar_compress_bitmap_{key,value}, _mirrored,
+ *              mustafar_compress_pack_{key,value}) and the fused decode through mustafar_decode_attention_hd.  At D = 64 the
+ *              K tile id is (token/64)*64 + d and the V tile id (token/64)*64 + token%64 (one tile per token): bmp [B', t],
+ *              idx [B', t + 1].  Row pointers (x, out, windows, k_new) must be 16-byte aligned (rows are moved as 16-byte pieces).
+ *              Everything else returns MUSTAFAR_EINVAL for D = 64: the two reference SpMV entry points (D = 128 in the reference),
+ *              the one-pass conversion, mustafar_cache_append_*, the trigger batch and the cache-view / extent decode forms.
  */
 #ifndef MUSTAFAR_HIP_H
 #define MUSTAFAR_HIP_H
@@ -139,6 +148,28 @@ int mustafar_decode_attention(void* stream, const uint64_t* k_bmp, const void* k
                               const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                               int heads_per_mask_row, uint32_t flags);
 int64_t mustafar_decode_workspace_bytes(int T, int Batch_Size, int num_key_value_groups, int Split_K);
+
+/*
+ * mustafar_decode_attention for a given head_dim (ABI 107).  Same arguments, same semantics, plus `head_dim`:
+ *   128  forwards to mustafar_decode_attention (the same kernels, the same output bit for bit).
+ *   64   the D = 64 kernels: q [Batch_Size, 64], windows [B', window_capacity, 64], k_new / v_new [B', 64], out [Batch_Size, 64].
+ *        One launch + a row merge: a workgroup serves one kv head and a run of 64-token blocks for all G q heads of it (key phase,
+ *        online softmax step, value phase per block), the dense window rides along as 64-row workgroups, each leaves a (max, sum,
+ *        output) slab per head and the row kernel merges them.  Group counts 1..8.  Exact fp16 x fp16 products, fp32 sums (the
+ *        v_fma_mix engine's arithmetic): every engine flag runs it; MUSTAFAR_FLAG_TWO_LAUNCH is rejected.  `scores` / `ld_scores`
+ *        are validated as for D = 128 but not written.  mustafar_last_decode_choice() reports engine 0, structure 1, form 5.
+ *        Profile records (mustafar_profile_begin): the one-pass launch as "key", the row merge as "finish".
+ *   any other value: MUSTAFAR_EINVAL.
+ * mustafar_decode_workspace_bytes_hd: the workspace of that call (0 for an unsupported head_dim).
+ */
+int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                                 const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                                 const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                                 const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                                 void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                 const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                 int heads_per_mask_row, uint32_t flags, int head_dim);
+int64_t mustafar_decode_workspace_bytes_hd(int T, int Batch_Size, int num_key_value_groups, int Split_K, int head_dim);
 
 /*
  * Compressed cache with spare capacity (extension; SURVEY 8f rank 2: the reference re-copies bitmaps, offsets and every
@@ -349,7 +380,7 @@ int mustafar_get_fma_engine(void);
 int mustafar_set_onepass(int mode);
 int mustafar_get_onepass(void);
 /* What the last fused call on the calling thread launched: FMA engine that ran (0 v_fma_mix_f32, 1 matrix pipe, 2 v_dot2_f32_f16)
- * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block, 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that);
+ * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block, 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that, 5 the head_dim 64 kernel of mustafar_decode_attention_hd);
  * -1 before the first call.  For tests and tools: a call's `flags` and the process defaults can be checked against what ran. */
 int mustafar_last_decode_choice(void);
 /* Tuning knobs for the measurement scripts under tools/ (launch shapes of the one-pass forms); not an operator interface.

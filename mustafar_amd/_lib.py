@@ -40,6 +40,9 @@ SIGNATURES = {
     "mustafar_value_workspace_bytes": (_i64, [_i32] * 6),
     "mustafar_decode_attention": (_i32, [_vp] * 14 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp,
                                          _vp, _i64, _i32, ctypes.c_uint32]),
+    "mustafar_decode_attention_hd": (_i32, [_vp] * 14 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp,
+                                            _vp, _i64, _i32, ctypes.c_uint32, _i32]),
+    "mustafar_decode_workspace_bytes_hd": (_i64, [_i32] * 5),
     "mustafar_decode_attention_view": (_i32, [_vp, _view_p, _view_p] + [_vp] * 5 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
                                               ctypes.c_float, _vp, _vp, _i64, _i32, ctypes.c_uint32]),
     "mustafar_decode_attention_extents": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp] + [_vp] * 5 +

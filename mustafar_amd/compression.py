@@ -144,13 +144,17 @@ def prune_magnitude(x: torch.Tensor, target_sparsity: float, out: torch.Tensor |
     if not x.is_cuda or x.dtype != torch.float16:
         raise RuntimeError("prune_magnitude expects a float16 tensor on the GPU")
     D = x.shape[-1]
-    if D != 128:
-        raise RuntimeError("prune_magnitude: this build supports head_dim == 128")
+    if D not in (64, 128):
+        raise RuntimeError("prune_magnitude: this build supports head_dim 64 and 128")
     xc = x.contiguous()
+    if D == 64 and xc.data_ptr() % 16:   # (the head_dim-64 kernel moves rows as 16-byte pieces)
+        xc = xc.clone()
     if out is None:
         out = torch.empty_like(xc)
     elif not (out.is_contiguous() and out.shape == xc.shape and out.dtype == xc.dtype and out.device == xc.device):
         raise RuntimeError("prune_magnitude: `out` must be a contiguous tensor like the input")
+    elif D == 64 and out.data_ptr() % 16:
+        raise RuntimeError("prune_magnitude: `out` must be 16-byte aligned at head_dim 64")
     L = _lib.load()
     with torch.cuda.device(x.device):
         err = L.mustafar_prune_magnitude(_stream_ptr(x.device), xc.data_ptr(), out.data_ptr(), xc.numel() // D, D,
@@ -249,9 +253,11 @@ def _convert(inputs: torch.Tensor, which: str, onepass: bool | None = None) -> T
     assert inputs.is_cuda
     assert inputs.dim() == 3
     assert M % 64 == 0
-    if inputs.dtype != torch.float16 or N != 128:
-        raise RuntimeError("convert_*_batched expects float16 [B', t, 128]")
+    if inputs.dtype != torch.float16 or N not in (64, 128):
+        raise RuntimeError("convert_*_batched expects float16 [B', t, 128] or [B', t, 64]")
     x = inputs.contiguous()
+    if N == 64:   # head_dim 64: the two-pass form only (whatever MUSTAFAR_CONVERT says), rows 16-byte aligned
+        return _convert_twopass(x if x.data_ptr() % 16 == 0 else x.clone(), which)
     if onepass is None:
         onepass = _CONVERT_FORM == 1 or (_CONVERT_FORM == 0 and B * M >= _CONVERT_ONEPASS_ROWS)
     if not onepass or B * M * (N // 8) > 0xffffffff:
@@ -290,10 +296,10 @@ def _convert(inputs: torch.Tensor, which: str, onepass: bool | None = None) -> T
 
 
 def convert_key_batched(inputs: torch.Tensor):
-    """kernel/compression.py:249-339.  inputs: pruned K [B', t, 128] fp16 (t % 64 == 0)."""
+    """kernel/compression.py:249-339.  inputs: pruned K [B', t, D] fp16, D in {64, 128} (t % 64 == 0)."""
     return _convert(inputs, "key")
 
 
 def convert_value_batched(inputs: torch.Tensor):
-    """kernel/compression.py:341-432.  inputs: pruned V [B', t, 128] fp16 (t % 64 == 0)."""
+    """kernel/compression.py:341-432.  inputs: pruned V [B', t, D] fp16, D in {64, 128} (t % 64 == 0)."""
     return _convert(inputs, "value")

@@ -17,6 +17,7 @@
 
 #include "../../include/mustafar_hip.h"
 #include "select_kth.h"
+#include "headdim64.h"
 
 namespace {
 
@@ -918,6 +919,7 @@ extern "C" {
 
 int mustafar_prune_magnitude(void* stream, const void* x, void* out, int64_t n_rows, int D, int kth)
 {
+    if (D == mustafar_hd64::kD) return mustafar_hd64::prune(static_cast<hipStream_t>(stream), x, out, n_rows, kth);
     if (D != kD || kth < 1 || kth > D || n_rows < 0 || !x || !out) return MUSTAFAR_EINVAL;
     if (n_rows == 0) return 0;
     const int64_t blocks = (n_rows + kPruneRows - 1) / kPruneRows;
@@ -930,23 +932,43 @@ int mustafar_prune_magnitude(void* stream, const void* x, void* out, int64_t n_r
 
 int mustafar_compress_bitmap_key(void* stream, const void* x, int Bp, int t, int D, int64_t* bmp, int32_t* accum,
                                  int64_t* head_off)
-{ return bitmap_common(true, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true); }
+{
+    if (D == mustafar_hd64::kD)
+        return mustafar_hd64::bitmap(true, static_cast<hipStream_t>(stream), x, Bp, t, bmp, accum, head_off, nullptr);
+    return bitmap_common(true, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true);
+}
 
 int mustafar_compress_bitmap_value(void* stream, const void* x, int Bp, int t, int D, int64_t* bmp, int32_t* accum,
                                    int64_t* head_off)
-{ return bitmap_common(false, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true); }
+{
+    if (D == mustafar_hd64::kD)
+        return mustafar_hd64::bitmap(false, static_cast<hipStream_t>(stream), x, Bp, t, bmp, accum, head_off, nullptr);
+    return bitmap_common(false, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true);
+}
 
 int mustafar_compress_bitmap_mirrored(void* stream, const void* x, int Bp, int t, int D, int key, int64_t* bmp, int32_t* accum, int64_t* head_off,
                                       int64_t* host_mirror)
-{ return bitmap_common(key != 0, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true, host_mirror); }
+{
+    if (D == mustafar_hd64::kD)
+        return mustafar_hd64::bitmap(key != 0, static_cast<hipStream_t>(stream), x, Bp, t, bmp, accum, head_off, host_mirror);
+    return bitmap_common(key != 0, stream, x, Bp, t, D, bmp, accum, head_off, fresh_rows(t), true, host_mirror);
+}
 
 int mustafar_compress_pack_key(void* stream, const void* x, int Bp, int t, int D, const int64_t* bmp,
                                const int32_t* accum, const int64_t* head_off, void* nz_flat)
-{ return pack_common(true, stream, x, Bp, t, D, bmp, accum, head_off, nullptr, nz_flat, fresh_rows(t)); }
+{
+    if (D == mustafar_hd64::kD)
+        return mustafar_hd64::pack(true, static_cast<hipStream_t>(stream), x, Bp, t, bmp, accum, head_off, nz_flat);
+    return pack_common(true, stream, x, Bp, t, D, bmp, accum, head_off, nullptr, nz_flat, fresh_rows(t));
+}
 
 int mustafar_compress_pack_value(void* stream, const void* x, int Bp, int t, int D, const int64_t* bmp,
                                  const int32_t* accum, const int64_t* head_off, void* nz_flat)
-{ return pack_common(false, stream, x, Bp, t, D, bmp, accum, head_off, nullptr, nz_flat, fresh_rows(t)); }
+{
+    if (D == mustafar_hd64::kD)
+        return mustafar_hd64::pack(false, static_cast<hipStream_t>(stream), x, Bp, t, bmp, accum, head_off, nz_flat);
+    return pack_common(false, stream, x, Bp, t, D, bmp, accum, head_off, nullptr, nz_flat, fresh_rows(t));
+}
 
 // ---- in-place append into a cache view (model :339-390 without the re-copies) ----------------------------------------
 int64_t mustafar_convert_scratch_bytes(int Bp, int t)

@@ -1,0 +1,31 @@
+// headdim64.h -- internal interface of headdim64.hip (head_dim 64) to the C ABI entry points of compress.hip and spmv.hip.
+// Not part of the public ABI (include/mustafar_hip.h); every function validates its own arguments and returns a hipError_t value.
+#ifndef MUSTAFAR_HEADDIM64_H
+#define MUSTAFAR_HEADDIM64_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mustafar_hd64 {
+
+constexpr int kD = 64;
+
+int prune(hipStream_t st, const void* x, void* out, int64_t n_rows, int kth);
+// pass 1 of the two-pass conversion: bmp [B', t], accum [B', t + 1], head_off [B' + 1] (halfs); mirror as mustafar_compress_bitmap_mirrored
+int bitmap(bool key, hipStream_t st, const void* x, int Bp, int t, int64_t* bmp, int32_t* accum, int64_t* head_off, int64_t* mirror);
+// pass 2: the packed streams at nz_flat + head_off[h]
+int pack(bool key, hipStream_t st, const void* x, int Bp, int t, const int64_t* bmp, const int32_t* accum, const int64_t* head_off,
+         void* nz_flat);
+
+// fused decode (the arguments of mustafar_decode_attention; flags already checked by the caller).  ev: 4 events (decode launch start /
+// stop, row-merge start / stop) or nullptr.
+int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
+           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
+           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
+           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev);
+int64_t workspace_bytes(int T, int Batch_Size, int groups);
+
+}  // namespace mustafar_hd64
+
+#endif

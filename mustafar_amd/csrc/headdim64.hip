@@ -1,0 +1,590 @@
+// headdim64.hip -- head_dim 64: magnitude prune, the two-pass conversion to the compressed format and the fused decode, for gfx950.
+//
+// The D = 128 kernels (compress.hip, spmv.hip) are tuned to a 64-token block of 128 tiles; this file is the D = 64 path, written plainly
+// (no inline assembly) and reached through the same C ABI entry points (mustafar_prune_magnitude, mustafar_compress_{bitmap,pack}_*,
+// mustafar_decode_attention_hd).  Format at D = 64 (kernel/compression.py:32-36, :87-97):
+//   K tile id = (token/64)*64 + d          64 consecutive tokens of channel d
+//   V tile id = (token/64)*64 + token%64   the 64 channels of one token
+//   bmp [B', t], idx [B', t + 1]: one tile per token and head on either side.
+//
+// Fused decode (mustafar_decode_attention's semantics): grid (x, y) = (S1 compressed workgroups + window chunks, kv head).  A workgroup is
+// one wave and serves ALL G q heads of its kv head (q in LDS), so the compressed bytes are read once per kv head.  For every 64-token
+// block of its run: the block's key stream -- one contiguous 16-byte aligned byte range -- is copied to LDS with coalesced loads, then
+//   key phase    lane = token: for each of the 64 channel tiles the bitmap (a scalar load) bit-reversed is the lane mask of the tile and
+//                the input of v_mbcnt, which ranks the lane's element in the tile's packed stream; score[g] += k * q[g][d] in fp32
+//   softmax step fp16(score) * (1/sqrt d) -> fp16 (+ mask, clamped), running max / sum per head, e = fp16(exp(x - max)) to LDS
+//   value phase  lane = channel: the block's value stream to LDS, one tile per token, o[g] += e[g][token] * v
+// Window workgroups do the same over 64 dense window rows each (and store the step's new K / V row).  Each workgroup leaves one
+// (max, sum, o[64]) slab per head; hd64_finish_kernel merges a row's slabs.  Products are fp16 x fp16, exact in fp32; sums are fp32.
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/mustafar_hip.h"
+#include "headdim64.h"
+
+namespace mustafar_hd64 {
+namespace {
+
+typedef _Float16 h16;
+typedef const __attribute__((address_space(4))) uint64_t* cu64_p;   // read-only, wave-uniform: scalar loads
+typedef const __attribute__((address_space(4))) uint32_t* cu32_p;
+
+constexpr int kScanThreads = 256;
+constexpr int kWinChunk = 64;       // window rows per window workgroup
+constexpr int kMaxWindow = 1024;    // the window capacity the slab count is sized for (as at D = 128)
+constexpr int kMaxSlabs = 1024;     // slabs of a row (compressed workgroups + window chunks)
+constexpr int kWgTarget = 4096;     // workgroups (= waves) a launch aims for: four per SIMD on 256 CUs
+
+__device__ __forceinline__ bool nonzero_h(uint32_t v) { return (v & 0x7fffu) != 0; }   // -0.0 is zero, NaN is not
+
+__device__ __forceinline__ uint32_t rank_below(uint64_t mr)   // set bits of mr below the lane
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mr >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mr, 0u));
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------ prune
+// Lane = row of 64 halfs (32 words).  thr = k-th smallest magnitude (torch.kthvalue(|x|, k), model :103), found bit by bit from the MSB:
+// thr |= b iff fewer than k magnitudes are < (thr | b).  SWAR compare: with the guard bit 0x8000 set in each half, (m | H) - (c | c << 16)
+// keeps the guard bit of a half iff that magnitude >= c (no borrow crosses the halves).  out = |x| >= thr ? x : sign-preserving zero.
+__global__ __launch_bounds__(64) void prune64_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int64_t n_rows, int kth)
+{
+    const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (row >= n_rows) return;
+    const uint32_t H = 0x80008000u, ONES = 0x00010001u;
+    uint32_t raw[32];
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        const uint4 v = x[row * 8 + p];
+        raw[4 * p] = v.x; raw[4 * p + 1] = v.y; raw[4 * p + 2] = v.z; raw[4 * p + 3] = v.w;
+    }
+    uint32_t thr = 0;
+#pragma unroll 1
+    for (int bit = 14; bit >= 0; bit--) {
+        const uint32_t c = thr | (1u << bit);
+        const uint32_t cc = c | (c << 16);
+        uint32_t ge = 0;
+#pragma unroll
+        for (int j = 0; j < 32; j++) ge += (((raw[j] | H) - cc) >> 15) & ONES;
+        const int below = 64 - (int)((ge & 0xffffu) + (ge >> 16));
+        if (below < kth) thr = c;
+    }
+    const uint32_t tt = thr | (thr << 16);
+#pragma unroll
+    for (int j = 0; j < 32; j++) {
+        const uint32_t keep = (((raw[j] | H) - tt) >> 15) & ONES;   // bit 0 / bit 16: that half is kept
+        raw[j] &= ((keep << 16) - keep) | H;                         // kept halves whole, pruned ones keep their sign bit only
+    }
+#pragma unroll
+    for (int p = 0; p < 8; p++) out[row * 8 + p] = make_uint4(raw[4 * p], raw[4 * p + 1], raw[4 * p + 2], raw[4 * p + 3]);
+}
+
+// ------------------------------------------------------------------------------------------------ conversion, pass 1
+// grid (block, head), one wave, lane = token row.  Lane l owns tile l of the block: its bitmap (MSB = element 0), its padded count
+// ceil8(nnz)/2 (compression.py:46-48) and the inclusive prefix of those counts inside the block; blk[h][tb] = the block's total.
+__global__ __launch_bounds__(64) void bitmap64_kernel(const uint16_t* __restrict__ x, int t, int key, int64_t* __restrict__ bmp,
+                                                      int32_t* __restrict__ accum, int32_t* __restrict__ blk)
+{
+    const int lane = threadIdx.x, tb = blockIdx.x, h = blockIdx.y, ntb = gridDim.x;
+    const uint4* src = reinterpret_cast<const uint4*>(x + ((int64_t)h * t + (int64_t)tb * 64 + lane) * kD);
+    uint32_t w[32];
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        const uint4 v = src[p];
+        w[4 * p] = v.x; w[4 * p + 1] = v.y; w[4 * p + 2] = v.z; w[4 * p + 3] = v.w;
+    }
+    uint64_t mine = 0;
+    if (key) {   // tile d = channel d of the 64 tokens: the ballot over the lanes (bit l = token l), bit-reversed
+#pragma unroll
+        for (int d = 0; d < 64; d++) {
+            const uint64_t b = __ballot(nonzero_h(w[d >> 1] >> (16 * (d & 1))));
+            if (lane == d) mine = __builtin_bitreverse64(b);
+        }
+    } else {     // tile = this token's row: element c at bit 63 - c
+#pragma unroll
+        for (int j = 0; j < 32; j++) {
+            mine |= (uint64_t)nonzero_h(w[j]) << (63 - 2 * j);
+            mine |= (uint64_t)nonzero_h(w[j] >> 16) << (62 - 2 * j);
+        }
+    }
+    int32_t c = ((__popcll(mine) + 7) & ~7) >> 1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t u = __shfl_up(c, o);
+        if (lane >= o) c += u;
+    }
+    const int64_t tile = (int64_t)h * t + (int64_t)tb * 64 + lane;
+    bmp[tile] = (int64_t)mine;
+    accum[tile + h + 1] = c;   // (row h of accum is t + 1 long)
+    if (lane == 63) blk[(int64_t)h * ntb + tb] = c;
+}
+
+// One workgroup per head: block totals -> exclusive bases (compression.py:294-298 at block granularity), the head's stream length in
+// halfs (:302) -> totals[h], accum[h][0] = 0.
+__global__ __launch_bounds__(kScanThreads) void scan64_kernel(int32_t* __restrict__ blk, int ntb, int t, int32_t* __restrict__ accum,
+                                                              int64_t* __restrict__ totals)
+{
+    __shared__ int32_t s_wave[kScanThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = blockIdx.x;
+    int32_t* bt = blk + (int64_t)h * ntb;
+    int32_t carry = 0;
+    for (int base = 0; base < ntb; base += kScanThreads) {
+        const int i = base + threadIdx.x;
+        const int32_t own = i < ntb ? bt[i] : 0;
+        int32_t v = own;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t u = __shfl_up(v, o);
+            if (lane >= o) v += u;
+        }
+        if (lane == 63) s_wave[wave] = v;
+        __syncthreads();
+        int32_t add = carry, tot = 0;
+        for (int k = 0; k < kScanThreads / 64; k++) {
+            if (k < wave) add += s_wave[k];
+            tot += s_wave[k];
+        }
+        if (i < ntb) bt[i] = v - own + add;
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        accum[(int64_t)h * (t + 1)] = 0;
+        totals[h] = 2 * (int64_t)carry;
+    }
+}
+
+// head_off = exclusive prefix of the heads' lengths (compression.py:303-304), [B'] = the total; in place, one workgroup.  mirror: the same
+// values stored once more, each an aligned 8-byte system-scope store, into device-visible host memory the caller polls.
+__global__ __launch_bounds__(kScanThreads) void head_off64_kernel(int64_t* __restrict__ head_off, int Bp, int64_t* mirror)
+{
+    __shared__ int64_t s_wave[kScanThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t carry = 0;
+    for (int base = 0; base < Bp; base += kScanThreads) {
+        const int i = base + threadIdx.x;
+        const int64_t own = i < Bp ? head_off[i] : 0;
+        int64_t v = own;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int64_t u = __shfl_up(v, o);
+            if (lane >= o) v += u;
+        }
+        if (lane == 63) s_wave[wave] = v;
+        __syncthreads();
+        int64_t add = carry, tot = 0;
+        for (int k = 0; k < kScanThreads / 64; k++) {
+            if (k < wave) add += s_wave[k];
+            tot += s_wave[k];
+        }
+        if (i < Bp) {
+            head_off[i] = v - own + add;
+            if (mirror) __hip_atomic_store(mirror + i, v - own + add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        head_off[Bp] = carry;
+        if (mirror) __hip_atomic_store(mirror + Bp, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+__global__ __launch_bounds__(64) void fixup64_kernel(const int32_t* __restrict__ blk_base, int t, int32_t* __restrict__ accum)
+{
+    const int tb = blockIdx.x, h = blockIdx.y;
+    accum[(int64_t)h * (t + 1) + (int64_t)tb * 64 + threadIdx.x + 1] += blk_base[(int64_t)h * gridDim.x + tb];
+}
+
+// ------------------------------------------------------------------------------------------------ conversion, pass 2
+// Non-zeros of a tile in ascending element order at its stream offset, then zeros up to ceil8(nnz) (compression.py:164-174, :309).
+// m: the tile's bitmap as stored (wave-uniform), v: the lane's element (element index = lane).
+__device__ __forceinline__ void pack_tile(uint16_t* __restrict__ dst, uint64_t m, uint16_t v, int lane)
+{
+    const uint64_t mr = __builtin_bitreverse64(m);
+    const int nnz = __popcll(mr);
+    if ((mr >> lane) & 1ull) dst[rank_below(mr)] = v;
+    if (lane >= nnz && lane < ((nnz + 7) & ~7)) dst[lane] = 0;
+}
+
+// grid (block, head), one wave.  K: lane = token (its row in registers), tile d = channel d.  V: lane = channel, tile r = token r.
+__global__ __launch_bounds__(64) void pack64_kernel(const uint16_t* __restrict__ x, int t, int key, const int64_t* __restrict__ bmp,
+                                                    const int32_t* __restrict__ accum, const int64_t* __restrict__ head_off,
+                                                    uint16_t* __restrict__ nz)
+{
+    const int lane = threadIdx.x, tb = blockIdx.x, h = blockIdx.y;
+    const int64_t tile0 = (int64_t)h * t + (int64_t)tb * 64;
+    const uint64_t bm = (uint64_t)bmp[tile0 + lane];
+    const int32_t st = accum[tile0 + h + lane];   // start of tile `lane` (half2 units)
+    uint16_t* nz_h = nz + head_off[h];
+    if (key) {
+        const uint4* src = reinterpret_cast<const uint4*>(x + (tile0 + lane) * kD);
+        uint32_t w[32];
+#pragma unroll
+        for (int p = 0; p < 8; p++) {
+            const uint4 v = src[p];
+            w[4 * p] = v.x; w[4 * p + 1] = v.y; w[4 * p + 2] = v.z; w[4 * p + 3] = v.w;
+        }
+#pragma unroll
+        for (int d = 0; d < 64; d++) {
+            const uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(bm >> 32), d) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)bm, d);
+            const int32_t s = __builtin_amdgcn_readlane(st, d);
+            pack_tile(nz_h + 2 * (int64_t)s, m, (uint16_t)(w[d >> 1] >> (16 * (d & 1))), lane);
+        }
+    } else {
+        const uint16_t* xb = x + tile0 * kD;
+#pragma unroll 8
+        for (int r = 0; r < 64; r++) {
+            const uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(bm >> 32), r) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)bm, r);
+            const int32_t s = __builtin_amdgcn_readlane(st, r);
+            pack_tile(nz_h + 2 * (int64_t)s, m, xb[r * kD + lane], lane);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ fused decode
+struct DecArgs {
+    const h16* q;          // [BH, 64]
+    float* ws_o;           // [slabs, BH, 64] unnormalised outputs
+    float* ws_ml;          // [slabs, BH, 2] (max, sum)
+    h16* k_win;            // [B', w_cap, 64]
+    h16* v_win;
+    const h16* k_new;      // [B', 64] or nullptr
+    const h16* v_new;
+    const int* w_extra;    // device step counter (graph replay) or nullptr
+    const h16* mask;       // additive fp16 mask rows or nullptr
+    int64_t mask_stride;
+    int mask_heads;
+    int T, BH, bpw, S1, w_len, w_cap;
+    float inv_sqrt_d;
+};
+
+// x = fp16(fp16(score) * (1/sqrt d)) (model :284; the product with the fp32 reciprocal, as at D = 128), then the hook's mask: an fp16
+// addition clamped at finfo(fp16).min (model :293-301).
+__device__ __forceinline__ float scaled(float acc, float inv_sqrt_d) { return (float)(h16)((float)(h16)acc * inv_sqrt_d); }
+__device__ __forceinline__ float masked(float x, h16 m) { return fmaxf((float)(h16)(x + (float)m), -65504.f); }
+
+// Online softmax step of one 64-token batch: x (lane = token, -inf beyond the window) -> e in LDS, running (max, sum), o rescaled.
+template <int G>
+__device__ __forceinline__ void softmax_step(const float (&x)[G], float (&M)[G], float (&L)[G], float (&o)[G], h16* s_e, int lane)
+{
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const float mn = fmaxf(M[g], wave_max(x[g]));
+        const float alpha = __expf(M[g] - mn);                 // (exp(-inf) = 0 before the first batch)
+        const float e = (float)(h16)__expf(x[g] - mn);         // e in fp16, as the one-pass forms at D = 128
+        L[g] = L[g] * alpha + wave_sum(e);
+        o[g] *= alpha;
+        M[g] = mn;
+        s_e[g * 64 + lane] = (h16)e;
+    }
+}
+
+// A block's packed stream [2 idx[first tile], 2 idx[first tile + 64]) halfs -> LDS (16-byte pieces: every tile's stream is padded to 8 halfs,
+// a head's stream starts on 16 bytes).  Returns the block's first offset (half2 units).
+__device__ __forceinline__ uint32_t stage_block(const uint4* __restrict__ head_nz, cu32_p idx, uint4* s_buf, int lane)
+{
+    const uint32_t i0 = idx[0], i1 = idx[64];
+    const int n16 = (int)((i1 - i0) >> 2);   // <= 64 tiles x 64 halfs / 8 = 512
+    const uint4* src = head_nz + (i0 >> 2);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int i = lane + 64 * k;
+        if (i < n16) s_buf[i] = src[i];
+    }
+    return i0;
+}
+
+template <int G, bool MASK>
+__global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restrict__ k_bmp, const uint4* __restrict__ k_nz,
+                                                         const uint32_t* __restrict__ k_idx, const uint32_t* __restrict__ k_off,
+                                                         const uint64_t* __restrict__ v_bmp, const uint4* __restrict__ v_nz,
+                                                         const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_off, DecArgs a)
+{
+    __shared__ uint4 s_buf[512];        // a block's key or value stream (at most 4096 halfs)
+    __shared__ h16 s_q[G * 64];
+    __shared__ h16 s_e[G * 64];
+    const int lane = threadIdx.x, kvh = blockIdx.y, x = blockIdx.x;
+    const int bh0 = kvh * G;
+    const uint16_t* sb = reinterpret_cast<const uint16_t*>(s_buf);
+#pragma unroll
+    for (int g = 0; g < G; g++) s_q[g * 64 + lane] = a.q[(int64_t)(bh0 + g) * kD + lane];
+    const h16* mrow[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) mrow[g] = MASK ? a.mask + (int64_t)((bh0 + g) / a.mask_heads) * a.mask_stride : nullptr;
+    float M[G], L[G], o[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) { M[g] = -INFINITY; L[g] = 0.f; o[g] = 0.f; }
+    __syncthreads();
+
+    if (x < a.S1) {
+        // ---- compressed blocks [tb0, tb1) of kv head kvh
+        const int ntb = a.T / 64;
+        const int tb0 = x * a.bpw, tb1 = min(ntb, tb0 + a.bpw);
+        const uint4* kz = k_nz + k_off[kvh];
+        const uint4* vz = v_nz + v_off[kvh];
+        for (int tb = tb0; tb < tb1; tb++) {
+            const int64_t tile0 = (int64_t)kvh * a.T + (int64_t)tb * 64;
+            const cu64_p kb = (cu64_p)(k_bmp + tile0);
+            const cu32_p ki = (cu32_p)(k_idx + tile0 + kvh);
+            const uint32_t k0 = stage_block(kz, ki, s_buf, lane);
+            __syncthreads();
+            float s[G];
+#pragma unroll
+            for (int g = 0; g < G; g++) s[g] = 0.f;
+#pragma unroll 16
+            for (int d = 0; d < 64; d++) {   // key phase: lane = token, tile d = channel d
+                const uint64_t mr = __builtin_bitreverse64(kb[d]);
+                const uint32_t off = 2 * (ki[d] - k0) + rank_below(mr);
+                const uint16_t raw = sb[off < 4096 ? off : 0];
+                const float kv = ((mr >> lane) & 1ull) ? (float)__builtin_bit_cast(h16, raw) : 0.f;
+#pragma unroll
+                for (int g = 0; g < G; g++) s[g] = __builtin_fmaf(kv, (float)s_q[g * 64 + d], s[g]);
+            }
+            float xs[G];
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                xs[g] = scaled(s[g], a.inv_sqrt_d);
+                if (MASK) xs[g] = masked(xs[g], mrow[g][tb * 64 + lane]);
+            }
+            __syncthreads();   // (s_buf is read; the value stream goes there next)
+            softmax_step<G>(xs, M, L, o, s_e, lane);
+            const cu64_p vb = (cu64_p)(v_bmp + tile0);
+            const cu32_p vi = (cu32_p)(v_idx + tile0 + kvh);
+            const uint32_t v0 = stage_block(vz, vi, s_buf, lane);
+            __syncthreads();
+#pragma unroll 16
+            for (int r = 0; r < 64; r++) {   // value phase: lane = channel, tile r = token r
+                const uint64_t mr = __builtin_bitreverse64(vb[r]);
+                const uint32_t off = 2 * (vi[r] - v0) + rank_below(mr);
+                const uint16_t raw = sb[off < 4096 ? off : 0];
+                const float vv = ((mr >> lane) & 1ull) ? (float)__builtin_bit_cast(h16, raw) : 0.f;
+#pragma unroll
+                for (int g = 0; g < G; g++) o[g] = __builtin_fmaf(vv, (float)s_e[g * 64 + r], o[g]);
+            }
+            __syncthreads();
+        }
+    } else {
+        // ---- window chunk: rows [w0, w0 + 64) of the dense window (the step's new row appended at w_len - 1)
+        const int w_len = a.w_extra ? min(a.w_len + *a.w_extra, a.w_cap) : a.w_len;
+        const int w0 = (x - a.S1) * kWinChunk;
+        if (w0 < w_len) {
+            const int w = w0 + lane;
+            const bool valid = w < w_len;
+            const int wr = valid ? w : w0;
+            const bool fresh_k = a.k_new && wr == w_len - 1;
+            h16* krow = a.k_win + ((int64_t)kvh * a.w_cap + wr) * kD;
+            const uint4* ksrc = reinterpret_cast<const uint4*>(fresh_k ? a.k_new + (int64_t)kvh * kD : krow);
+            uint4 kr[8];
+#pragma unroll
+            for (int p = 0; p < 8; p++) kr[p] = ksrc[p];
+            if (fresh_k && valid) {   // store the new key row (model :270)
+#pragma unroll
+                for (int p = 0; p < 8; p++) reinterpret_cast<uint4*>(krow)[p] = kr[p];
+            }
+            const h16* kh = reinterpret_cast<const h16*>(kr);
+            float xs[G];
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                float s = 0.f;
+#pragma unroll
+                for (int c = 0; c < kD; c++) s = __builtin_fmaf((float)kh[c], (float)s_q[g * 64 + c], s);
+                float xv = scaled(s, a.inv_sqrt_d);
+                if (MASK && valid) xv = masked(xv, mrow[g][a.T + w]);
+                xs[g] = valid ? xv : -INFINITY;
+            }
+            softmax_step<G>(xs, M, L, o, s_e, lane);
+            __syncthreads();
+            const int n = min(kWinChunk, w_len - w0);
+            for (int r = 0; r < n; r++) {   // lane = channel
+                const int ww = w0 + r;
+                h16* vrow = a.v_win + ((int64_t)kvh * a.w_cap + ww) * kD;
+                h16 v;
+                if (a.v_new && ww == w_len - 1) {
+                    v = a.v_new[(int64_t)kvh * kD + lane];
+                    vrow[lane] = v;   // store the new value row (model :309)
+                } else {
+                    v = vrow[lane];
+                }
+#pragma unroll
+                for (int g = 0; g < G; g++) o[g] = __builtin_fmaf((float)v, (float)s_e[g * 64 + r], o[g]);
+            }
+        }
+    }
+    // ---- the workgroup's slab of every head (an empty window chunk: weight zero)
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const int64_t row = (int64_t)x * a.BH + bh0 + g;
+        a.ws_o[row * kD + lane] = o[g];
+        if (lane == 0) { a.ws_ml[2 * row] = M[g]; a.ws_ml[2 * row + 1] = L[g]; }
+    }
+}
+
+// out[bh, c] = fp16( sum_s w_s o_s[c] / sum_s w_s l_s ),  w_s = exp(m_s - max m) (0 for an empty slab).  One workgroup per row, four waves
+// over the slabs (lane = channel), folded through LDS.
+__global__ __launch_bounds__(256) void hd64_finish_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, int S, int BH,
+                                                          h16* __restrict__ out)
+{
+    __shared__ float part[4][kD];
+    const int bh = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float mx = -INFINITY;
+    for (int s = lane; s < S; s += 64) mx = fmaxf(mx, ws_ml[((int64_t)s * BH + bh) * 2]);
+    const float Mx = wave_max(mx);
+    float acc = 0.f, den = 0.f;
+    for (int s = wave; s < S; s += 4) {
+        const float m = ws_ml[((int64_t)s * BH + bh) * 2], l = ws_ml[((int64_t)s * BH + bh) * 2 + 1];
+        const float w = l > 0.f ? __expf(m - Mx) : 0.f;
+        den += w * l;
+        acc += w * ws_o[((int64_t)s * BH + bh) * kD + lane];
+    }
+    part[wave][lane] = acc;
+    __shared__ float dens[4];
+    if (lane == 0) dens[wave] = den;
+    __syncthreads();
+    if (wave == 0) {
+        const float o = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+        out[(int64_t)bh * kD + lane] = (h16)(o / (dens[0] + dens[1] + dens[2] + dens[3]));
+    }
+}
+
+// blocks per compressed workgroup: ~kWgTarget workgroups over all kv heads, never more slabs per row than the row kernel takes
+inline int blocks_per_wg(int ntb, int Bp)
+{
+    if (ntb <= 0) return 1;
+    int bpw = (int)(((int64_t)ntb * Bp + kWgTarget / 2) / kWgTarget);
+    if (bpw < 1) bpw = 1;
+    while ((ntb + bpw - 1) / bpw > kMaxSlabs - kMaxWindow / kWinChunk) bpw++;
+    return bpw;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ host entry points
+int prune(hipStream_t st, const void* x, void* out, int64_t n_rows, int kth)
+{
+    // rows are read and written as 16-byte pieces
+    if (kth < 1 || kth > kD || n_rows < 0 || !x || !out || !aligned16(x) || !aligned16(out)) return MUSTAFAR_EINVAL;
+    if (n_rows == 0) return 0;
+    const int64_t blocks = (n_rows + 63) / 64;
+    if (blocks > 0x7fffffff) return MUSTAFAR_EINVAL;
+    prune64_kernel<<<(unsigned)blocks, 64, 0, st>>>(static_cast<const uint4*>(x), static_cast<uint4*>(out), n_rows, kth);
+    return (int)hipGetLastError();
+}
+
+int bitmap(bool key, hipStream_t st, const void* x, int Bp, int t, int64_t* bmp, int32_t* accum, int64_t* head_off, int64_t* mirror)
+{
+    if (Bp < 1 || t < 64 || (t & 63) || !x || !aligned16(x) || !bmp || !accum || !head_off) return MUSTAFAR_EINVAL;
+    const int ntb = t / 64;
+    int32_t* blk = nullptr;
+    bool pooled = true;
+    if (hipMallocAsync(reinterpret_cast<void**>(&blk), sizeof(int32_t) * (size_t)Bp * ntb, st) != hipSuccess) {
+        (void)hipGetLastError();
+        pooled = false;
+        if (hipMalloc(reinterpret_cast<void**>(&blk), sizeof(int32_t) * (size_t)Bp * ntb) != hipSuccess) return (int)hipGetLastError();
+    }
+    bitmap64_kernel<<<dim3(ntb, Bp), 64, 0, st>>>(static_cast<const uint16_t*>(x), t, key ? 1 : 0, bmp, accum, blk);
+    scan64_kernel<<<Bp, kScanThreads, 0, st>>>(blk, ntb, t, accum, head_off);
+    head_off64_kernel<<<1, kScanThreads, 0, st>>>(head_off, Bp, mirror);   // (in front of the fix-up: a polling caller has the sizes sooner)
+    fixup64_kernel<<<dim3(ntb, Bp), 64, 0, st>>>(blk, t, accum);
+    const int err = (int)hipGetLastError();
+    if (pooled) {
+        (void)hipFreeAsync(blk, st);
+    } else {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(blk);
+    }
+    return err;
+}
+
+int pack(bool key, hipStream_t st, const void* x, int Bp, int t, const int64_t* bmp, const int32_t* accum, const int64_t* head_off,
+         void* nz_flat)
+{
+    if (Bp < 1 || t < 64 || (t & 63) || !x || !aligned16(x) || !bmp || !accum || !head_off) return MUSTAFAR_EINVAL;
+    if (!nz_flat) return 0;   // nothing to write: every tile of every head is empty
+    pack64_kernel<<<dim3(t / 64, Bp), 64, 0, st>>>(static_cast<const uint16_t*>(x), t, key ? 1 : 0, bmp, accum, head_off,
+                                                   static_cast<uint16_t*>(nz_flat));
+    return (int)hipGetLastError();
+}
+
+int64_t workspace_bytes(int T, int Batch_Size, int groups)
+{
+    if (T < 0 || groups < 1 || Batch_Size < groups || Batch_Size % groups) return 0;
+    const int ntb = T / 64;
+    const int S1 = ntb > 0 ? (ntb + blocks_per_wg(ntb, Batch_Size / groups) - 1) / blocks_per_wg(ntb, Batch_Size / groups) : 0;
+    return (int64_t)(S1 + kMaxWindow / kWinChunk) * Batch_Size * (kD + 2) * (int64_t)sizeof(float);
+}
+
+int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
+           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
+           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
+           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev)
+{
+    if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
+    if (T < 0 || (T & 63) || groups < 1 || groups > 8 || Batch_Size < 1 || Batch_Size % groups || window_len < 1 ||
+        window_len > window_capacity || window_capacity > kMaxWindow ||
+        ld_scores < T + (window_len_extra ? window_capacity : window_len) || (ld_scores & 7) || Split_K < 1 || !(sqrt_d > 0.f))
+        return MUSTAFAR_EINVAL;
+    if (!q || !k_window || !v_window || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    // window rows (and the new rows) are read as 16-byte pieces
+    if (!aligned16(k_window) || !aligned16(v_window) || (k_new && !aligned16(k_new))) return MUSTAFAR_EINVAL;
+    if (T > 0 && (!k_bmp || !k_nz || !k_idx || !k_nz_offset || !v_bmp || !v_nz || !v_idx || !v_nz_offset)) return MUSTAFAR_EINVAL;
+    const int Bp = Batch_Size / groups, ntb = T / 64;
+    const int bpw = blocks_per_wg(ntb, Bp);
+    const int S1 = ntb > 0 ? (ntb + bpw - 1) / bpw : 0;
+    const int nchunks = (window_capacity + kWinChunk - 1) / kWinChunk;
+    float* ws_o = static_cast<float*>(workspace);
+    float* ws_ml = ws_o + (int64_t)(S1 + nchunks) * Batch_Size * kD;
+    const DecArgs a{static_cast<const h16*>(q), ws_o, ws_ml, static_cast<h16*>(k_window), static_cast<h16*>(v_window),
+                    static_cast<const h16*>(k_new), static_cast<const h16*>(v_new), window_len_extra,
+                    static_cast<const h16*>(attention_mask), mask_row_stride, heads_per_mask_row > 0 ? heads_per_mask_row : 1,
+                    T, Batch_Size, bpw, S1, window_len, window_capacity, (float)(1.0 / (double)sqrt_d)};
+    const dim3 grid(S1 + nchunks, Bp);
+    hipEvent_t e0 = ev ? ev[0] : nullptr, e1 = ev ? ev[1] : nullptr, e2 = ev ? ev[2] : nullptr, e3 = ev ? ev[3] : nullptr;
+    auto kb = k_bmp, vb = v_bmp;
+    auto kz = static_cast<const uint4*>(k_nz), vz = static_cast<const uint4*>(v_nz);
+#define MUSTAFAR_HD64(GG)                                                                                                              \
+    do {                                                                                                                               \
+        if (attention_mask)                                                                                                            \
+            hipExtLaunchKernelGGL((hd64_decode_kernel<GG, true>), grid, dim3(64), 0, st, e0, e1, 0, kb, kz, k_idx, k_nz_offset, vb, vz, \
+                                  v_idx, v_nz_offset, a);                                                                              \
+        else                                                                                                                           \
+            hipExtLaunchKernelGGL((hd64_decode_kernel<GG, false>), grid, dim3(64), 0, st, e0, e1, 0, kb, kz, k_idx, k_nz_offset, vb,   \
+                                  vz, v_idx, v_nz_offset, a);                                                                          \
+    } while (0)
+    switch (groups) {
+        case 1: MUSTAFAR_HD64(1); break;
+        case 2: MUSTAFAR_HD64(2); break;
+        case 3: MUSTAFAR_HD64(3); break;
+        case 4: MUSTAFAR_HD64(4); break;
+        case 5: MUSTAFAR_HD64(5); break;
+        case 6: MUSTAFAR_HD64(6); break;
+        case 7: MUSTAFAR_HD64(7); break;
+        default: MUSTAFAR_HD64(8); break;
+    }
+#undef MUSTAFAR_HD64
+    hipExtLaunchKernelGGL(hd64_finish_kernel, dim3(Batch_Size), dim3(256), 0, st, e2, e3, 0, ws_o, ws_ml, S1 + nchunks, Batch_Size,
+                          static_cast<h16*>(out));
+    return (int)hipGetLastError();
+}
+
+}  // namespace mustafar_hd64

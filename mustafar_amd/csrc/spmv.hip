@@ -29,6 +29,7 @@
 #include <stdlib.h>
 
 #include "../../include/mustafar_hip.h"
+#include "headdim64.h"
 
 namespace {
 
@@ -4349,7 +4350,7 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
 
 extern "C" {
 
-int mustafar_abi_version(void) { return 106; }   // 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
+int mustafar_abi_version(void) { return 107; }   // 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
 
 int Key_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const void* NZ, const uint32_t* idx,
                    const uint32_t* NZ_offset, const void* B, void* C, int M_Global, int N_Global, int K_Global,
@@ -4741,6 +4742,40 @@ int mustafar_decode_attention(void* stream, const uint64_t* k_bmp, const void* k
     return decode_attention(stream, kc, vc, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
                             workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
                             mask_row_stride, heads_per_mask_row, flags);
+}
+
+int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                                 const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                                 const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                                 const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                                 void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                 const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                 int heads_per_mask_row, uint32_t flags, int head_dim)
+{
+    if (head_dim == kD)
+        return mustafar_decode_attention(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new,
+                                         v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
+                                         num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
+    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    // every engine flag runs the one exact engine (v_fma_mix arithmetic); the two-launch structure has no D = 64 form
+    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
+    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
+    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
+    const int err = mustafar_hd64::decode(static_cast<hipStream_t>(stream), k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q,
+                                          k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace,
+                                          Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
+                                          mask_row_stride, heads_per_mask_row, prof ? g_prof.ev + 4 * g_prof.n : nullptr);
+    if (err) return err;
+    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }   // (the one-pass launch in the "key" pair, the row merge in the second)
+    t_last_choice = 0 | (1 << 4) | (5 << 8);
+    return 0;
+}
+
+int64_t mustafar_decode_workspace_bytes_hd(int T, int Batch_Size, int num_key_value_groups, int Split_K, int head_dim)
+{
+    if (head_dim == kD) return mustafar_decode_workspace_bytes(T, Batch_Size, num_key_value_groups, Split_K);
+    if (head_dim != mustafar_hd64::kD) return 0;
+    return mustafar_hd64::workspace_bytes(T, Batch_Size, num_key_value_groups);
 }
 
 int mustafar_decode_attention_view(void* stream, const mustafar_cache_view* k_cache, const mustafar_cache_view* v_cache,

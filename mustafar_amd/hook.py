@@ -197,6 +197,10 @@ class MustafarAttention:
         self.num_key_value_heads = config.num_key_value_heads
         self.num_key_value_groups = self.num_heads // self.num_key_value_heads
         self.head_dim = config.head_dim
+        if config.head_dim == 64 and (config.api != "fused" or config.arena):
+            # the reference SpMV entry points are head_dim 128 only; head_dim 64 decodes through its own fused kernel
+            raise ValueError("head_dim 64 is supported with MustafarConfig(api='fused', arena=False) only "
+                             f"(got api={config.api!r}, arena={config.arena})")
         self.Reduction_Workspace = None   # model :658: a 1-element fp16 tensor shared by all layers
 
     # ---- pruning (model :77-153) -----------------------------------------------------------------------------
@@ -326,7 +330,7 @@ class MustafarAttention:
         256 off `step_counter` (tests/test_gpu_extents.py)."""
         cfg = self.cfg
         bsz, _, q_len, D = query_states.shape
-        assert q_len == 1 and D == 128
+        assert q_len == 1 and (D == 128 or (D == 64 and self.head_dim == 64))
         BH, Bkv, groups = bsz * self.num_heads, bsz * self.num_key_value_heads, self.num_key_value_groups
         k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
         C_used = C
@@ -342,13 +346,20 @@ class MustafarAttention:
         v_w.reserve(w_len)
         dev = query_states.device
         L = _lib.load()
-        split = L.mustafar_value_pick_split_k(128, 1, C, BH, groups) if C else 1
+        if D == 64:   # the head_dim-64 kernel picks its own split (mustafar_decode_attention_hd)
+            split = 1
+            ws_bytes = L.mustafar_decode_workspace_bytes_hd(C, BH, groups, split, D)
+        else:
+            split = L.mustafar_value_pick_split_k(128, 1, C, BH, groups) if C else 1
+            ws_bytes = L.mustafar_decode_workspace_bytes(C, BH, groups, split)
         ld = (C + max(k_w.cap, v_w.cap) + 31) // 32 * 32   # rows on 64-byte lines of their own (one-pass form: mustafar_hip.h)
-        scores, ws = self._scratch(dev, BH, ld, L.mustafar_decode_workspace_bytes(C, BH, groups, split))
+        scores, ws = self._scratch(dev, BH, ld, ws_bytes)
         out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
         q = query_states if query_states.is_contiguous() else query_states.contiguous()
         kn = key_states if key_states.is_contiguous() else key_states.contiguous()
         vn = value_states if value_states.is_contiguous() else value_states.contiguous()
+        if D == 64 and kn.data_ptr() % 16:   # (the head_dim-64 kernel reads the new key row as 16-byte pieces)
+            kn = kn.clone()
         if k_w.cap != v_w.cap:
             raise RuntimeError("key/value windows must have the same capacity")
         mask_ptr, mask_stride = None, 0
@@ -398,6 +409,10 @@ class MustafarAttention:
                                                               t_device.data_ptr() if t_device is not None else None)
             elif use_arena:
                 err = L.mustafar_decode_attention_view(st, k_c.view_ptr(), v_c.view_ptr(), *tail)
+            elif D == 64:
+                err = L.mustafar_decode_attention_hd(
+                    st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,
+                    p(v_c[0]) if C else None, p(v_c[2].flat) if C else None, p(v_c[1]) if C else None, p(v_c[3]) if C else None, *tail, D)
             else:
                 err = L.mustafar_decode_attention(
                     st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,

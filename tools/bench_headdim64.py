@@ -1,0 +1,140 @@
+"""head_dim-64 decode at Llama-3.2-1B geometry: 16 layers, 32 q / 8 kv heads, D = 64, batch 8, K / V sparsity 70 %.
+
+Prints ONE JSON line.  Per cache length L (prefill of L tokens, then decode):
+  tok_s             decode tokens/s: a captured graph of one step over all layers (decode_fused with a step counter), replayed;
+                    device-event time of the replays, windows reset every 16 steps (the trigger is not part of the step)
+  kernel_us         mean device time of one layer's decode launch (mustafar_profile_*: the "key" record), finish_us the row merge
+  bytes_per_layer   bytes the step must read per layer: compressed K / V streams + bitmaps + offsets, dense window rows, q and out
+  frac_8tbs_kernel  bytes_per_layer / kernel_us over 8 TB/s;  frac_8tbs_step  16 x bytes_per_layer per step over 8 TB/s
+and, at L = 8192, prune_convert_us_per_layer: device-synchronised wall time of one layer's prefill prune + two-pass conversion of K and V.
+Needs an MI355X; it does not fall back to anything.  Usage: python tools/bench_headdim64.py [--lengths 4096,8192,32768] [--steps 64]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ctypes  # noqa: E402
+
+import torch  # noqa: E402
+
+from mustafar_amd import _lib  # noqa: E402
+from mustafar_amd.hook import MustafarAttention, MustafarConfig  # noqa: E402
+
+LAYERS, HQ, HKV, D, BATCH, S = 16, 32, 8, 64, 8, 0.7
+
+
+def stream_bytes(c) -> int:
+    bmp, idx, nzs, off = c
+    return bmp.numel() * 8 + idx.numel() * 4 + nzs.flat.numel() * 2 + off.numel() * 4
+
+
+def run_length(L: int, steps: int, dev) -> dict:
+    attn = MustafarAttention(MustafarConfig(num_attention_heads=HQ, num_key_value_heads=HKV, head_dim=D, k_sparsity=S, v_sparsity=S,
+                                            api="fused"))
+    g = torch.Generator(device=dev).manual_seed(L)
+    pasts, conv_us = [], []
+    for layer in range(LAYERS):
+        K = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+        V = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        past = attn.build_cache(K, V)
+        torch.cuda.synchronize()
+        conv_us.append((time.perf_counter() - t0) * 1e6)
+        pasts.append(attn.to_fused(past))
+        del K, V
+    C, wl = pasts[0][4], pasts[0][1].len
+    win_bytes = BATCH * HKV * (wl + 1) * D * 2 * 2
+    per_layer = stream_bytes(pasts[0][0]) + stream_bytes(pasts[0][2]) + win_bytes + 2 * BATCH * HQ * D * 2
+    q = torch.randn((BATCH, HQ, 1, D), generator=g, device=dev).half()
+    kn = torch.randn((BATCH, HKV, 1, D), generator=g, device=dev).half()
+    vn = torch.randn((BATCH, HKV, 1, D), generator=g, device=dev).half()
+    ctr = torch.zeros((1,), dtype=torch.int32, device=dev)
+    Lb = _lib.load()
+
+    def step():
+        for p in pasts:
+            attn.decode_fused(q, kn, vn, p, step_counter=ctr)
+        Lb.mustafar_counter_add(torch.cuda.current_stream().cuda_stream, ctr.data_ptr(), 1)
+
+    def reset():
+        ctr.zero_()
+
+    # ---- kernel time (profile records; eager calls, one record per layer call)
+    for _ in range(2):
+        step()
+    reset()
+    torch.cuda.synchronize()
+    n_rec = 4 * LAYERS
+    _lib.check(Lb.mustafar_profile_begin(n_rec), "mustafar_profile_begin")
+    for _ in range(4):
+        step()
+    reset()
+    k_us, v_us, f_us, recs = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _lib.check(Lb.mustafar_profile_end2(ctypes.byref(k_us), ctypes.byref(v_us), ctypes.byref(f_us), ctypes.byref(recs)), "mustafar_profile_end2")
+    assert Lb.mustafar_last_decode_choice() == (1 << 4) | (5 << 8)
+    # ---- tokens/s: graph replays of one step over all layers
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    reset()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    reset()
+    room = pasts[0][1].cap - wl - 1   # steps before the windows are full
+    per_round = max(1, min(16, room))
+    for _ in range(per_round):       # warm-up
+        graph.replay()
+    reset()
+    torch.cuda.synchronize()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    total_ms, done = 0.0, 0
+    while done < steps:
+        n = min(per_round, steps - done)
+        ev0.record()
+        for _ in range(n):
+            graph.replay()
+        ev1.record()
+        ev1.synchronize()
+        total_ms += ev0.elapsed_time(ev1)
+        done += n
+        reset()
+    step_us = total_ms * 1e3 / done
+    torch.cuda.synchronize()
+    return {"L": L, "compressed": C, "window": wl + 1, "tok_s": round(BATCH * 1e6 / step_us, 1), "step_us": round(step_us, 2),
+            "kernel_us": round(k_us.value, 3), "finish_us": round(f_us.value, 3), "records": recs.value,
+            "bytes_per_layer": per_layer, "frac_8tbs_kernel": round(per_layer / (k_us.value * 1e-6) / 8e12, 4),
+            "frac_8tbs_step": round(LAYERS * per_layer / (step_us * 1e-6) / 8e12, 4),
+            "prune_convert_us_per_layer": round(sorted(conv_us[1:])[len(conv_us[1:]) // 2], 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lengths", default="4096,8192,32768")
+    ap.add_argument("--steps", type=int, default=64)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_headdim64 needs a GPU")
+    dev = torch.device("cuda:0")
+    res = []
+    for L in (int(v) for v in args.lengths.split(",")):
+        res.append(run_length(L, args.steps, dev))
+        torch.cuda.empty_cache()
+    out = {"workload": "llama-3.2-1b decode, head_dim 64", "layers": LAYERS, "q_heads": HQ, "kv_heads": HKV, "head_dim": D, "batch": BATCH,
+           "k_sparsity": S, "v_sparsity": S, "device": torch.cuda.get_device_name(dev), "results": res,
+           "prune_convert_us_per_layer_L8192": next((r["prune_convert_us_per_layer"] for r in res if r["L"] == 8192), None)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
