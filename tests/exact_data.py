@@ -190,9 +190,11 @@ def needle_misses(out: torch.Tensor, want: torch.Tensor) -> torch.Tensor:
 
 
 # ---- float64 model of the hook's decode arithmetic on finite-gap data -------------------------------------------------------------
-def hook_model(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, groups: int):
+def hook_model(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, groups: int, mask: torch.Tensor = None):
     """The fused decode's arithmetic in float64 for pruned-but-dense K / V (fp16, the step's new row last): returns (out, bound),
-    both float64 [B, Hq, 1, D]: |kernel - out| <= bound must hold element by element.
+    both float64 [B, Hq, 1, D]: |kernel - out| <= bound must hold element by element.  mask: None, or an additive fp16 mask that
+    broadcasts to [B, Hq, 1, L], applied as the hook does (model :293-301) -- max(fp16(x + m), finfo(fp16).min), an fp16 addition --
+    to EVERY candidate x below, so that [x_lo, x_hi] still holds every x the kernels can form.
 
     The roundings that happen, and what each contributes:
       * the score s = q . k is an fp32 sum of exact fp16 products, stored as fp16.  fp32 accumulation in any order stays within
@@ -221,6 +223,9 @@ def hook_model(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, groups: int):
         acc = 128 * 2.0 ** -24 * torch.einsum("kgd,ktd->kgt", qd.abs(), Kd.abs())
         cands = [(s - acc).half().double(), (s + acc).half().double(), s.half().double()]
         xs = [f(c) for c in cands for f in (lambda c: (c / rs).half().double(), lambda c: (c.float() * inv).half().double())]
+        if mask is not None:
+            mb = mask[b].to(torch.float16).expand(Hq, 1, L).reshape(Hkv, groups, L)
+            xs = [torch.clamp(c.half() + mb, min=torch.finfo(torch.float16).min).double() for c in xs]
         x = xs[4]                                        # the quotient of the nearest rounding: the reference's x
         lo, hi = torch.stack(xs).amin(0), torch.stack(xs).amax(0)
         dx = hi - lo
@@ -236,20 +241,32 @@ def hook_model(q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, groups: int):
     return torch.stack(outs), torch.stack(bounds)
 
 
-def model_ok(out, q, K, V, C, groups, pads=None, k_sparsity: float = 0.7, v_sparsity: float = 0.7):
+def model_ok(out, q, K, V, C, groups, pads=None, k_sparsity: float = 0.7, v_sparsity: float = 0.7, mask=None, pruned=None):
     """|fused - float64 model of the hook's arithmetic| within the model's bound, element by element (hook_model), over K / V whose first
     C tokens are pruned by the oracle's rule at k_sparsity / v_sparsity.  This, not the dense comparator, holds the random-data steps:
     tests/util.py's DENSE_ULPS bar is statistical (3 fp16 ulps of the output scale) and 32 rows x 128 channels of group count 8 exceed it
     by up to 1.3x on correct outputs, where the model's bound -- what the roundings of each element allow -- holds.  pads: left padding
-    per batch entry (masked columns dropped)."""
+    per batch entry, or per batch entry and q head ([B][Hq]: one model per head, groups = 1) (masked columns dropped).  mask: a finite
+    additive fp16 mask broadcasting to [B, Hq, 1, L] (hook_model).  pruned: (Kp, Vp), the first C rows already pruned by the oracle."""
     Kp, Vp = K.clone(), V.clone()
-    Kp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(K[:, :, :C].cpu().numpy(), k_sparsity)).to(K.device)
-    Vp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(V[:, :, :C].cpu().numpy(), v_sparsity)).to(V.device)
+    if pruned is not None:
+        Kp[:, :, :C], Vp[:, :, :C] = pruned
+    else:
+        Kp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(K[:, :, :C].cpu().numpy(), k_sparsity)).to(K.device)
+        Vp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(V[:, :, :C].cpu().numpy(), v_sparsity)).to(V.device)
+    Hq = q.shape[1]
     for b in range(out.shape[0]):
         p = pads[b] if pads else 0
-        want, bound = hook_model(q[b:b + 1], Kp[b:b + 1, :, p:], Vp[b:b + 1, :, p:], groups)
-        ratio = float(((out[b:b + 1].double() - want).abs() / bound).max())
-        assert ratio <= 1.0, f"batch {b}: |fused - model| / bound = {ratio:.3f} (sparsity K {k_sparsity}, V {v_sparsity})"
+        if isinstance(p, (list, tuple)):
+            assert len(p) == Hq
+            units = [(slice(h, h + 1), slice(h // groups, h // groups + 1), int(p[h]), 1) for h in range(Hq)]
+        else:
+            units = [(slice(None), slice(None), int(p), groups)]
+        for hs, ks, pp, g in units:
+            mb = None if mask is None else mask[b:b + 1].expand(1, Hq, 1, K.shape[2])[:, hs, :, pp:]
+            want, bound = hook_model(q[b:b + 1, hs], Kp[b:b + 1, ks, pp:], Vp[b:b + 1, ks, pp:], g, mask=mb)
+            ratio = float(((out[b:b + 1, hs].double() - want).abs() / bound).max())
+            assert ratio <= 1.0, f"batch {b} heads {hs}: |fused - model| / bound = {ratio:.3f} (sparsity K {k_sparsity}, V {v_sparsity})"
 
 
 def sink_data(B: int, Hq: int, Hkv: int, L: int, gap: float, sink: np.ndarray, seed: int = 0, device="cpu", outliers: int = 4):

@@ -1,8 +1,6 @@
 """GPU: head_dim 64 -- prune and the two-pass conversion bit-exact against the reference's fixtures and the oracle, the fused decode
 (mustafar_decode_attention_hd) against the float64 model of the hook's arithmetic and on exactly checkable needle data, and the hook end
 to end at Llama-3.2-1B head geometry (32 q / 8 kv heads, D = 64) against the dense decode over the oracle-pruned cache."""
-import ctypes
-import math
 import os
 
 import numpy as np
@@ -12,12 +10,10 @@ import torch
 from oracle import oracle as orc
 from oracle.dense_ref import dense_decode_layer
 from tests.exact_data import model_ok
+from tests.hd64_util import DEV, D, S, Step, _left_pad_mask, _rand, _t, needle_data_64, needle_expect_64
 from tests.util import DENSE_ULPS, excess
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-D = 64
-S = 0.7
 CHOICE_D64 = (1 << 4) | (5 << 8)   # engine 0, structure 1 (one pass), form 5 (mustafar_hip.h)
 
 
@@ -25,10 +21,6 @@ CHOICE_D64 = (1 << 4) | (5 << 8)   # engine 0, structure 1 (one pass), form 5 (m
 def pkg():
     from mustafar_amd import _lib, compression
     return _lib.load(), compression
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 # ---- prune and conversions ---------------------------------------------------------------------------------------------------------
@@ -73,74 +65,7 @@ def test_compress_bit_exact(pkg, golden_dir, which):
         assert np.array_equal(torch.cat(nzs).cpu().numpy().view(np.uint16), np.concatenate(onz).view(np.uint16)), (B, t, s)
 
 
-# ---- fused decode through the C ABI ------------------------------------------------------------------------------------------------
-def _cache(x, which, comp):
-    from mustafar_amd.hook import nz_offset_from_idxs
-    conv = comp.convert_key_batched if which == "key" else comp.convert_value_batched
-    bmp, idx, nzs = conv(x)
-    return bmp, idx, torch.cat(nzs), nz_offset_from_idxs(idx, x.shape[0])
-
-
-class Step:
-    """Operands of one mustafar_decode_attention_hd call for K / V [B, Hkv, L, D] (the step's new row last), C of them compressed:
-    the compressed part is the oracle-pruned rows through the package's conversion, the window holds rows [C, L - 1)."""
-
-    def __init__(self, pkg, K, V, C, groups, cap=None, mask=None, extra=None):
-        L_, comp = pkg
-        self.L = L_
-        B, Hkv, n, Dd = K.shape
-        self.B, self.Hkv, self.groups, self.C, self.Dd = B, Hkv, groups, C, Dd
-        self.BH = B * Hkv * groups
-        wl = n - C
-        self.cap = cap or max(64, (wl + 63) // 64 * 64)
-        Kp = torch.from_numpy(orc.prune_magnitude(K[:, :, :C].cpu().numpy(), S)).to(DEV)
-        Vp = torch.from_numpy(orc.prune_magnitude(V[:, :, :C].cpu().numpy(), S)).to(DEV)
-        self.kc = _cache(Kp.reshape(B * Hkv, C, Dd), "key", comp) if C else None
-        self.vc = _cache(Vp.reshape(B * Hkv, C, Dd), "value", comp) if C else None
-        self.kw = torch.zeros((B, Hkv, self.cap, Dd), dtype=torch.float16, device=DEV)
-        self.vw = torch.zeros_like(self.kw)
-        self.kw[:, :, :wl - 1] = K[:, :, C:n - 1]
-        self.vw[:, :, :wl - 1] = V[:, :, C:n - 1]
-        self.kn = K[:, :, n - 1].contiguous()
-        self.vn = V[:, :, n - 1].contiguous()
-        self.wl = wl
-        self.ld = (C + self.cap + 31) // 32 * 32
-        self.scores = torch.empty((self.BH, self.ld), dtype=torch.float16, device=DEV)
-        self.ws = torch.empty((L_.mustafar_decode_workspace_bytes_hd(C, self.BH, groups, 1, Dd),), dtype=torch.uint8, device=DEV)
-        self.out = torch.empty((B, Hkv * groups, 1, Dd), dtype=torch.float16, device=DEV)
-        self.mask, self.extra = mask, extra
-
-    def call(self, q, flags=0, head_dim=None, fn=None):
-        p = lambda t: t.data_ptr() if t is not None else None
-        kc, vc = self.kc or (None,) * 4, self.vc or (None,) * 4
-        args = [torch.cuda.current_stream().cuda_stream, p(kc[0]), p(kc[2]), p(kc[1]), p(kc[3]), p(vc[0]), p(vc[2]), p(vc[1]), p(vc[3]),
-                q.data_ptr(), self.kw.data_ptr(), self.vw.data_ptr(), self.kn.data_ptr(), self.vn.data_ptr(), self.wl, self.cap,
-                self.scores.data_ptr(), self.ld, self.out.data_ptr(), self.ws.data_ptr(), 1, self.C, self.BH, self.groups,
-                ctypes.c_float(math.sqrt(self.Dd)), p(self.extra), p(self.mask), self.mask.shape[-1] if self.mask is not None else 0,
-                self.Hkv * self.groups, flags]
-        if fn is None:
-            err = self.L.mustafar_decode_attention_hd(*args, head_dim or self.Dd)
-        else:
-            err = fn(*args)
-        assert err == 0
-        return self.out
-
-
-def _rand(B, Hkv, n, groups, seed):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    K = torch.randn((B, Hkv, n, D), generator=g, device=DEV).half()
-    V = torch.randn((B, Hkv, n, D), generator=g, device=DEV).half()
-    q = torch.randn((B, Hkv * groups, 1, D), generator=g, device=DEV).half()
-    return K, V, q
-
-
-def _left_pad_mask(B, cols, pads):
-    m = torch.zeros((B, 1, 1, cols), dtype=torch.float16, device=DEV)
-    for b, p in enumerate(pads):
-        m[b, ..., :p] = torch.finfo(torch.float16).min
-    return m
-
-
+# ---- fused decode through the C ABI (operands and data: tests/hd64_util.py) -----------------------------------------------------------
 @pytest.mark.parametrize("groups", [1, 2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("C,wl", [(0, 1), (0, 70), (64, 33), (4096, 64), (4096, 130)])
 def test_decode_model(pkg, groups, C, wl):
@@ -208,40 +133,6 @@ def test_decode_graph_replay_with_window_len_extra(pkg):
 
 
 # ---- needles: exactly checkable outputs ----------------------------------------------------------------------------------------------
-SLOT, A1, QB = 8, 16.0, 8.0
-
-
-def needle_data_64(B, Hq, Hkv, n, pos, seed):
-    """K, V [B, Hkv, n, 64], q [B, Hq, 1, 64]: q head h attends to token pos[b, h] only (the D = 64 version of tests/exact_data.py).
-    Key noise multiples of 1/4 in [-1, 1]; the needle row holds A1 = 16 on the head's slot of 8 channels (8 disjoint slots per kv head),
-    q holds QB = 8 there.  Scores: needle 1024 (x = 128), any other <= 64 (x <= 8): exp(-120) is 0 in fp16 and in fp32, so the output is
-    the needle's V row (pruned when the token is compressed) exactly; V holds multiples of 2^-5."""
-    g = Hq // Hkv
-    assert g <= D // SLOT
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    K = torch.randint(-4, 5, (B, Hkv, n, D), generator=gen, device=DEV).half() * 0.25
-    V = torch.randint(-64, 65, (B, Hkv, n, D), generator=gen, device=DEV).half() * 2.0 ** -5
-    q = torch.zeros((B, Hq, 1, D), dtype=torch.float16, device=DEV)
-    for b in range(B):
-        for h in range(Hq):
-            ch = slice((h % g) * SLOT, (h % g + 1) * SLOT)
-            K[b, h // g, int(pos[b, h]), ch] = A1
-            q[b, h, 0, ch] = QB
-    return K, V, q
-
-
-def needle_expect_64(V, pos, C, groups):
-    B, Hkv, n, _ = V.shape
-    Vh = V.cpu().numpy()
-    want = np.zeros((B, Hkv * groups, 1, D), np.float16)
-    for b in range(B):
-        for h in range(Hkv * groups):
-            t = int(pos[b, h])
-            row = Vh[b, h // groups, t]
-            want[b, h, 0] = orc.prune_magnitude(row[None], S)[0] if t < C else row
-    return torch.from_numpy(want).to(DEV)
-
-
 @pytest.mark.parametrize("groups", [1, 3, 4, 8])
 def test_decode_needles_bit_exact(pkg, groups):
     B, Hkv, C, wl = 2, 2, 512, 70

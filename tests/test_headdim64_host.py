@@ -100,3 +100,123 @@ def test_hook_construction_rules_for_head_dim_64():
             MustafarAttention(MustafarConfig(head_dim=64, **kw))
     MustafarAttention(MustafarConfig(head_dim=128, api="native"))   # other head dims behave as before
     MustafarAttention(MustafarConfig(head_dim=128, api="fused", arena=True))
+
+
+# ---- the run shapes the multi-block GPU tests rely on (tests/test_gpu_headdim64_runs.py) -------------------------------------------
+def _formula(ntb, Bp):
+    """about 4096 one-wave workgroups over all kv heads, at most 1008 compressed slabs per row."""
+    bpw = max(1, (ntb * Bp + 2048) // 4096)
+    while -(-ntb // bpw) > 1008:
+        bpw += 1
+    return bpw
+
+
+def test_run_shape_table():
+    from mustafar_amd import _lib
+    from tests.hd64_util import RUN_SHAPES, run_shape
+    L = _lib.load()
+    for name, (Bp, T, bpw, S1, last) in RUN_SHAPES.items():
+        ntb = T // 64
+        assert _formula(ntb, Bp) == bpw and -(-ntb // bpw) == S1 and ntb - (S1 - 1) * bpw == last, name
+        for g in range(1, 9):   # the shape depends on B', not on the group count
+            assert run_shape(L, T, Bp * g, g) == (S1, bpw), (name, g)
+    assert {v[2] for v in RUN_SHAPES.values()} >= {1, 2, 3, 8}
+    assert any(v[4] < v[2] for v in RUN_SHAPES.values()), "no short last run in the table"
+    # the first D = 64 module's shapes all get one block per workgroup: the gap the runs module closes
+    for Bp, T in [(4, 4096), (6, 640), (2, 32768), (4, 1024), (4, 512), (8, 28 * 64)]:
+        assert run_shape(L, T, Bp * 4, 4) == (T // 64, 1)
+    assert run_shape(L, 0, 8, 4) == (0, 1)
+
+
+# ---- the D = 64 needle generator and the model's mask, checked on the CPU ----------------------------------------------------------
+@pytest.mark.parametrize("ks,vs", [(0.0, 0.0), (0.3, 0.3), (0.5, 0.8), (0.7, 0.7), (0.9, 0.0), (0.99, 0.99)])
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_needles_64_survive_the_prune_and_decide_the_output(ks, vs, k):
+    import math
+    import numpy as np
+    import torch
+    from oracle import dense_ref
+    from oracle import oracle as orc
+    from tests.hd64_util import D, needle_data_64, needle_expect_64
+    B, Hq, Hkv, n, C = 2, 16, 2, 3000, 2944       # 8 heads per kv head: every slot in use
+    rng = np.random.default_rng(k)
+    pos = np.stack([rng.choice(n, k, replace=False) for _ in range(B * Hq)]).reshape(B, Hq, k)
+    pos[0, 0, 0], pos[0, 1, 0], pos[1, 0, 0] = 0, n - 1, C - 1
+    pos = np.stack([p if len(set(p)) == k else np.arange(k) + 7 for p in pos.reshape(-1, k)]).reshape(B, Hq, k)
+    K, V, q = needle_data_64(B, Hq, Hkv, n, pos, seed=k, device="cpu")
+    Kp, Vp = K.clone(), V.clone()
+    Kp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(K[:, :, :C].numpy(), ks))
+    Vp[:, :, :C] = torch.from_numpy(orc.prune_magnitude(V[:, :, :C].numpy(), vs))
+    g = Hq // Hkv
+    x = torch.einsum("bkgd,bktd->bkgt", q.double().view(B, Hkv, g, D), Kp.double()).reshape(B, Hq, n) / math.sqrt(D)
+    top = x.topk(k + 1, -1).values
+    assert (top[..., :k] == 128).all(), "a needle's slot does not survive the prune"
+    assert (top[..., k] <= 8).all(), "a non-needle token scores above 8"
+    assert np.exp(np.float32(8 - 128)) == 0 and np.float16(np.exp(np.float32(8 - 128))) == 0   # every other weight: 0 in fp32 and fp16
+    want = needle_expect_64(V, pos, C, g, vs=vs)
+    got = dense_ref.dense_decode_layer(q, Kp, Vp, g)
+    assert torch.equal(got.double(), want.double())
+
+
+def test_a_needle_64_moved_by_one_token_fails_the_checker():
+    import numpy as np
+    from tests.hd64_util import needle_data_64, needle_expect_64
+    B, Hq, Hkv, n, C = 1, 8, 2, 400, 256
+    pos = np.array([[0, 63, 64, 255, 256, 300, 398, 399]])
+    K, V, q = needle_data_64(B, Hq, Hkv, n, pos, seed=7, device="cpu")
+    want = needle_expect_64(V, pos, C, Hq // Hkv)
+    for h, d in ((0, 1), (3, 1), (4, -1), (7, -1)):      # across block, compressed / window and new-row edges
+        moved = pos.copy()
+        moved[0, h] += d
+        miss = (needle_expect_64(V, moved, C, Hq // Hkv).float() != want.float()).any(-1).reshape(-1)
+        assert miss[h] and miss.sum() == 1
+    # a secondary needle wins once the primary one is masked, and only then
+    pos2 = np.array([[5, -1, -1, -1, 390, -1, -1, 2]])
+    K, V, q = needle_data_64(B, Hq, Hkv, n, pos, seed=7, device="cpu", pos2=pos2)
+    masked = np.zeros((B, Hq, n), bool)
+    masked[0, 0, 0] = masked[0, 4, 256] = True
+    alt = needle_expect_64(V, pos, C, Hq // Hkv, pos2=pos2, masked=masked)
+    miss = (alt.float() != want.float()).any(-1).reshape(-1)
+    assert miss.tolist() == [True, False, False, False, True, False, False, False]
+
+
+@pytest.mark.parametrize("Dd", [64, 128])
+def test_model_mask_is_the_hooks_mask(Dd):
+    import math
+    import torch
+    from tests import exact_data as xd
+    torch.manual_seed(Dd)
+    B, Hq, Hkv, n = 2, 8, 2, 300
+    K, V, q = torch.randn(B, Hkv, n, Dd).half(), torch.randn(B, Hkv, n, Dd).half(), torch.randn(B, Hq, 1, Dd).half()
+    out0, bound0 = xd.hook_model(q, K, V, Hq // Hkv)
+    zero = torch.zeros((B, 1, 1, n), dtype=torch.float16)
+    out1, bound1 = xd.hook_model(q, K, V, Hq // Hkv, mask=zero)
+    assert torch.equal(out0, out1) and torch.equal(bound0, bound1)
+    # finfo.min on the first p columns == those columns dropped (their weight is exp(-65504 - m) = 0)
+    p = 37
+    pad = zero.clone()
+    pad[..., :p] = torch.finfo(torch.float16).min
+    out2, bound2 = xd.hook_model(q, K, V, Hq // Hkv, mask=pad)
+    out3, bound3 = xd.hook_model(q, K[:, :, p:], V[:, :, p:], Hq // Hkv)
+    assert float((out2 - out3).abs().max()) <= 1e-13 and float((bound2 - bound3).abs().max()) <= 2.0 ** -25 * p * 16   # (sums in another order)
+    # a finite mask per q head: the hook's own arithmetic (fp16 scores, fp16 mask addition, fp32 softmax) sits inside the bound,
+    # and the mask matters (the unmasked output is outside it)
+    m = (-4 * torch.rand(B, Hq, 1, n)).half()
+    out4, bound4 = xd.hook_model(q, K, V, Hq // Hkv, mask=m)
+    Kr, Vr = K.float().repeat_interleave(Hq // Hkv, 1), V.float().repeat_interleave(Hq // Hkv, 1)
+    x = torch.matmul(q.float(), Kr.transpose(2, 3)).half() / math.sqrt(Dd)
+    x = torch.max(x + m, torch.tensor(torch.finfo(torch.float16).min, dtype=torch.float16))
+    hook = torch.matmul(torch.softmax(x.float(), -1), Vr).half().double()
+    assert ((hook - out4).abs() <= bound4).all()
+    assert not ((out0 - out4).abs() <= bound4).all()
+
+
+def test_threaded_oracle_prune_is_the_oracle_prune():
+    import numpy as np
+    import torch
+    from oracle import oracle as orc
+    from tests.hd64_util import oracle_prune
+    x = np.random.default_rng(4).standard_normal((3, 70000 // 3 + 1, 64)).astype(np.float16)
+    x[0, :100] = np.round(x[0, :100] * 2) / 2     # ties
+    for s in (0.0, 0.7, 0.99):
+        assert np.array_equal(oracle_prune(torch.from_numpy(x), s).numpy().view(np.uint16), orc.prune_magnitude(x, s).view(np.uint16))
