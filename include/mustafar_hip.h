@@ -380,14 +380,15 @@ int mustafar_get_fma_engine(void);
 int mustafar_set_onepass(int mode);
 int mustafar_get_onepass(void);
 /* What the last fused call on the calling thread launched: FMA engine that ran (0 v_fma_mix_f32, 1 matrix pipe, 2 v_dot2_f32_f16)
- * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block, 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that, 5 the head_dim 64 kernel of mustafar_decode_attention_hd);
+ * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block: both removed, the codes no longer occur; 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that, 5 the head_dim 64 kernel of mustafar_decode_attention_hd);
  * -1 before the first call.  For tests and tools: a call's `flags` and the process defaults can be checked against what ran. */
 int mustafar_last_decode_choice(void);
 /* Tuning knobs for the measurement scripts under tools/ (launch shapes of the one-pass forms); not an operator interface.
  * Round 6: knob 11 = the small-launch kernel (0 never, 1 launches of two blocks per workgroup that put at most one wave on every SIMD -- the
- * default, 2 every launch of two blocks per workgroup); knob 12 = bytes of key stream per block for the speculative first-chunk request
- * (an experiment that measured slower; 0 = off, the default); knob 13 = Value_SplitK_API with N_Global = 8 on the lean kernel, the pad rows read by
- * workgroups of their own behind the row-0 workgroups (1, the default) or on round 1's kernel (0). */
+ * default, 2 every launch of two blocks per workgroup); knob 13 = Value_SplitK_API with N_Global = 8 on the lean kernel, the pad rows read by
+ * workgroups of their own behind the row-0 workgroups (1, the default) or on round 1's kernel (0).
+ * Knob 0 chose among three generations of the one-pass kernel; the two older ones were removed: value 2 is accepted and does nothing,
+ * 0 and 1 return MUSTAFAR_EINVAL, and so does knob 12 (the speculative first-chunk request, an experiment that measured slower). */
 int mustafar_tune(int knob, int value);
 
 /*

@@ -35,6 +35,44 @@ namespace {
 
 typedef _Float16 h16;
 
+// ------------------------------------------------------------------------------------------------ compile-time knobs
+// Every -D knob of this file, with its default.  A knob lives here only while a file under tests/ or tools/ passes or names it;
+// experiments that were decided are folded to a constexpr next to their measurement (DESIGN.md, round history).
+//   MUSTAFAR_WAVE_TRACE         (off) wave / phase timelines: tools/wave_trace.py, wave_trace_onepass.py, clock_probe.py (macros below)
+//   MUSTAFAR_PROBE_NOSTREAM     (off) timing only, results wrong: the stream loads touch no memory (tools/traffic_items.sh)
+//   MUSTAFAR_PROBE_NOLDSWAIT    (off) timing only, results wrong: the G = 4 FMAs do not wait for their gathers (tools/build_variant.sh)
+//   MUSTAFAR_PROBE_NOMETAWAIT   removed in round 6, cannot be built: its steps consumed scalar registers that s_load_dwordx16 / x8 were
+//                               still writing -- as stream offsets of the gathers and, through the chunk bounds, of global loads -- and
+//                               took a GPU box down with a memory-access fault twice (profiles/r05_probes.txt item 3)
+//   MUSTAFAR_DOT_GUARD          the wait states that end an asm statement holding v_dot2 (see fma8_d2)
+//   MUSTAFAR_FINISH_EARLY = 20  slabs per thread that onepass_finish_kernel requests before the weights are known (round 5: 32 -> 20;
+//                               c3's rows have 36 slabs: tokens/s + 1-2 % at c3, c4 / c5 unchanged -- same-box A/B, profiles/r05_probes.txt)
+//   MUSTAFAR_META_EARLY = 1     the NEXT step's bitmaps and offsets are requested in front of this step's gathers, so that the one wait
+//                               of the step (every lgkmcnt wait is a full drain) covers LDS and scalar-memory latency at once; 0: requested
+//                               behind the gather wait and waited for behind the FMAs (rounds 1-2: two waits per step, the second one all
+//                               scalar-memory latency).  1 = the matrix-pipe pair form (its coefficients sit in LDS: c3 38.1 -> 37.6 us);
+//                               2 = experiments: the G <= 2 forms too (c2: key 10.7 -> 11.1 us, value 16.1 -> 16.5, one-pass 15.8 -> 16.3:
+//                               their launches are latency chains of a few waves, the extra scalar spills cost more than the wait saved)
+//                               and the GQA-4 vector engines (140+ scalar registers short: the compiler then spills registers that loads
+//                               are still writing -- tools/check_smem_hazards.py refuses that build)
+#ifdef MUSTAFAR_PROBE_NOMETAWAIT
+#error "MUSTAFAR_PROBE_NOMETAWAIT was removed: it uses registers a scalar load is still writing as addresses (GPU memory-access fault)"
+#endif
+#ifdef MUSTAFAR_PROBE_NOLDSWAIT
+#define MUSTAFAR_GWAIT "s_nop 0"
+#else
+#define MUSTAFAR_GWAIT "s_waitcnt lgkmcnt(0)"
+#endif
+#ifndef MUSTAFAR_DOT_GUARD
+#define MUSTAFAR_DOT_GUARD "s_nop 3\n\t"
+#endif
+#ifndef MUSTAFAR_FINISH_EARLY
+#define MUSTAFAR_FINISH_EARLY 20
+#endif
+#ifndef MUSTAFAR_META_EARLY
+#define MUSTAFAR_META_EARLY 1
+#endif
+
 // Wave timeline (tools/wave_trace.py; only in builds with -DMUSTAFAR_WAVE_TRACE): lane 0 of every SpMV wave records
 // {start, end} of the 100 MHz wall clock, its HW_ID / XCC_ID registers and its grid position (record = 4 x u64).
 #ifdef MUSTAFAR_WAVE_TRACE
@@ -138,7 +176,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <bool SKIP = false>
 __device__ __forceinline__ Stage stage_issue(const unsigned char* __restrict__ src, uint32_t len, int lane)
 {
-#ifdef MUSTAFAR_PROBE_NOSTREAM   // timing-only build (tools/ab.py): zero records -> every stream load returns zeros without
+#ifdef MUSTAFAR_PROBE_NOSTREAM   // timing-only build: zero records -> every stream load returns zeros without
     const __amdgpu_buffer_rsrc_t rsrc =   // touching memory; instruction stream, waits and LDS traffic unchanged, results wrong
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(src), (short)0, 0, 0x00020000);
 #else
@@ -150,18 +188,16 @@ __device__ __forceinline__ Stage stage_issue(const unsigned char* __restrict__ s
     u32x4 t;
     // Cache policy of the stream loads: non-temporal (aux bit 1 = nt on gfx940+).  Every stream byte is read once per launch; with
     // the default policy that traffic pushed the metadata lines out of L2 between their vector prefetch and the scalar loads
-    // that use them (c3 one-pass, pair grain: 52.3 -> 48.1 us with nt alone).  MUSTAFAR_STREAM_AUX: experiment knob.
-#ifndef MUSTAFAR_STREAM_AUX
-#define MUSTAFAR_STREAM_AUX 2
-#endif
+    // that use them (c3 one-pass, pair grain: 52.3 -> 48.1 us with nt alone).
+    constexpr int kStreamAux = 2;
     // (skipping the 1-KiB pieces that lie wholly beyond the chunk's data -- a chunk is ~1.5 KiB at 70 % sparsity -- was
     // measured in round 2: the scalar branches cost the VALU engine 2-3 %, the matrix-pipe engine nothing either way)
-    t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, MUSTAFAR_STREAM_AUX);        s.r0 = {t.x, t.y, t.z, t.w};
-    t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 1024, 0, MUSTAFAR_STREAM_AUX); s.r1 = {t.x, t.y, t.z, t.w};
+    t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, kStreamAux);        s.r0 = {t.x, t.y, t.z, t.w};
+    t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 1024, 0, kStreamAux); s.r1 = {t.x, t.y, t.z, t.w};
     if constexpr (SKIP) { s.r2 = {0u, 0u, 0u, 0u}; s.r3 = {0u, 0u, 0u, 0u}; }
     if (!SKIP || len > 2048u) {
-        t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 2048, 0, MUSTAFAR_STREAM_AUX); s.r2 = {t.x, t.y, t.z, t.w};
-        t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 3072, 0, MUSTAFAR_STREAM_AUX); s.r3 = {t.x, t.y, t.z, t.w};
+        t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 2048, 0, kStreamAux); s.r2 = {t.x, t.y, t.z, t.w};
+        t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 3072, 0, kStreamAux); s.r3 = {t.x, t.y, t.z, t.w};
     }
     return s;
 }
@@ -204,68 +240,23 @@ typedef h16 h16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
-// MUSTAFAR_META_TOUCH (experiment, off): see metab_issue_touch_at
-#ifndef MUSTAFAR_META_TOUCH
-#define MUSTAFAR_META_TOUCH 0
-#endif
 struct MetaB {         // tile metadata of one step (8 tiles) -- all SGPRs
     u32x16 bm;         // 8 bitmaps (lo, hi dwords)
     u32x8 ix;          // 8 stream offsets (half2 units)
-#if MUSTAFAR_META_TOUCH
-    uint32_t t0 = 0, t1 = 0;   // landing registers of metab_issue_touch_at's two touches (never read; they stay allocated until the wait)
-#endif
 };
-
-// MUSTAFAR_META_EARLY (default): the NEXT step's bitmaps and offsets are requested in front of this step's gathers, so that the one
-// wait of the step (every lgkmcnt wait is a full drain) covers LDS and scalar-memory latency at once; 0: requested behind the
-// gather wait and waited for behind the FMAs (rounds 1-2: two waits per step, the second one all scalar-memory latency).
-// 1 = the matrix-pipe pair form (its coefficients sit in LDS: c3 38.1 -> 37.6 us); 2 = experiments: the G <= 2 forms too (c2: key 10.7 ->
-// 11.1 us, value 16.1 -> 16.5, one-pass 15.8 -> 16.3: their launches are latency chains of a few waves, the extra scalar spills cost
-// more than the wait saved) and the GQA-4 vector engines (140+ scalar registers short: the compiler then spills registers that loads
-// are still writing -- tools/check_smem_hazards.py).
-#ifndef MUSTAFAR_META_EARLY
-#define MUSTAFAR_META_EARLY 1
-#endif
 
 // Issue the scalar loads of the bitmaps / offsets of step S of a chunk (byte offsets are immediates).  Nothing may
 // read `m` before a metab_wait() that follows.
-#ifdef MUSTAFAR_PROBE_HOTMETA   // timing-only build: every wave reads the SAME 256 + 128 bytes of metadata (scalar-cache hits);
-__device__ uint64_t g_hot_bmp[32] = {   // ~30 % dense masks; results are wrong, the instruction stream is unchanged
-    0x1249249249249249ull, 0x2492492492492492ull, 0x4924924924924924ull, 0x9249249249249249ull, 0x1111111144444444ull, 0x0f0f00ff00f0f00full,
-    0x1249249249249249ull, 0x2492492492492492ull, 0x4924924924924924ull, 0x9249249249249249ull, 0x1111111144444444ull, 0x0f0f00ff00f0f00full,
-    0x1249249249249249ull, 0x2492492492492492ull, 0x4924924924924924ull, 0x9249249249249249ull, 0x1111111144444444ull, 0x0f0f00ff00f0f00full,
-    0x1249249249249249ull, 0x2492492492492492ull, 0x4924924924924924ull, 0x9249249249249249ull, 0x1111111144444444ull, 0x0f0f00ff00f0f00full,
-    0x1249249249249249ull, 0x2492492492492492ull, 0x4924924924924924ull, 0x9249249249249249ull, 0x1111111144444444ull, 0x0f0f00ff00f0f00full,
-    0x1249249249249249ull, 0x2492492492492492ull};
-__device__ uint32_t g_hot_idx[32] = {0, 12, 24, 36, 48, 60, 72, 84, 96, 108, 120, 132, 144, 156, 168, 180,
-                                     192, 204, 216, 228, 240, 252, 264, 276, 288, 300, 312, 324, 336, 348, 360, 372};
-#endif
-
 template <int S>
 __device__ __forceinline__ void metab_issue(MetaB& m, const uint64_t* __restrict__ bmp, const uint32_t* __restrict__ idx)
 {
-#ifdef MUSTAFAR_PROBE_HOTMETA
-    bmp = g_hot_bmp;
-    idx = g_hot_idx;
-#endif
     asm volatile("s_load_dwordx16 %0, %2, %4\n\ts_load_dwordx8 %1, %3, %5"
                  : "=&s"(m.bm), "=&s"(m.ix)
                  : "s"(bmp), "s"(idx), "i"(S * 64), "i"(S * 32));
 }
-#ifdef MUSTAFAR_PROBE_NOMETAWAIT
-// (rounds 3-5 had a timing-only build here whose next step did not wait for its metadata.  It consumed scalar registers that
-// s_load_dwordx16 / x8 were still writing -- as STREAM OFFSETS of the gathers and, through the chunk bounds, of global loads -- and
-// took a GPU box down with a memory-access fault twice (profiles/r05_probes.txt item 3).  Removed in round 6: it cannot be built.)
-#error "MUSTAFAR_PROBE_NOMETAWAIT was removed: it uses registers a scalar load is still writing as addresses (GPU memory-access fault)"
-#endif
-#if MUSTAFAR_META_TOUCH
-#define MUSTAFAR_MOPS_T , "+s"(m.t0), "+s"(m.t1)
-#else
-#define MUSTAFAR_MOPS_T
-#endif
-__device__ __forceinline__ void metab_wait(MetaB& m) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(m.bm), "+s"(m.ix) MUSTAFAR_MOPS_T); }
+__device__ __forceinline__ void metab_wait(MetaB& m) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(m.bm), "+s"(m.ix)); }
 // Ordering point without an instruction: legal right after a wait that already drained the counter.
-__device__ __forceinline__ void metab_ready(MetaB& m) { asm volatile("" : "+s"(m.bm), "+s"(m.ix) MUSTAFAR_MOPS_T); }
+__device__ __forceinline__ void metab_ready(MetaB& m) { asm volatile("" : "+s"(m.bm), "+s"(m.ix)); }
 
 // Coefficients of step S: per head 8 halfs (4 dwords).  ONE buffer: the loads of step S are issued after the FMAs of
 // step S - 1 have issued and land during the gather phase of step S (whose wait drains them too) -- a second buffer
@@ -292,17 +283,12 @@ struct Gathered {
     uint32_t t[8];   // gathered halfs (VGPRs; meaningful only in lanes whose bit is set, and only after gather_wait)
 };
 
-#ifdef MUSTAFAR_PROBE_NOGATHER   // timing-only build: no LDS gather (the address stands in for the value); results wrong
-#define MUSTAFAR_GATHER_LD(j) "v_mov_b32 %[t" #j "], %[t" #j "]\n\t"
-#else
-#define MUSTAFAR_GATHER_LD(j) "ds_read_u16 %[t" #j "], %[t" #j "]\n\t"
-#endif
 #define MUSTAFAR_GATHER(j)                                                  \
     "s_lshl2_add_u32 %[u" #j "], %[o" #j "], %[adj]\n\t"                     \
     "v_mbcnt_lo_u32_b32 %[t" #j "], %[l" #j "], 0\n\t"                        \
     "v_mbcnt_hi_u32_b32 %[t" #j "], %[h" #j "], %[t" #j "]\n\t"               \
     "v_lshl_add_u32 %[t" #j "], %[t" #j "], 1, %[u" #j "]\n\t"                \
-    MUSTAFAR_GATHER_LD(j)
+    "ds_read_u16 %[t" #j "], %[t" #j "]\n\t"
 #define MUSTAFAR_GOPS(j) [l##j] "s"((uint32_t)g.m[j]), [h##j] "s"((uint32_t)(g.m[j] >> 32)), [o##j] "s"(m.ix[j])
 
 // Gather the 8 tiles of a step from the wave's LDS window (no wait).
@@ -324,12 +310,8 @@ __device__ __forceinline__ void gather8(const MetaB& m, uint32_t adj, Gathered& 
                  : "scc");
 }
 
-// Drains the counter: the gathers AND the coefficient loads issued before them.
-#ifdef MUSTAFAR_PROBE_NOLDSWAIT   // timing-only build: the FMAs do not wait for the gathers (nor the coefficients); results wrong
-#define MUSTAFAR_GWAIT "s_nop 0"
-#else
-#define MUSTAFAR_GWAIT "s_waitcnt lgkmcnt(0)"
-#endif
+// Drains the counter: the gathers AND the coefficient loads issued before them.  (MUSTAFAR_GWAIT: a wait, or nothing in the
+// MUSTAFAR_PROBE_NOLDSWAIT timing build)
 template <int G>
 __device__ __forceinline__ void gather_wait(Gathered& g, u32x4 (&c)[G])
 {
@@ -572,16 +554,9 @@ __device__ __forceinline__ uint32_t pad_row_mask(const h16* __restrict__ dense, 
 
 // The same question for a GROUP of consecutive token chunks (round 6, value_lean_kernel's pad workgroups): bit 8 c + n of the result is set iff pad row
 // n (1 <= n < N) holds a non-zero for any of the G heads over chunk c of [col0, col0 + ncols) (chunks of chunk_cols columns, at most four; ncols % 8 == 0).
-// Written for memory-level parallelism -- a thread's loads are independent and MUSTAFAR_PAD_UNROLL of them are in flight per trip; a row's slice is one contiguous run.
-#ifndef MUSTAFAR_PROBE_N1AS8
-#define MUSTAFAR_PROBE_N1AS8 0    // (timing probe, with MUSTAFAR_PROBE_NOPADWG: 8-row calls run the N = 1 instantiation on row 0 at the 8-row pitch of the dense operand; the output layout is wrong)
-#endif
-#ifndef MUSTAFAR_PAD_UNROLL
-#define MUSTAFAR_PAD_UNROLL 4
-#endif
-#ifndef MUSTAFAR_PAD_GROUP
-#define MUSTAFAR_PAD_GROUP 4      // token chunks per pad workgroup (at most 4: a byte of the mask per chunk)
-#endif
+// Written for memory-level parallelism -- a thread's loads are independent and kPadUnroll of them are in flight per trip; a row's slice is one contiguous run.
+constexpr int kPadUnroll = 4;     // 16-byte loads in flight per thread and trip (the hook's pads are ~14 vectors per thread: four trips; other depths were not measured)
+constexpr int kPadGroup  = 4;     // token chunks per pad workgroup (at most 4: a byte of the mask per chunk)
 template <int G, int N>
 __device__ __forceinline__ uint32_t pad_group_mask(const h16* __restrict__ dense, int64_t row_len, int bh0, int col0, int ncols, int chunk_cols,
                                                    uint32_t* sh_mask)
@@ -595,10 +570,10 @@ __device__ __forceinline__ uint32_t pad_group_mask(const h16* __restrict__ dense
     const int dr = nthr / V, dk = nthr - dr * V;
     uint32_t mine = 0;
     while (r < R) {
-        u32x4 v[MUSTAFAR_PAD_UNROLL];
-        int rr[MUSTAFAR_PAD_UNROLL], kk[MUSTAFAR_PAD_UNROLL];
+        u32x4 v[kPadUnroll];
+        int rr[kPadUnroll], kk[kPadUnroll];
 #pragma unroll
-        for (int i = 0; i < MUSTAFAR_PAD_UNROLL; i++) {
+        for (int i = 0; i < kPadUnroll; i++) {
             rr[i] = r;
             kk[i] = k;
             v[i] = u32x4{0u, 0u, 0u, 0u};
@@ -611,7 +586,7 @@ __device__ __forceinline__ uint32_t pad_group_mask(const h16* __restrict__ dense
             if (k >= V) { k -= V; r++; }
         }
 #pragma unroll
-        for (int i = 0; i < MUSTAFAR_PAD_UNROLL; i++)
+        for (int i = 0; i < kPadUnroll; i++)
             if ((v[i].x | v[i].y | v[i].z | v[i].w) & 0x7fff7fffu) mine |= 1u << (8 * ((kk[i] * 8) / chunk_cols) + 1 + rr[i] % (N - 1));   // (-0.0 counts as zero)
     }
     if (mine) atomicOr(sh_mask, mine);
@@ -687,11 +662,7 @@ __device__ __forceinline__ void key_tokblk(unsigned char* smem, uint32_t lds_off
             const h16x2* cp[G];
 #pragma unroll
             for (int h = 0; h < G; h++) cp[h] = qw + h * chead + c * (kChunkTiles / 2);
-            #ifdef MUSTAFAR_PROBE_HOTMETA
-            const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr);   // the fixed offsets of g_hot_idx stay inside the window
-#else
             const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr - 4u * i0);
-#endif
             if constexpr (MF && G == 4) {
                 if (c == 0)      chunk32_mfma<0>(adj, bmp_t, idx_t, ctab_lane, accv);
                 else if (c == 1) chunk32_mfma<64>(adj, bmp_t + kChunkTiles, idx_t + kChunkTiles, ctab_lane, accv);
@@ -866,13 +837,8 @@ __device__ __forceinline__ void value_window_wg(unsigned char* smem, const h16* 
 // grid: x = ceil(T/256) token super-blocks (SPLIT = 1: one wave per 64-token block) or ceil(T/128) (SPLIT = 2: two
 // waves per token block, 64 channels each, partial scores folded through LDS -- twice the workgroups, half as long:
 // used when the SPLIT = 1 grid would fit on the chip in a single round), y = kv-heads * (groups / G)
-#ifndef MUSTAFAR_KEY_WAVES      // experiment knob (tools/build_variant.sh): minimum waves per SIMD the key kernel is compiled for
-#define MUSTAFAR_KEY_BOUNDS __launch_bounds__(kThreads)
-#else
-#define MUSTAFAR_KEY_BOUNDS __launch_bounds__(kThreads, MUSTAFAR_KEY_WAVES)
-#endif
 template <int G, bool MF, int SPLIT>
-__global__ MUSTAFAR_KEY_BOUNDS void key_spmv_kernel(
+__global__ __launch_bounds__(kThreads) void key_spmv_kernel(
     const uint64_t* __restrict__ bmp, const unsigned char* __restrict__ nz, const uint32_t* __restrict__ idx,
     const uint32_t* __restrict__ nz_off, const h16* __restrict__ q, h16* __restrict__ out, int T, int N, int groups,
     int ldc, WinArgs wa, int64_t bmp_stride, int64_t idx_stride, uint32_t nz_stride)
@@ -938,9 +904,6 @@ __global__ MUSTAFAR_KEY_BOUNDS void key_spmv_kernel(
             const h16x2* qw = reinterpret_cast<const h16x2*>(q + ((int64_t)bh0 * N + n) * kD);
             if (tb < ntb) {
                 if constexpr (SPLIT == 1) {
-#ifdef MUSTAFAR_PROBE_REPEAT   // timing-only build: every wave processes its token block MUSTAFAR_PROBE_REPEAT times (warm-cache cost per block)
-                    for (int rep = 0; rep < MUSTAFAR_PROBE_REPEAT; rep++)
-#endif
                     key_tokblk<G, MF, 0, 4>(smem, wave * kStageBytes, bmp_t, idx_t, nz_h, qw, chead, lane, acc, ctab_lane);
                 } else {
                     if (part == 0) key_tokblk<G, MF, 0, 2>(smem, wave * kStageBytes, bmp_t, idx_t, nz_h, qw, chead, lane, acc, ctab_lane);
@@ -1046,11 +1009,7 @@ __device__ __forceinline__ void value_tokblks(unsigned char* smem, uint32_t lds_
             const h16x2* cp[G];
 #pragma unroll
             for (int h = 0; h < G; h++) cp[h] = pw + h * chead + ((uint32_t)tb * 64u + (c & 1) * 32u) / 2u;
-            #ifdef MUSTAFAR_PROBE_HOTMETA
-            const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr);   // the fixed offsets of g_hot_idx stay inside the window
-#else
             const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr - 4u * i0);
-#endif
             if constexpr (MF && G == 4) {
                 if (c == 0)      chunk32_mfma<0>(adj, bmp_t, idx_t, ctab_lane, accv0);
                 else if (c == 1) chunk32_mfma<64>(adj, bmp_t + kChunkTiles, idx_t + kChunkTiles, ctab_lane, accv0);
@@ -1089,16 +1048,8 @@ __device__ __forceinline__ void value_tokblks(unsigned char* smem, uint32_t lds_
 // wave does.
 //   direct != 0 (one chunk): fp16 results go straight to `out`;
 //   else fp32 partial slabs ws[(s*BH + bh)*N + n][128] + one row mask per workgroup in `flags`.
-#ifndef MUSTAFAR_VALUE_MF_WAVES   // experiment knob (tools/build_variant.sh): minimum waves per SIMD of the matrix-pipe value kernels
-#define MUSTAFAR_VALUE_BOUNDS __launch_bounds__(NW * 64)
-#else
-#define MUSTAFAR_VALUE_BOUNDS __launch_bounds__(NW * 64, MF ? MUSTAFAR_VALUE_MF_WAVES : 1)
-#endif
-#ifndef MUSTAFAR_PAD_LATE
-#define MUSTAFAR_PAD_LATE 0   // (0 = the pad rows are read and reduced in front of row 0, rounds 1-5; 1 = requested in front, looked at behind row 0; 2 = read and looked at behind row 0)
-#endif
 template <int G, bool MF, int NW, int SPLIT, bool WIN = true>   // WIN = false: no window workgroups in the launch (the reference entry point): round 5, as key_lean_kernel
-__global__ MUSTAFAR_VALUE_BOUNDS void value_spmv_kernel(
+__global__ __launch_bounds__(NW * 64) void value_spmv_kernel(
     const uint64_t* __restrict__ bmp, const unsigned char* __restrict__ nz, const uint32_t* __restrict__ idx,
     const uint32_t* __restrict__ nz_off, const h16* __restrict__ p, h16* __restrict__ out, float* __restrict__ ws,
     uint32_t* __restrict__ flags, int T, int N, int groups, int BH, int tb_per_wg, int direct, int ldb, WinArgs wa,
@@ -1141,50 +1092,16 @@ __global__ MUSTAFAR_VALUE_BOUNDS void value_spmv_kernel(
 
     uint32_t rows = 1u;
     // Pad rows (N > 1; the hook's seven zero rows, llama_mustafar_kernel.py:313): they must be READ to be known zero -- 28 MB per call at c3.
-    // Round 6 measured WHERE in the workgroup's life they are read (MUSTAFAR_PAD_LATE; c3, N = 8, us per call, same box): in front of row 0
-    // (rounds 1-5, the default) 38.6-40.0; requested in front and looked at behind row 0 (1) 42.6-43.9 -- sixteen more registers, and loads return
-    // in order, so the first stream chunk waits for them all the same; read and looked at behind row 0 (2) 39.7-42.0, c5 109 against 103.  The call
-    // moves 1.43 x the bytes of the N = 1 call and takes 1.49 x its time: it is the bytes, not their place (profiles/r06_probes.txt item 5).
-    constexpr int kPadRegs = 4;   // 16-byte pieces per thread kept in flight: G x 7 rows x 256 tokens over 256 threads = 3.5
-    uint4 padv[kPadRegs];
-    const int pad_cols = (tb_end - tb0) * 64, pad_per_row = pad_cols / 8;
-    const int npad = N > 1 ? G * (N - 1) * pad_per_row : 0;
-    const bool pad_regs = N > 1 && npad <= kPadRegs * NW * 64 && MUSTAFAR_PAD_LATE == 1;
-    if (pad_regs) {
-#pragma unroll
-        for (int i = 0; i < kPadRegs; i++) {
-            const int u = min((int)threadIdx.x + i * NW * 64, npad - 1);   // (no divergent branch in front of the rows' asm statements: a lane beyond the slice repeats its last piece)
-            const int hn = u / pad_per_row, k = u % pad_per_row;
-            const int h = hn / (N - 1), n = 1 + hn % (N - 1);
-            padv[i] = *reinterpret_cast<const uint4*>(p + ((int64_t)(bh0 + h) * N + n) * ldb + tb0 * 64 + k * 8);
-        }
-        __builtin_amdgcn_sched_barrier(0);   // (the requests stay in front of row 0: without it the compiler sinks them to their use behind it)
-    } else if (N > 1 && MUSTAFAR_PAD_LATE != 2) {
-        rows |= pad_row_mask<G>(p, ldb, bh0, N, tb0 * 64, pad_cols, reinterpret_cast<uint32_t*>(smem));
+    // They are read and reduced in FRONT of row 0.  Round 6 measured the other places (c3, N = 8, us per call, same box): in front of row 0
+    // 38.6-40.0; requested in front and looked at behind row 0 42.6-43.9 -- sixteen more registers, and loads return in order, so the first
+    // stream chunk waits for them all the same; read and looked at behind row 0 39.7-42.0, c5 109 against 103.  The call moves 1.43 x the
+    // bytes of the N = 1 call and takes 1.49 x its time: it is the bytes, not their place (profiles/r06_probes.txt item 5).
+    if (N > 1) {
+        rows |= pad_row_mask<G>(p, ldb, bh0, N, tb0 * 64, (tb_end - tb0) * 64, reinterpret_cast<uint32_t*>(smem));
         if (!direct && threadIdx.x == 0) flags[blockIdx.x * gridDim.y + by] = rows;   // (no window rows when N > 1)
     }
 
     for (int n = 0; n < N; n++) {
-        if (n == 1 && MUSTAFAR_PAD_LATE == 2) {   // (2: the slice is read AND looked at behind row 0 -- nothing in front of the workgroup's first stream request)
-            rows |= pad_row_mask<G>(p, ldb, bh0, N, tb0 * 64, pad_cols, reinterpret_cast<uint32_t*>(smem));
-            if (!direct && threadIdx.x == 0) flags[blockIdx.x * gridDim.y + by] = rows;
-        }
-        if (n == 1 && pad_regs) {   // (workgroup-uniform) row 0 is done: which pad rows hold a non-zero in this workgroup's columns?
-            uint32_t* sh_mask = reinterpret_cast<uint32_t*>(smem);   // (behind the barrier that ended row 0: the stage windows are free)
-            if (threadIdx.x == 0) *sh_mask = 0u;
-            __syncthreads();
-            uint32_t mine = 0;
-#pragma unroll
-            for (int i = 0; i < kPadRegs; i++) {
-                const int u = threadIdx.x + i * NW * 64;
-                if (u < npad && nzbits(padv[i])) mine |= 1u << (1 + (u / pad_per_row) % (N - 1));
-            }
-            if (mine) atomicOr(sh_mask, mine);
-            __syncthreads();
-            rows |= (uint32_t)__builtin_amdgcn_readfirstlane((int)*sh_mask);   // (wave-uniform, and known to the compiler as such: the rows' asm statements own EXEC)
-            __syncthreads();
-            if (!direct && threadIdx.x == 0) flags[blockIdx.x * gridDim.y + by] = rows;
-        }
         const bool live = (rows >> n) & 1u;
         if (!live && !direct) continue;   // the combine pass skips this row of this slab
         float acc0[G], acc1[G];
@@ -1243,9 +1160,7 @@ __global__ __launch_bounds__(256) void value_combine_kernel(const float* __restr
     uint32_t mine = 0;
     if (N > 1) {
         if (threadIdx.x == 0) any_rows = 0u;
-#ifndef MUSTAFAR_PROBE_NOPADWG   // (that timing probe leaves the masks unwritten: take them as "row 0 only")
         for (int k = threadIdx.x; k < S; k += 256) mine |= flags[k * gy + y];   // (requested in front of row 0's loads)
-#endif
     }
     {
         const float* src = ws + (int64_t)bh * N * kD + c;
@@ -1641,9 +1556,6 @@ struct OneArgs {   // operands of the one-pass launch beyond the two caches (by 
     // workgroups of a launch's LAST, nearly empty round (a cache a trigger or two past one resident round of workgroups: T = 8448 at c3's
     // geometry is 2112 workgroups on 2048 slots) start when the first slots free up and would otherwise crawl along at an eighth of a SIMD
     int hi_prio_from = 0x7fffffff;
-    // round 6 (experiment, mustafar_tune(12, bytes)): expected bytes of key stream per 64-token block; > 0: a wave asks for the lines around
-    // the PREDICTED position of its first key chunk next to its bounds load (see decode_onepass_sb_kernel)
-    int spec_k_bytes = 0;
 };
 
 // Window workgroup: 64 window tokens of one head batch -> scores, softmax partial, p.V partial -> slab (S + chunk).
@@ -1780,207 +1692,6 @@ __device__ __forceinline__ void onepass_window_wg(unsigned char* smem, const Win
     if (tid < 2 * G) slab_ml[tid] = ml[tid];
 }
 
-// grid: x = token chunks (tb_per_wg blocks each), y = kv-heads * (groups / G) (+ win_rows leading rows of window
-// workgroups).  4 waves; PAIR = false: wave w takes blocks tb0 + w, tb0 + w + 4, ... whole; PAIR = true: two waves share a
-// block -- 64 channels each in the key phase (partial scores folded through LDS), one 64-channel half of the output each in
-// the value phase -- and the workgroup walks two blocks at a time with two barriers per step.  The finer grain is what the
-// VALU engine wants (its two-launch forms of the same grain: key 24.6 vs 25.8 us, value 29.5 vs 34.9 us at c3); the
-// matrix-pipe engine is faster with whole blocks.
-template <int G, bool MF, bool PAIR>
-__global__ __launch_bounds__(kThreads, MF ? 5 : 1) void decode_onepass_kernel(   // (matrix-pipe form: 97 registers unbounded, one over the 5-wave step)
-    const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
-    const uint32_t* __restrict__ k_nz_off, const uint64_t* __restrict__ v_bmp, const unsigned char* __restrict__ v_nz,
-    const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_nz_off, OneArgs a, int64_t k_bmp_stride,
-    int64_t k_idx_stride, uint32_t k_nz_stride, int64_t v_bmp_stride, int64_t v_idx_stride, uint32_t v_nz_stride)
-{
-    constexpr int kTabBytes = (MF && G == 4) ? 4 * kKeyTabStride + kWaves * 4 * kValTabStride : 0;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[kWaves * kStageBytes + kTabBytes];
-    static_assert(kWaves * kStageBytes >= (kWaves * 2 * 4 * 64 + 2 * kWaves * 4) * 4, "combine buffers must fit in the stage area");
-    MUSTAFAR_PTRACE_BEGIN();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int S = gridDim.x;
-    if ((int)blockIdx.y < a.win_rows) {   // dense window
-        const int task = blockIdx.y * gridDim.x + blockIdx.x;
-        if (task < (int)(gridDim.y - a.win_rows) * a.nchunks) onepass_window_wg<G>(smem, win_args(a), task, S);
-        MUSTAFAR_PTRACE_END(5);
-        return;
-    }
-    const int by = blockIdx.y - a.win_rows;
-    const int hb_per_kv = a.groups / G;
-    const int kvh = by / hb_per_kv;
-    const int bh0 = kvh * a.groups + (by % hb_per_kv) * G;
-    const int ntb = a.T >> 6;
-    const int tb0 = blockIdx.x * a.tb_per_wg;
-    const int tb_end = min(ntb, tb0 + a.tb_per_wg);
-    const int64_t tiles = (int64_t)ntb * kTilesPerTb;
-    const uint64_t* kb = k_bmp + (int64_t)kvh * (k_bmp_stride ? k_bmp_stride : tiles);
-    const uint32_t* ki = k_idx + (int64_t)kvh * (k_idx_stride ? k_idx_stride : tiles + 1);
-    const unsigned char* kn = k_nz + 16ull * (k_nz_stride ? (uint64_t)kvh * k_nz_stride : (uint64_t)k_nz_off[kvh]);
-    const uint64_t* vb = v_bmp + (int64_t)kvh * (v_bmp_stride ? v_bmp_stride : tiles);
-    const uint32_t* vi = v_idx + (int64_t)kvh * (v_idx_stride ? v_idx_stride : tiles + 1);
-    const unsigned char* vn = v_nz + 16ull * (v_nz_stride ? (uint64_t)kvh * v_nz_stride : (uint64_t)v_nz_off[kvh]);
-    const h16x2* qw = reinterpret_cast<const h16x2*>(a.q + (int64_t)bh0 * kD);
-    h16* erow = a.e_rows + (int64_t)bh0 * a.ld;
-    const h16x2* pw = reinterpret_cast<const h16x2*>(erow);
-    const h16* mrow = a.mask.ptr ? a.mask.ptr + (int64_t)(bh0 / a.mask.heads) * a.mask.stride : nullptr;
-
-    uint32_t ctab_lane = 0;
-    unsigned char* ptab = nullptr;
-    if constexpr (MF && G == 4) {   // key-side coefficient table: the q rows of the 4 heads (as key_spmv_kernel)
-        unsigned char* tab = smem + kWaves * kStageBytes;
-        if (threadIdx.x < 64)
-            *reinterpret_cast<uint4*>(tab + (threadIdx.x >> 4) * kKeyTabStride + (threadIdx.x & 15) * 16) =
-                *reinterpret_cast<const uint4*>(a.q + (int64_t)(bh0 + (threadIdx.x >> 4)) * kD + (threadIdx.x & 15) * 8);
-        __syncthreads();
-        ctab_lane = (uint32_t)reinterpret_cast<uintptr_t>(tab) + (lane & 3) * kKeyTabStride;
-        ptab = tab + 4 * kKeyTabStride + wave * (4 * kValTabStride);
-    }
-
-    static_assert(!(MF && PAIR), "the matrix-pipe engine runs whole blocks per wave");
-    float m_run[G], l_lane[G], acc0[G], acc1[G];   // (m_run, l_lane: wave-uniform, in scalar registers)
-#pragma unroll
-    for (int h = 0; h < G; h++) { m_run[h] = -INFINITY; l_lane[h] = 0.f; acc0[h] = 0.f; acc1[h] = 0.f; }
-    // softmax step of one block on the lanes' scores s[] (lane = token): running maximum, e -> the score scratch, running
-    // sum; returns the factors the earlier partial outputs are rescaled by
-    auto softmax_step = [&](int tb, float (&s)[G], float (&alpha)[G]) {
-        h16 mk = (h16)0.f;
-        if (mrow) mk = mrow[tb * 64 + lane];
-#pragma unroll
-        for (int h = 0; h < G; h++) {
-            float x = scaled((h16)s[h], a.inv_sqrt_d);        // fp16 score (SpMM_Kernel.cuh:418), / sqrt(d) in fp16 (model :284)
-            if (mrow) x = masked(x, mk);
-            const float m_new = uniform_f(fmaxf(m_run[h], wave_max(x)));
-            alpha[h] = uniform_f(__expf(m_run[h] - m_new));   // 0 for the first block (m_run = -inf)
-            const h16 e = (h16)__expf(x - m_new);
-            if constexpr (MF && G == 4) {
-                // matrix-pipe engine: e goes straight into the wave's LDS coefficient table [head][token] -- no memory round trip
-                *reinterpret_cast<h16*>(ptab + h * kValTabStride + lane * 2) = e;
-            } else {
-                erow[(int64_t)h * a.ld + tb * 64 + lane] = e;
-            }
-            l_lane[h] = uniform_f(l_lane[h] * alpha[h] + wave_sum((float)e));   // (the running sum of the wave, uniform)
-            m_run[h] = m_new;
-        }
-        // VALU engine: the value phase reads the e segments back as coefficients through scalar loads -- after the stores
-        // have reached L2
-        if constexpr (!(MF && G == 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    if constexpr (!PAIR) {
-        for (int tb = tb0 + wave; tb < tb_end; tb += kWaves) {
-            float s[G], alpha[G];
-#pragma unroll
-            for (int h = 0; h < G; h++) s[h] = 0.f;
-            key_tokblk<G, MF, 0, 4>(smem, wave * kStageBytes, kb + (int64_t)tb * kTilesPerTb, ki + (int64_t)tb * kTilesPerTb, kn, qw, kD / 2,
-                                    lane, s, ctab_lane);
-            MUSTAFAR_PTRACE_STAMP(2);
-            softmax_step(tb, s, alpha);
-            MUSTAFAR_PTRACE_STAMP(3);
-#pragma unroll
-            for (int h = 0; h < G; h++) { acc0[h] *= alpha[h]; acc1[h] *= alpha[h]; }
-            value_tokblks<G, MF, 0, 4, 1, MF && G == 4>(smem, wave * kStageBytes, vb, vi, vn, pw, (uint32_t)a.ld / 2u, tb, tb + 1, lane, acc0, acc1, ptab);
-            MUSTAFAR_PTRACE_STAMP(5);
-        }
-    } else {
-        const int pair = wave >> 1, odd = wave & 1;
-        // exchange area of the pair: the ODD wave's stage window (dead between the phases): G x 64 partial scores, then G factors
-        float* xch = reinterpret_cast<float*>(smem + (2 * pair + 1) * kStageBytes);
-        for (int t = tb0; t < tb_end; t += kWaves / 2) {   // workgroup-uniform: the barriers below are reached by every wave
-            const int tb = t + pair;
-            const bool active = tb < tb_end;
-            float s[G], alpha[G];
-#pragma unroll
-            for (int h = 0; h < G; h++) { s[h] = 0.f; alpha[h] = 1.f; }
-            if (active) {
-                const uint64_t* kbt = kb + (int64_t)tb * kTilesPerTb;
-                const uint32_t* kit = ki + (int64_t)tb * kTilesPerTb;
-                if (odd) key_tokblk<G, MF, 2, 2>(smem, wave * kStageBytes, kbt, kit, kn, qw, kD / 2, lane, s, ctab_lane);
-                else     key_tokblk<G, MF, 0, 2>(smem, wave * kStageBytes, kbt, kit, kn, qw, kD / 2, lane, s, ctab_lane);
-                if (odd) {
-#pragma unroll
-                    for (int h = 0; h < G; h++) xch[h * 64 + lane] = s[h];
-                }
-            }
-            MUSTAFAR_PTRACE_STAMP(2);
-            __syncthreads();
-            if (active && !odd) {
-#pragma unroll
-                for (int h = 0; h < G; h++) s[h] += xch[h * 64 + lane];
-                softmax_step(tb, s, alpha);
-                if (lane < G) {
-                    float mine = alpha[0];
-#pragma unroll
-                    for (int h = 1; h < G; h++) mine = (lane == h) ? alpha[h] : mine;
-                    xch[G * 64 + lane] = mine;
-                }
-            }
-            __syncthreads();
-            MUSTAFAR_PTRACE_STAMP(3);
-            if (active) {
-                if (odd) {
-#pragma unroll
-                    for (int h = 0; h < G; h++) alpha[h] = xch[G * 64 + h];
-                }
-#pragma unroll
-                for (int h = 0; h < G; h++) { acc0[h] *= alpha[h]; acc1[h] *= alpha[h]; }
-                // (the odd wave's LDS reads above are issued before its value phase rewrites the window: one wave, in order)
-                if (odd) value_tokblks<G, MF, 2, 2, 1>(smem, wave * kStageBytes, vb, vi, vn, pw, (uint32_t)a.ld / 2u, tb, tb + 1, lane, acc0, acc1, ptab);
-                else     value_tokblks<G, MF, 0, 2, 1>(smem, wave * kStageBytes, vb, vi, vn, pw, (uint32_t)a.ld / 2u, tb, tb + 1, lane, acc0, acc1, ptab);
-            }
-            MUSTAFAR_PTRACE_STAMP(5);
-        }
-        if (odd) {   // maximum and sum live in the even wave; the odd wave contributes its output half only
-#pragma unroll
-            for (int h = 0; h < G; h++) l_lane[h] = 0.f;
-        }
-    }
-    // ---- merge the waves: common maximum, rescaled sums and outputs -> one slab per head.  (PAIR: an odd wave carries
-    // the second channel half of its pair's blocks and must be scaled by the PAIR's maximum: it borrows the even wave's.)
-    float* red = reinterpret_cast<float*>(smem);                 // [kWaves][2G][64]
-    float* s_m = red + kWaves * 2 * G * 64;                      // [kWaves][G]
-    float* s_l = s_m + kWaves * G;                               // [kWaves][G]
-    __syncthreads();   // every wave is done with its stage window
-    if (lane < G && !(PAIR && (wave & 1))) {
-        float mine = m_run[0];
-#pragma unroll
-        for (int h = 1; h < G; h++) mine = (lane == h) ? m_run[h] : mine;
-        s_m[wave * G + lane] = mine;
-        if (PAIR) s_m[(wave + 1) * G + lane] = mine;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < G; h++) {
-        const float mw = s_m[wave * G + h];                      // (= m_run[h], or the partner's for an odd wave of a pair)
-        float M = s_m[h];
-#pragma unroll
-        for (int w = 1; w < kWaves; w++) M = fmaxf(M, s_m[w * G + h]);
-        const float scale = (mw == -INFINITY) ? 0.f : __expf(mw - M);   // a wave without blocks weighs nothing
-        const float l = l_lane[h] * scale;
-        if (lane == 0) s_l[wave * G + h] = l;
-        red[(wave * 2 * G + h) * 64 + lane]     = acc0[h] * scale;
-        red[(wave * 2 * G + G + h) * 64 + lane] = acc1[h] * scale;
-    }
-    __syncthreads();
-    float* slab_o = a.ws_o + ((int64_t)blockIdx.x * a.BH + bh0) * kD;
-    for (int o = threadIdx.x; o < 2 * G * 64; o += kThreads) {
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) sum += red[w * 2 * G * 64 + o];
-        const int hh = o >> 6, l = o & 63;   // hh = half * G + h
-        slab_o[(hh % G) * kD + (hh / G) * 64 + l] = sum;
-    }
-    if (threadIdx.x < G) {
-        const int h = threadIdx.x;
-        float M = s_m[h], L = s_l[h];
-#pragma unroll
-        for (int w = 1; w < kWaves; w++) { M = fmaxf(M, s_m[w * G + h]); L += s_l[w * G + h]; }
-        float* slab_ml = a.ws_ml + ((int64_t)blockIdx.x * a.BH + bh0 + h) * 2;
-        slab_ml[0] = M;
-        slab_ml[1] = L;
-    }
-    MUSTAFAR_PTRACE_END(MF ? 6 : 4);
-}
-
 // out[bh, c] = fp16( sum_s w_s * o_s[c] / sum_s w_s * l_s ),  w_s = exp(m_s - max_s m_s)   (the softmax of :304 and the
 // sums of :315-317, merged over the slabs of the row).  One workgroup per row, 256 threads: thread = (channel, parity).
 constexpr int kMaxSlabs = 512;
@@ -2000,9 +1711,6 @@ __global__ __launch_bounds__(256) void onepass_finish_kernel(const float* __rest
     const float* src = ws_o + (int64_t)bh * kD + c;
     // The first 2 * MUSTAFAR_FINISH_EARLY slabs' outputs are requested BEFORE the weights are known: the loads fly while the maxima / sums are
     // loaded and reduced (the kernel is two dependent memory round trips otherwise; 36-68 slabs at c3).
-#ifndef MUSTAFAR_FINISH_EARLY
-#define MUSTAFAR_FINISH_EARLY 20   // (round 5: 32 -> 20; c3's rows have 36 slabs: tokens/s + 1-2 % at c3, c4 / c5 unchanged -- same-box A/B, profiles/r05_probes.txt)
-#endif
     constexpr int kEarly = MUSTAFAR_FINISH_EARLY;   // per thread: slabs par, par + 2, ..., par + 2 * kEarly - 2 (128 slabs: a slab per pair at c3)
     float v[kEarly];
 #pragma unroll
@@ -2078,13 +1786,10 @@ __global__ __launch_bounds__(256) void onepass_finish_kernel(const float* __rest
 // The row kernel for rows of at most 64 slabs (round 5; every BASELINE shape up to 8k x batch 8): ONE thread per channel walks all the slabs of
 // the row -- no parity halves, no LDS, no barrier -- with the first kEarly1 slabs' outputs requested before the weights are known and each
 // weight taken from the lane that computed it (v_readlane; a slab per lane).  Two waves per row, each working the weights out for itself.
-#ifndef MUSTAFAR_FINISH1_EARLY
-#define MUSTAFAR_FINISH1_EARLY 40
-#endif
 __global__ __launch_bounds__(128) void onepass_finish1_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, int S,
                                                               h16* __restrict__ out, int BH)
 {
-    constexpr int kEarly1 = MUSTAFAR_FINISH1_EARLY;
+    constexpr int kEarly1 = 40;   // slab loads in flight per thread before the weights are known: covers c3's 36-slab rows whole (profiles/r05_probes.txt; other depths were not measured)
     static_assert(kEarly1 <= 64 && kEarly1 % 4 == 0, "a slab per lane");
     const int bh = blockIdx.x, c = threadIdx.x, lane = threadIdx.x & 63;
     const int64_t total = (int64_t)BH * kD;
@@ -2115,11 +1820,10 @@ __global__ __launch_bounds__(128) void onepass_finish1_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ one-pass decode, lean form (G = 4)
-// Same algorithm and slabs as decode_onepass_kernel, rebuilt around what the round-2 counters showed: at c3 a workgroup of the
-// pair form runs its block loop ONCE, and 2.3 of its 11.3 vector instructions per tile were the start-up and merge code around
-// that single iteration (sixteen hoisted coefficient pointers and a dozen chunk pointers spilled to VGPR lanes, the pair
-// exchange, two barriers).  Here
-//   * a wave owns whole 64-token blocks (no exchange, no barrier before the final merge);
+// The algorithm and slabs described above, built around what the counters of round 2's kernel (key_tokblk / value_tokblks in one
+// launch; removed) showed: at c3 a workgroup of its pair form ran its block loop ONCE, and 2.3 of its 11.3 vector
+// instructions per tile were the start-up and merge code around that single iteration (sixteen hoisted coefficient pointers and a
+// dozen chunk pointers spilled to VGPR lanes, the pair exchange, two barriers).  Here
 //   * every address inside a block is ONE base pointer + an immediate: the chunk's bitmaps / offsets (tile offset TOFF), the
 //     coefficients of the four heads (rows HS bytes apart: the q rows are contiguous, and the e segments of a block are laid out
 //     [head][64 tokens] in the score scratch, which is this kernel's to arrange), so nothing per chunk or per head is
@@ -2136,37 +1840,9 @@ __global__ __launch_bounds__(128) void onepass_finish1_kernel(const float* __res
 template <int TOFF>
 __device__ __forceinline__ void metab_issue_at(MetaB& m, const uint64_t* __restrict__ bmp, const uint32_t* __restrict__ idx)
 {
-#ifdef MUSTAFAR_PROBE_HOTMETA
-    asm volatile("s_load_dwordx16 %0, %2, %4\n\ts_load_dwordx8 %1, %3, %5"
-                 : "=&s"(m.bm), "=&s"(m.ix)
-                 : "s"(g_hot_bmp), "s"(g_hot_idx), "i"((TOFF % 32) * 8), "i"((TOFF % 32) * 4));
-#else
     asm volatile("s_load_dwordx16 %0, %2, %4\n\ts_load_dwordx8 %1, %3, %5"
                  : "=&s"(m.bm), "=&s"(m.ix)
                  : "s"(bmp), "s"(idx), "i"(TOFF * 8), "i"(TOFF * 4));
-#endif
-}
-// The same with a TOUCH of the metadata two steps ahead (TT = its tile offset, < 0: none): one dword of the bitmap line and one of the
-// offset line that the request AFTER this one will want -- they ride in this request's wait (same issue time, same L2 latency) and pull
-// the 64-byte lines into the scalar cache, so that from a chunk's second step on the 96-byte requests are scalar-cache hits instead of one
-// L2 round trip per step (probe build with every wave on the same hot lines: c3 40.7 -> 36.8 us, c5 128.5 -> 117.5: the bound of this).
-// MEASURED SLOWER (round 5, same box, kernel us, without / with: c3 42.0 / 43.2, c4 67.6 / 69.8, c5 128.4 / 133.4, c2 15.4 / 15.4): the
-// touches are scalar-cache misses themselves, every wait is a full drain, and 64 waves share a 16 KB scalar cache.  Off
-// (MUSTAFAR_META_TOUCH = 0); kept as an experiment knob.
-template <int TOFF, int TT>
-__device__ __forceinline__ void metab_issue_touch_at(MetaB& m, const uint64_t* __restrict__ bmp, const uint32_t* __restrict__ idx)
-{
-    if constexpr (TT < 0 || !MUSTAFAR_META_TOUCH) {
-        metab_issue_at<TOFF>(m, bmp, idx);
-    } else {
-#if defined(MUSTAFAR_PROBE_HOTMETA) || !MUSTAFAR_META_TOUCH
-        metab_issue_at<TOFF>(m, bmp, idx);
-#else
-        asm volatile("s_load_dwordx16 %0, %4, %6\n\ts_load_dwordx8 %1, %5, %7\n\ts_load_dword %2, %4, %8\n\ts_load_dword %3, %5, %9"
-                     : "=&s"(m.bm), "=&s"(m.ix), "=&s"(m.t0), "=&s"(m.t1)
-                     : "s"(bmp), "s"(idx), "i"(TOFF * 8), "i"(TOFF * 4), "i"(TT * 8), "i"(TT * 4));
-#endif
-    }
 }
 // coefficients of one step for the four heads: 16 bytes each at base + OFF + h * HS
 template <int OFF, int HS>
@@ -2191,29 +1867,10 @@ __device__ __forceinline__ void coef_issue_at(u32x4 (&c)[G], const void* __restr
 }
 
 // Coefficient rows that are NOT a fixed distance apart (the value entry point's probabilities: rows N * ldb halfs apart, a runtime
-// quantity): one base pointer per head, the offset inside the block still an immediate.
-template <int G>
-struct CoefPtrs {
-    const void* p[G];
-};
-template <int G, int OFF, int HS>
-__device__ __forceinline__ void coef_issue_at(u32x4 (&c)[G], const CoefPtrs<G>& cb)
-{
-    if constexpr (G == 4) {
-        asm volatile("s_load_dwordx4 %0, %4, %8\n\ts_load_dwordx4 %1, %5, %8\n\t"
-                     "s_load_dwordx4 %2, %6, %8\n\ts_load_dwordx4 %3, %7, %8"
-                     : "=&s"(c[0]), "=&s"(c[1]), "=&s"(c[2]), "=&s"(c[3])
-                     : "s"(cb.p[0]), "s"(cb.p[1]), "s"(cb.p[2]), "s"(cb.p[3]), "i"(OFF));
-    } else if constexpr (G == 2) {
-        asm volatile("s_load_dwordx4 %0, %2, %4\n\ts_load_dwordx4 %1, %3, %4" : "=&s"(c[0]), "=&s"(c[1]) : "s"(cb.p[0]), "s"(cb.p[1]), "i"(OFF));
-    } else {
-        asm volatile("s_load_dwordx4 %0, %1, %2" : "=&s"(c[0]) : "s"(cb.p[0]), "i"(OFF));
-    }
-}
-
-// The same rows through ONE base pointer and a scalar byte offset per further head (round 5): gfx950's scalar loads take a scalar
-// offset AND an immediate (s_load_dwordx4 sdst, sbase, soffset offset:imm), so rows a runtime distance apart cost three scalar
-// registers next to the base instead of three more pointers, and nothing but the base moves from block to block.
+// quantity): ONE base pointer and a scalar byte offset per further head, the offset inside the block still an immediate (round 5;
+// rounds 4 / 5a: a pointer per head).  gfx950's scalar loads take a scalar offset AND an immediate (s_load_dwordx4 sdst, sbase,
+// soffset offset:imm), so such rows cost three scalar registers next to the base instead of three more pointers, and nothing but
+// the base moves from block to block.
 template <int G>
 struct CoefStride {
     const void* base;
@@ -2238,27 +1895,16 @@ struct Gathered2 {
     uint32_t t[8];   // gathered halfs, EXACT zero where the tile has no element in the lane: even tiles bits 15:0, odd tiles bits 31:16
 };
 // Zeroing the gather registers (the masked gathers leave the lanes without an element untouched) is one full-rate v_mov_b32 per tile
-// -- 1 of the 6.5 vector instructions per tile of the dot2 loop, 1 of the 4.75 of the matrix-pipe loop.  MUSTAFAR_ZFILL = 1 lets the
-// LDS pipe do it instead: an UNMASKED ds_read_u16 from an address beyond the workgroup's LDS allocation (the tile's own address
-// register + 65534: out-of-range LDS reads return zero; LDS operations of a wave return in order, so the masked gather behind it lands
-// on top of the zeros).  Correct (the GPU suite passes with it) and 1 vector instruction per tile cheaper, but SLOWER: the gathers
-// already keep the CU's one LDS pipe busy a third of the launch, and a second LDS instruction per tile costs more than the v_mov it
-// saves (round 4, c3, kernel us: dot2 42.8 -> 43.4, matrix pipe 32.9 -> 36.0; c4 57.4 -> 63.5, c5 113.7 -> 121.6:
-// profiles/r04_probes.txt).  Off.
-#ifndef MUSTAFAR_ZFILL
-#define MUSTAFAR_ZFILL 0
-#endif
-#if MUSTAFAR_ZFILL
-#define MUSTAFAR_D2_ZERO(j, k) "ds_read_u16 %[t" #j "], %[x" #k "] offset:65534\n\t"
-#else
-#define MUSTAFAR_D2_ZERO(j, k) "v_mov_b32 %[t" #j "], 0\n\t"
-#endif
+// -- 1 of the 6.5 vector instructions per tile of the dot2 loop, 1 of the 4.75 of the matrix-pipe loop.  (Letting the LDS pipe zero
+// them -- an unmasked ds_read_u16 from beyond the workgroup's LDS allocation in front of the masked gather -- is correct and one vector
+// instruction per tile cheaper, but SLOWER: the gathers already keep the CU's one LDS pipe busy a third of the launch.  Round 4, c3,
+// kernel us: dot2 42.8 -> 43.4, matrix pipe 32.9 -> 36.0; c4 57.4 -> 63.5, c5 113.7 -> 121.6: profiles/r04_probes.txt.)
 #define MUSTAFAR_D2_RANK(j, k)                                              \
     "s_lshl2_add_u32 %[u" #k "], %[o" #j "], %[adj]\n\t"                     \
     "v_mbcnt_lo_u32_b32 %[x" #k "], %[l" #j "], 0\n\t"                        \
     "v_mbcnt_hi_u32_b32 %[x" #k "], %[h" #j "], %[x" #k "]\n\t"               \
     "v_lshl_add_u32 %[x" #k "], %[x" #k "], 1, %[u" #k "]\n\t"                \
-    MUSTAFAR_D2_ZERO(j, k)
+    "v_mov_b32 %[t" #j "], 0\n\t"
 #define MUSTAFAR_D2_LOAD(j, k) "s_mov_b64 exec, %[m" #j "]\n\tds_read_u16 %[t" #j "], %[x" #k "]\n\t"
 #define MUSTAFAR_D2_LOAD_HI(j, k) "s_mov_b64 exec, %[m" #j "]\n\tds_read_u16_d16_hi %[t" #j "], %[x" #k "]\n\t"
 // (EXEC contract as fma8 / gather8_clean: full wave at entry, restored before the statement ends)
@@ -2303,10 +1949,7 @@ __device__ __forceinline__ void gather2_wait(Gathered2& g, u32x4 (&c)[4])   // d
 // Round 6 found this the hard way: with the online-softmax text removed the register allocator placed `v_mov_b32 v29, v9` one wait
 // state behind the key phase's last `v_dot2_f32_f16 v9, ...` and half of the block pairs got a stale partial score for head 3 (the
 // LAST accumulator written) -- bisected on the ISA with tools/isa_patch.sh (profiles/r06_probes.txt item 1); 16 wait states in front of
-// that move fixed it, this is the principled form.  tools/check_smem_hazards.py check (6) holds every asm statement to it.
-#ifndef MUSTAFAR_DOT_GUARD
-#define MUSTAFAR_DOT_GUARD "s_nop 3\n\t"
-#endif
+// that move fixed it, this is the principled form (MUSTAFAR_DOT_GUARD, "s_nop 3").  tools/check_smem_hazards.py check (6) holds every asm statement to it.
 // acc[h] += tile(2w) * coef(2w) + tile(2w + 1) * coef(2w + 1): the coefficient dword w of head h holds exactly that pair
 __device__ __forceinline__ void fma8_d2(const u32x4 (&c)[4], Gathered2& g, float (&acc)[4])
 {
@@ -2317,71 +1960,6 @@ __device__ __forceinline__ void fma8_d2(const u32x4 (&c)[4], Gathered2& g, float
                    [t4] "+v"(g.t[4]), [t6] "+v"(g.t[6])
                  : [t1] "v"(g.t[1]), [t3] "v"(g.t[3]), [t5] "v"(g.t[5]), [t7] "v"(g.t[7]), MUSTAFAR_COPS(0), MUSTAFAR_COPS(1),
                    MUSTAFAR_COPS(2), MUSTAFAR_COPS(3));
-}
-
-// Round 5, dot2 engine: the pair register built WITHOUT zeroing and WITHOUT switching EXEC per tile.  The gathers run unmasked (a lane
-// without an element reads a neighbouring half of the same stream: a valid LDS address, a value nobody uses), then per pair
-//   v_cndmask_b32      t_even, 0, t_even, mask_even                                   -> bits 15:0 = the even tile's element or 0, bits 31:16 = 0
-//   v_cndmask_b32_sdwa t_even, zero, t_odd, vcc (= mask_odd)  dst_sel:WORD_1 PRESERVE  -> bits 31:16 = the odd tile's element or 0
-// : two vector instructions per pair instead of three (two v_mov_b32 + v_or_b32), 6.0 per tile in the loop instead of 6.5, and one scalar
-// move per pair (vcc) instead of two (exec).  `zero`: a register holding 0 (SDWA takes no inline constant on gfx9).  A partial (dst_sel)
-// write needs one wait state before a vector instruction reads the register (gfx940+ forwarding hazard): the next pair's two selects
-// stand between a pair's SDWA write and its v_dot2 -- and an s_nop behind the last pair's.
-// MEASURED SLOWER (same box, kernel us, v_mov + v_or form / this form): c3 39.3-40.2 / 39.9-41.1, c4 66.5 / 68.6, c5 126.7 / 130.3 -- the v_mov_b32 and
-// v_or_b32 it saves are the two FULL-rate instructions of the loop (tools/ubench/issue_rates.hip: twice the rate of anything with a
-// scalar operand or a VOP3 / SDWA encoding), the two selects are not, and the masks now live to the FMA phase (68 scalar spills
-// instead of 44).  Off (MUSTAFAR_D2_SDWA = 0); kept as an experiment knob.
-#ifndef MUSTAFAR_D2_SDWA
-#define MUSTAFAR_D2_SDWA 0
-#endif
-#define MUSTAFAR_D2U_RANK(j, k)                                              \
-    "s_lshl2_add_u32 %[u" #k "], %[o" #j "], %[adj]\n\t"                     \
-    "v_mbcnt_lo_u32_b32 %[x" #k "], %[l" #j "], 0\n\t"                        \
-    "v_mbcnt_hi_u32_b32 %[x" #k "], %[h" #j "], %[x" #k "]\n\t"               \
-    "v_lshl_add_u32 %[x" #k "], %[x" #k "], 1, %[u" #k "]\n\t"
-#define MUSTAFAR_D2U_LOAD(j, k) "ds_read_u16 %[t" #j "], %[x" #k "]\n\t"
-struct Gathered2u {
-    uint32_t t[8];   // gathered halfs in bits 15:0 (garbage where the tile has no element in the lane: selected away by fma8_d2s)
-    uint64_t m[8];   // bit i <=> element i of the tile non-zero
-};
-__device__ __forceinline__ void gather8_d2u(const MetaB& m, uint32_t adj, Gathered2u& g)
-{
-#pragma unroll
-    for (int j = 0; j < 8; j++) g.m[j] = __builtin_bitreverse64(m.bm[2 * j] | ((uint64_t)m.bm[2 * j + 1] << 32));
-    const uint64_t m0 = g.m[0], m1 = g.m[1], m2 = g.m[2], m3 = g.m[3], m4 = g.m[4], m5 = g.m[5], m6 = g.m[6], m7 = g.m[7];
-    uint32_t x0, x1, x2, x3, u0, u1, u2, u3;
-    asm volatile(MUSTAFAR_D2U_RANK(0, 0) MUSTAFAR_D2U_RANK(1, 1) MUSTAFAR_D2U_RANK(2, 2) MUSTAFAR_D2U_RANK(3, 3)
-                 MUSTAFAR_D2U_LOAD(0, 0) MUSTAFAR_D2U_LOAD(1, 1) MUSTAFAR_D2U_LOAD(2, 2) MUSTAFAR_D2U_LOAD(3, 3)
-                 MUSTAFAR_D2U_RANK(4, 0) MUSTAFAR_D2U_RANK(5, 1) MUSTAFAR_D2U_RANK(6, 2) MUSTAFAR_D2U_RANK(7, 3)
-                 MUSTAFAR_D2U_LOAD(4, 0) MUSTAFAR_D2U_LOAD(5, 1) MUSTAFAR_D2U_LOAD(6, 2) MUSTAFAR_D2U_LOAD(7, 3)
-                 : [t0] "=&v"(g.t[0]), [t1] "=&v"(g.t[1]), [t2] "=&v"(g.t[2]), [t3] "=&v"(g.t[3]), [t4] "=&v"(g.t[4]),
-                   [t5] "=&v"(g.t[5]), [t6] "=&v"(g.t[6]), [t7] "=&v"(g.t[7]), [x0] "=&v"(x0), [x1] "=&v"(x1), [x2] "=&v"(x2),
-                   [x3] "=&v"(x3), [u0] "=&s"(u0), [u1] "=&s"(u1), [u2] "=&s"(u2), [u3] "=&s"(u3)
-                 : MUSTAFAR_MOPS(0), MUSTAFAR_MOPS(1), MUSTAFAR_MOPS(2), MUSTAFAR_MOPS(3), MUSTAFAR_MOPS(4), MUSTAFAR_MOPS(5),
-                   MUSTAFAR_MOPS(6), MUSTAFAR_MOPS(7), [o0] "s"(m.ix[0]), [o1] "s"(m.ix[1]), [o2] "s"(m.ix[2]), [o3] "s"(m.ix[3]),
-                   [o4] "s"(m.ix[4]), [o5] "s"(m.ix[5]), [o6] "s"(m.ix[6]), [o7] "s"(m.ix[7]), [adj] "s"(adj)
-                 : "scc");
-}
-__device__ __forceinline__ void gather2u_wait(Gathered2u& g, u32x4 (&c)[4])   // drains the gathers and the coefficient loads
-{
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(g.t[0]), "+v"(g.t[1]), "+v"(g.t[2]), "+v"(g.t[3]), "+v"(g.t[4]), "+v"(g.t[5]), "+v"(g.t[6]), "+v"(g.t[7]),
-                   "+s"(c[0]), "+s"(c[1]), "+s"(c[2]), "+s"(c[3]));
-}
-#define MUSTAFAR_D2S_PAIR(e, o)                                                                                         \
-    "v_cndmask_b32_e64 %[t" #e "], 0, %[t" #e "], %[m" #e "]\n\t"                                                        \
-    "s_mov_b64 vcc, %[m" #o "]\n\t"                                                                                     \
-    "v_cndmask_b32_sdwa %[t" #e "], %[z], %[t" #o "], vcc dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:WORD_0\n\t"
-__device__ __forceinline__ void fma8_d2s(const u32x4 (&c)[4], Gathered2u& g, uint32_t zero, float (&acc)[4])
-{
-    asm volatile(MUSTAFAR_D2S_PAIR(0, 1) MUSTAFAR_D2S_PAIR(2, 3) MUSTAFAR_DOT4(0, 0) MUSTAFAR_D2S_PAIR(4, 5) MUSTAFAR_DOT4(2, 1)
-                 MUSTAFAR_D2S_PAIR(6, 7) MUSTAFAR_DOT4(4, 2) "s_nop 0\n\t" MUSTAFAR_DOT4(6, 3) MUSTAFAR_DOT_GUARD
-                 : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [a2] "+v"(acc[2]), [a3] "+v"(acc[3]), [t0] "+v"(g.t[0]), [t2] "+v"(g.t[2]),
-                   [t4] "+v"(g.t[4]), [t6] "+v"(g.t[6])
-                 : [t1] "v"(g.t[1]), [t3] "v"(g.t[3]), [t5] "v"(g.t[5]), [t7] "v"(g.t[7]), [z] "v"(zero),
-                   [m0] "s"(g.m[0]), [m1] "s"(g.m[1]), [m2] "s"(g.m[2]), [m3] "s"(g.m[3]), [m4] "s"(g.m[4]), [m5] "s"(g.m[5]),
-                   [m6] "s"(g.m[6]), [m7] "s"(g.m[7]), MUSTAFAR_COPS(0), MUSTAFAR_COPS(1), MUSTAFAR_COPS(2), MUSTAFAR_COPS(3)
-                 : "vcc");
 }
 
 // The matrix-pipe engine on the lean addressing: the dot2 form's gather (tile pairs packed in one register, exact zeros where a lane
@@ -2440,14 +2018,11 @@ __device__ __forceinline__ void chunk32_mfma_at(uint32_t adj, const uint64_t* __
 // prefetch_meta without a divergent region (every lane loads; the lanes beyond the last sector repeat it): the lean kernels call it
 // inside their block loops, right in front of asm statements that own EXEC.  Tiles [T0, T0 + NT) of the block (a wave of the pair
 // form asks for its own half only), one 4-byte load per 64-byte line: NT / 8 lines of bitmaps, NT / 16 + 2 of offsets (the row may
-// start anywhere).  (One load per 32-byte sector measured the same: L2 fills whole lines.  MUSTAFAR_PF_SECTOR: experiment knob.)
-#ifndef MUSTAFAR_PF_SECTOR
-#define MUSTAFAR_PF_SECTOR 64
-#endif
+// start anywhere).  (One load per 32-byte sector measured the same: L2 fills whole lines.)
 template <int T0, int NT>
 __device__ __forceinline__ uint32_t prefetch_meta_all(const uint64_t* __restrict__ bmp_t, const uint32_t* __restrict__ idx_t, int lane)
 {
-    constexpr int kSec = MUSTAFAR_PF_SECTOR;
+    constexpr int kSec = 64;
     constexpr int kB = NT * 8 / kSec, kI = (NT * 4 + kSec - 1) / kSec + 1;
     static_assert(kB + kI <= 64, "one load per sector and lane");
     const int k = lane < kB + kI - 1 ? lane : kB + kI - 1;
@@ -2459,48 +2034,34 @@ __device__ __forceinline__ uint32_t prefetch_meta_all(const uint64_t* __restrict
 // One staged chunk (32 tiles) of the lean kernel; the step schedule is chunk32's.
 //   bmp_t / idx_t : the BLOCK's bitmaps / offsets (the chunk starts TOFF tiles in);  cbase + COFF + h * HS : the chunk's first
 //   coefficient of head h
-template <int ENG, int TOFF, int COFF, int HS, int G = 4, class CB = const void*, int NTOFF = -2>   // CB: const void* (rows HS bytes apart) or CoefPtrs<G>;
-                                           // NTOFF: tile offset of the chunk the wave works on NEXT (-1: none; -2: no touches at all, the round-4 callers)
+template <int ENG, int TOFF, int COFF, int HS, int G = 4, class CB = const void*>   // CB: const void* (rows HS bytes apart) or CoefStride<G>
 __device__ __forceinline__ void chunk32_at(uint32_t adj, const uint64_t* __restrict__ bmp_t, const uint32_t* __restrict__ idx_t,
                                            const CB& cbase, float (&acc)[G])
 {
-    // tile offset of the metadata the request of step S + 1 touches -- that of step S + 2, the next chunk's first step behind this chunk's last
-    // (metab_issue_touch_at) -- or -1
-#define MUSTAFAR_TT(S) (NTOFF == -2 ? -1 : ((S) + 2 < 4 ? TOFF + 8 * ((S) + 2) : (NTOFF >= 0 ? NTOFF + 8 * ((S) + 2 - 4) : -1)))
     static_assert(G == 4 || ENG == 0, "dot2 pairs four heads' coefficients; G < 4 runs v_fma_mix");
     // (with the coefficients in scalar registers as well, an early request leaves the loop 140+ registers short of the 78 a wave of
     // this launch has, and the compiler then spills registers that loads are still writing: tools/check_smem_hazards.py)
     constexpr bool kEarly = MUSTAFAR_META_EARLY > 1;
     MetaB cur, nxt;
     u32x4 c[G];
-    uint32_t zero = 0;   // (ENG == 2: the SDWA select's zero operand, held in a vector register)
-    if constexpr (ENG == 2 && MUSTAFAR_D2_SDWA) asm volatile("" : "+v"(zero));
-    metab_issue_touch_at<TOFF, (NTOFF == -2 ? -1 : TOFF + 8)>(cur, bmp_t, idx_t);
+    metab_issue_at<TOFF>(cur, bmp_t, idx_t);
     coef_issue_at<G, COFF, HS>(c, cbase);
     metab_wait(cur);
 #define MUSTAFAR_STEP(S)                                        \
-    if constexpr (kEarly) metab_issue_touch_at<TOFF + 8 * (S + 1), MUSTAFAR_TT(S)>(nxt, bmp_t, idx_t); \
+    if constexpr (kEarly) metab_issue_at<TOFF + 8 * (S + 1)>(nxt, bmp_t, idx_t); \
     if constexpr (ENG == 2) {                                   \
         if constexpr (G == 4) {                                 \
-            if constexpr (MUSTAFAR_D2_SDWA) {                   \
-                Gathered2u g;                                   \
-                gather8_d2u(cur, adj, g);                       \
-                gather2u_wait(g, c);                            \
-                if constexpr (!kEarly) metab_issue_touch_at<TOFF + 8 * (S + 1), MUSTAFAR_TT(S)>(nxt, bmp_t, idx_t);  \
-                fma8_d2s(c, g, zero, acc);                      \
-            } else {                                            \
-                Gathered2 g;                                    \
-                gather8_d2(cur, adj, g);                        \
-                gather2_wait(g, c);                             \
-                if constexpr (!kEarly) metab_issue_touch_at<TOFF + 8 * (S + 1), MUSTAFAR_TT(S)>(nxt, bmp_t, idx_t);  \
-                fma8_d2(c, g, acc);                             \
-            }                                                   \
+            Gathered2 g;                                        \
+            gather8_d2(cur, adj, g);                            \
+            gather2_wait(g, c);                                 \
+            if constexpr (!kEarly) metab_issue_at<TOFF + 8 * (S + 1)>(nxt, bmp_t, idx_t);  \
+            fma8_d2(c, g, acc);                                 \
         }                                                       \
     } else {                                                    \
         Gathered g;                                             \
         gather8(cur, adj, g);                                   \
         gather_wait<G>(g, c);                                   \
-        if constexpr (!kEarly) metab_issue_touch_at<TOFF + 8 * (S + 1), MUSTAFAR_TT(S)>(nxt, bmp_t, idx_t);  \
+        if constexpr (!kEarly) metab_issue_at<TOFF + 8 * (S + 1)>(nxt, bmp_t, idx_t);  \
         fma8<G>(c, g, acc);                                     \
     }                                                           \
     if constexpr (kEarly) metab_ready(nxt); else metab_wait(nxt); \
@@ -2510,17 +2071,10 @@ __device__ __forceinline__ void chunk32_at(uint32_t adj, const uint64_t* __restr
 #undef MUSTAFAR_STEP
     if constexpr (ENG == 2) {
         if constexpr (G == 4) {
-            if constexpr (MUSTAFAR_D2_SDWA) {
-                Gathered2u g;
-                gather8_d2u(cur, adj, g);
-                gather2u_wait(g, c);
-                fma8_d2s(c, g, zero, acc);
-            } else {
-                Gathered2 g;
-                gather8_d2(cur, adj, g);
-                gather2_wait(g, c);
-                fma8_d2(c, g, acc);
-            }
+            Gathered2 g;
+            gather8_d2(cur, adj, g);
+            gather2_wait(g, c);
+            fma8_d2(c, g, acc);
         }
     } else {
         Gathered g;
@@ -2528,7 +2082,6 @@ __device__ __forceinline__ void chunk32_at(uint32_t adj, const uint64_t* __restr
         gather_wait<G>(g, c);
         fma8<G>(c, g, acc);
     }
-#undef MUSTAFAR_TT
 }
 
 // The 128 tiles of one 64-token block against the coefficients at cbase (four rows HS bytes apart).
@@ -2577,11 +2130,7 @@ __device__ __forceinline__ void lean_block_phase(unsigned char* lds, uint32_t ld
         }
         if (c == CB + CN - 1) mid();
         __builtin_amdgcn_wave_barrier();
-#ifdef MUSTAFAR_PROBE_HOTMETA
-        const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr);   // the fixed offsets of g_hot_idx stay inside the window
-#else
         const uint32_t adj = __builtin_amdgcn_readfirstlane(lds_addr - 4u * i0);
-#endif
         if constexpr (ENG == 1) {
             if (c == 0)      chunk32_mfma_at<0, 0>(adj, bmp_t, idx_t, ctab_lane, mA);
             else if (c == 1) chunk32_mfma_at<32, 64>(adj, bmp_t, idx_t, ctab_lane, mA);
@@ -2659,10 +2208,10 @@ __device__ __forceinline__ void lean_pair_phase(unsigned char* lds, uint32_t lds
             else if (k == 2) chunk32_mfma_at<128, 0>(adj, bmp_t, idx_t, ctab_lane + (VAL ? 4 * kValTabStride : 0), VAL ? mA : mB);
             else             chunk32_mfma_at<160, 64>(adj, bmp_t, idx_t, ctab_lane + (VAL ? 4 * kValTabStride : 0), VAL ? mA : mB);
         } else {
-            if (k == 0)      chunk32_at<ENG, 0, 0, HS, G, CBT, 32>(adj, bmp_t, idx_t, cbase, accA);
-            else if (k == 1) chunk32_at<ENG, 32, 64, HS, G, CBT, 128>(adj, bmp_t, idx_t, cbase, accA);
-            else if (k == 2) chunk32_at<ENG, 128, kE, HS, G, CBT, 160>(adj, bmp_t, idx_t, cbase, accB);
-            else             chunk32_at<ENG, 160, kE + 64, HS, G, CBT, -1>(adj, bmp_t, idx_t, cbase, accB);
+            if (k == 0)      chunk32_at<ENG, 0, 0, HS, G, CBT>(adj, bmp_t, idx_t, cbase, accA);
+            else if (k == 1) chunk32_at<ENG, 32, 64, HS, G, CBT>(adj, bmp_t, idx_t, cbase, accA);
+            else if (k == 2) chunk32_at<ENG, 128, kE, HS, G, CBT>(adj, bmp_t, idx_t, cbase, accB);
+            else             chunk32_at<ENG, 160, kE + 64, HS, G, CBT>(adj, bmp_t, idx_t, cbase, accB);
         }
         __builtin_amdgcn_wave_barrier();
         if (k < 3) {
@@ -2679,175 +2228,36 @@ __device__ __forceinline__ void lean_pair_phase(unsigned char* lds, uint32_t lds
     }
 }
 
-// grid: x = ceil(T / 64 / (4 * tb_per_wg)) (a.tb_per_wg = consecutive 64-token blocks per WAVE here), y = kv-heads * groups / 4
-// (+ win_rows leading rows of window workgroups, as decode_onepass_kernel).  e scratch: a.e_rows is used as
-// [y][T / 64][4 heads][64 tokens] halfs (4 T halfs per y: fits the [BH, ld >= T] score buffer), every block's four segments
-// 512 contiguous bytes on scalar-cache lines of their own.
-// INVARIANT of the e round trip (vector stores, then scalar loads of the same bytes by the SAME wave): the wave waits vmcnt(0)
-// -- the stores are acknowledged by L2 -- before it issues the scalar loads; no wave scalar-reads those lines earlier in the
-// launch (a block's segments belong to one wave and are 64-byte aligned, ld_scores % 32 == 0 is checked by the host), so the
-// only stale copy the scalar cache could hold is one from an EARLIER launch reusing the scratch, and every dispatch (graph
-// nodes included) starts with an acquire that invalidates the scalar cache.  tests/test_gpu_benchshape.py replays a captured
-// step with alternating queries to hold this.
-template <int ENG>
-__global__ __launch_bounds__(kThreads) void decode_onepass_lean_kernel(
-    const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
-    const uint32_t* __restrict__ k_nz_off, const uint64_t* __restrict__ v_bmp, const unsigned char* __restrict__ v_nz,
-    const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_nz_off, OneArgs a, int64_t k_bmp_stride,
-    int64_t k_idx_stride, uint32_t k_nz_stride, int64_t v_bmp_stride, int64_t v_idx_stride, uint32_t v_nz_stride)
-{
-    constexpr int G = 4;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[kWaves * kStageBytes];
-    static_assert(kWaves * kStageBytes >= (kWaves * 2 * 4 * 64 + 2 * kWaves * 4) * 4, "combine buffers must fit in the stage area");
-    MUSTAFAR_PTRACE_BEGIN();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wrows = a.win_rows < 0 ? -a.win_rows : a.win_rows;   // window rows lead (win_rows > 0) or trail (< 0) the grid
-    const int wy = a.win_rows < 0 ? (int)blockIdx.y - ((int)gridDim.y - wrows) : (int)blockIdx.y;
-    if (wy >= 0 && wy < wrows) {   // dense window
-        const int task = wy * gridDim.x + blockIdx.x;
-        if (task < (int)(gridDim.y - wrows) * a.nchunks) onepass_window_wg<G>(smem, win_args(a), task, gridDim.x);
-        MUSTAFAR_PTRACE_END(5);
-        return;
-    }
-    const int by = blockIdx.y - (a.win_rows > 0 ? a.win_rows : 0);
-    const int hb_per_kv = a.groups >> 2;
-    const int kvh = hb_per_kv == 1 ? by : by / hb_per_kv;
-    const int bh0 = kvh * a.groups + (by - kvh * hb_per_kv) * G;
-    const int ntb = a.T >> 6;
-    int tb = (blockIdx.x * kWaves + wave) * a.tb_per_wg;
-    const int tb_end = min(ntb, tb + a.tb_per_wg);
-    const int64_t tiles = (int64_t)ntb * kTilesPerTb;
-    const uint64_t* kb = k_bmp + (int64_t)kvh * (k_bmp_stride ? k_bmp_stride : tiles);
-    const uint32_t* ki = k_idx + (int64_t)kvh * (k_idx_stride ? k_idx_stride : tiles + 1);
-    const unsigned char* kn = k_nz + 16ull * (k_nz_stride ? (uint64_t)kvh * k_nz_stride : (uint64_t)k_nz_off[kvh]);
-    const uint64_t* vb = v_bmp + (int64_t)kvh * (v_bmp_stride ? v_bmp_stride : tiles);
-    const uint32_t* vi = v_idx + (int64_t)kvh * (v_idx_stride ? v_idx_stride : tiles + 1);
-    const unsigned char* vn = v_nz + 16ull * (v_nz_stride ? (uint64_t)kvh * v_nz_stride : (uint64_t)v_nz_off[kvh]);
-    const h16* qb = a.q + (int64_t)bh0 * kD;                     // the four q rows, 256 bytes apart
-    h16* eb = a.e_rows + (int64_t)by * ntb * (G * 64);            // this head batch's e segments, [block][4][64]
-    const h16* mrow = a.mask.ptr ? a.mask.ptr + (int64_t)(bh0 / a.mask.heads) * a.mask.stride : nullptr;
-    unsigned char* lds = smem + wave * kStageBytes;
-    const uint32_t lds_addr = (uint32_t)reinterpret_cast<uintptr_t>(lds);
-    // e = exp(x - max) * kEScale as fp16 (ENG 2: out of the subnormal range, see above); kEScaleLog2 is added to the exponent
-    constexpr float kEScaleLog2 = ENG == 2 ? 15.f : 0.f;
-
-    float m_run[G], l_run[G], acc0[G], acc1[G];   // (m_run, l_run: wave-uniform)
-#pragma unroll
-    for (int h = 0; h < G; h++) { m_run[h] = -INFINITY; l_run[h] = 0.f; acc0[h] = 0.f; acc1[h] = 0.f; }
-#pragma unroll 1
-    for (; tb < tb_end; tb++) {
-        const uint64_t* kbt = kb + (int64_t)tb * kTilesPerTb;
-        const uint32_t* kit = ki + (int64_t)tb * kTilesPerTb;
-        const uint64_t* vbt = vb + (int64_t)tb * kTilesPerTb;
-        const uint32_t* vit = vi + (int64_t)tb * kTilesPerTb;
-        // everything the block needs from memory before its streams is requested up front: metadata lines into L2, the chunk
-        // bounds of both sides, the mask column of the lane's token
-        const uint32_t pfk = prefetch_meta_all<0, 128>(kbt, kit, lane);
-        const uint32_t bnd_k = bnd_load(kit, lane);
-        const uint32_t pfv = prefetch_meta_all<0, 128>(vbt, vit, lane);
-        const uint32_t bnd_v = bnd_load(vit, lane);
-        const h16 mk = mrow ? mrow[tb * 64 + lane] : (h16)0.f;   // (mrow is wave-uniform: a scalar branch)
-        float s[G];
-#pragma unroll
-        for (int h = 0; h < G; h++) s[h] = 0.f;
-        lean_block_phase<ENG, kD * 2, false, 0, 4>(lds, lds_addr, kbt, kit, kn, qb, bnd_k, lane, s, s MUSTAFAR_PTRACE_ARG);
-        prefetch_done(pfk);
-        MUSTAFAR_PTRACE_STAMP(2);
-        // ---- softmax step (as decode_onepass_kernel): running maximum, e -> the block's segments, running sum, rescale
-        h16* eblk = eb + (int64_t)tb * (G * 64);
-#pragma unroll
-        for (int h = 0; h < G; h++) {
-            float x = scaled((h16)s[h], a.inv_sqrt_d);        // fp16 score (SpMM_Kernel.cuh:418), / sqrt(d) in fp16 (model :284)
-            if (mrow) x = masked(x, mk);
-            const float m_new = uniform_f(fmaxf(m_run[h], wave_max(x)));
-            const float alpha = uniform_f(__expf(m_run[h] - m_new));   // 0 for the first block (m_run = -inf)
-            const h16 e = (h16)__builtin_amdgcn_exp2f((x - m_new) * 1.44269504f + kEScaleLog2);
-            eblk[h * 64 + lane] = e;
-            l_run[h] = uniform_f(l_run[h] * alpha + wave_sum((float)e));
-            m_run[h] = m_new;
-            acc0[h] *= alpha;
-            acc1[h] *= alpha;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the e stores have reached L2 (see the invariant above)
-        MUSTAFAR_PTRACE_STAMP(3);
-        lean_block_phase<ENG, 64 * 2, true, 0, 4>(lds, lds_addr, vbt, vit, vn, eblk, bnd_v, lane, acc0, acc1 MUSTAFAR_PTRACE_ARG);
-        prefetch_done(pfv);
-        MUSTAFAR_PTRACE_STAMP(5);
-    }
-    // ---- merge the four waves: common maximum, rescaled sums and outputs -> one slab per head (as decode_onepass_kernel)
-    float* red = reinterpret_cast<float*>(smem);                 // [kWaves][2G][64]
-    float* s_m = red + kWaves * 2 * G * 64;                      // [kWaves][G]
-    float* s_l = s_m + kWaves * G;                               // [kWaves][G]
-    __syncthreads();   // every wave is done with its stage window
-    if (lane < G) {
-        float mine = m_run[0];
-#pragma unroll
-        for (int h = 1; h < G; h++) mine = (lane == h) ? m_run[h] : mine;
-        s_m[wave * G + lane] = mine;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < G; h++) {
-        float M = s_m[h];
-#pragma unroll
-        for (int w = 1; w < kWaves; w++) M = fmaxf(M, s_m[w * G + h]);
-        // a wave without blocks weighs nothing; the e scale leaves here (a power of two: exact)
-        const float scale = (m_run[h] == -INFINITY) ? 0.f : __expf(m_run[h] - M) * (ENG == 2 ? 0x1p-15f : 1.f);
-        if (lane == 0) s_l[wave * G + h] = l_run[h] * scale;
-        red[(wave * 2 * G + h) * 64 + lane]     = acc0[h] * scale;
-        red[(wave * 2 * G + G + h) * 64 + lane] = acc1[h] * scale;
-    }
-    __syncthreads();
-    float* slab_o = a.ws_o + ((int64_t)blockIdx.x * a.BH + bh0) * kD;
-    for (int o = threadIdx.x; o < 2 * G * 64; o += kThreads) {
-        float sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) sum += red[w * 2 * G * 64 + o];
-        const int hh = o >> 6, l = o & 63;   // hh = half * G + h
-        slab_o[(hh % G) * kD + (hh / G) * 64 + l] = sum;
-    }
-    if (threadIdx.x < G) {
-        const int h = threadIdx.x;
-        float M = s_m[h], L = s_l[h];
-#pragma unroll
-        for (int w = 1; w < kWaves; w++) { M = fmaxf(M, s_m[w * G + h]); L += s_l[w * G + h]; }
-        float* slab_ml = a.ws_ml + ((int64_t)blockIdx.x * a.BH + bh0 + h) * 2;
-        slab_ml[0] = M;
-        slab_ml[1] = L;
-    }
-    MUSTAFAR_PTRACE_END(3);
-}
-
 // The lean form at the PAIR grain: two waves share a 64-token block -- 64 channels each in the key phase (partial scores folded
 // through LDS), one 64-channel half of the output each in the value phase -- and a workgroup (two pairs) takes two blocks at a
-// time.  The whole-block form above has the fewest instructions per tile but its waves live 40 us and wait on memory with nobody
-// to cover for them (probe builds: -12 us without the stream loads, -8 us with hot metadata; the pair grain: -2 / -2): half-size
-// waves, twice as many, is the grain at which the launch is bound by instruction issue, so this is the form that runs by default.
-//   grid: x = ceil(T / 64 / a.tb_per_wg) (a.tb_per_wg = blocks per WORKGROUP, even), y as decode_onepass_lean_kernel.
+// time.  A form with whole blocks per wave (round 3, removed) had the fewest instructions per tile but its waves lived 40 us and
+// waited on memory with nobody to cover for them (probe builds: -12 us without the stream loads, -8 us with hot metadata; the pair
+// grain: -2 / -2): half-size waves, twice as many, is the grain at which the launch is bound by instruction issue.
+//   grid: x = ceil(T / 64 / a.tb_per_wg) (a.tb_per_wg = blocks per WORKGROUP, even), y = kv-heads * groups / G (+ |win_rows| rows of
+//   window workgroups, leading or trailing).  e scratch: a.e_rows is used as [y][T / 64][G heads][64 tokens] halfs (G T halfs per y:
+//   fits the [BH, ld >= T] score buffer), every block's segments contiguous bytes on scalar-cache lines of their own.
 //   e round trip (vector engines): each wave stores the e segments of the two heads it finishes (the softmax step is split between
-//   the waves of a pair) and waits vmcnt(0) before the barrier; both waves then scalar-load all four segments (the invariant stated
-//   at decode_onepass_lean_kernel, with "the same wave" read as "the same pair").  Matrix-pipe engine: e goes into the pair's LDS table.
+//   the waves of a pair) and waits vmcnt(0) before the barrier; both waves then scalar-load all four segments.
+// INVARIANT of the e round trip (vector stores, then scalar loads of the same bytes by the SAME pair of waves): a wave waits vmcnt(0)
+// -- the stores are acknowledged by L2 -- before the barrier behind which the pair issues the scalar loads; no wave scalar-reads those
+// lines earlier in the launch (a block's segments belong to one pair and are 64-byte aligned, ld_scores % 32 == 0 is checked by the
+// host), so the only stale copy the scalar cache could hold is one from an EARLIER launch reusing the scratch, and every dispatch
+// (graph nodes included) starts with an acquire that invalidates the scalar cache.  tests/test_gpu_benchshape.py replays a captured
+// step with alternating queries to hold this.  Matrix-pipe engine: e goes into the pair's LDS table, no round trip.
 // Compiled for 8 waves per SIMD (<= 64 vector registers; the scalar file then spills ~45 values to lanes of a vector register):
 // with the stream loads non-temporal the launch is bound by how many waves are there to cover for each other (c3, dot2 form:
-// 7 waves 45.6 us, 8 waves 44.3 us).  MUSTAFAR_LP_WAVES: experiment knob (tools/build_variant.sh).
-#ifndef MUSTAFAR_LP_WAVES
-#define MUSTAFAR_LP_WAVES 8
-#endif
-#define MUSTAFAR_LP_BOUNDS __launch_bounds__(kThreads, MUSTAFAR_LP_WAVES)
+// 7 waves 45.6 us, 8 waves 44.3 us).
+constexpr int kLpWaves = 8;
 // Issue priority by PROGRESS (pair form): s_setprio 1 while a wave is on its FIRST block, 0 afterwards.  The arbiter serves equal
 // priorities oldest wave first, so the workgroups dispatched first ran ahead and left (the first ones at 60 % of the launch's span)
 // while the youngest dragged on at falling occupancy; with this the laggards overtake whoever has reached a second block.
 // Measured (c3, kernel us, same box): dot2 45.3 -> 44.3, matrix pipe 35.5 -> 33.2; c4 76.1 -> 73.2 / 59.9 -> 57.3; c5 unchanged.  A level
 // per PHASE (3, 2, 1, 0) was slower on the vector engines (c3 46.9, c5 148.6 vs 139.5: strict least-progress-first lines the waves
-// up on memory) -- profiles/r04_probes.txt.  MUSTAFAR_PRIO=0: off (experiment builds).
-#ifndef MUSTAFAR_PRIO
-#define MUSTAFAR_PRIO 1
-#endif
+// up on memory) -- profiles/r04_probes.txt.
 template <int ENG, bool EXT = false, int G = 4>   // G: q-heads per kv-head served by one pass (4, 2 or 1; G < 4 runs the v_fma_mix engine);
                                                 // EXT: the cache grew by extents (a.k_ext / a.v_ext / a.nb0); an instantiation of its own, so that
                                        // the plain launch does not carry the extra arguments (matrix-pipe form at c3: 37.6 vs 38.7 us)
-__global__ MUSTAFAR_LP_BOUNDS void decode_onepass_leanpair_kernel(
+__global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_leanpair_kernel(
     const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
     const uint32_t* __restrict__ k_nz_off, const uint64_t* __restrict__ v_bmp, const unsigned char* __restrict__ v_nz,
     const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_nz_off, OneArgs a, int64_t k_bmp_stride,
@@ -2864,9 +2274,6 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_leanpair_kernel(
     const int wrows = a.win_rows < 0 ? -a.win_rows : a.win_rows;   // window rows lead (win_rows > 0) or trail (< 0) the grid
     const int wy = a.win_rows < 0 ? (int)blockIdx.y - ((int)gridDim.y - wrows) : (int)blockIdx.y;
     if (wy >= 0 && wy < wrows) {   // dense window
-#ifdef MUSTAFAR_WIN_PRIO   // experiment: the window workgroups (short latency chains dispatched behind the SpMV rows) at a high issue priority
-        __builtin_amdgcn_s_setprio(MUSTAFAR_WIN_PRIO);
-#endif
         const int task = wy * gridDim.x + blockIdx.x;
         if (task < (int)(gridDim.y - wrows) * a.nchunks) {
             int T_used = -1;
@@ -2965,7 +2372,7 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_leanpair_kernel(
     for (int h = 0; h < G; h++) acc[h] = 0.f;
 #pragma unroll
     for (int j = 0; j < HW; j++) { m_run[j] = -INFINITY; l_run[j] = 0.f; }
-    if (MUSTAFAR_PRIO) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
     for (int t = tb0; t < tb_end; t += kWaves / 2) {   // workgroup-uniform: every wave reaches the barriers below
         const int tb = t + pair;
@@ -3040,7 +2447,7 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_leanpair_kernel(
             prefetch_done(pfv);
         }
         MUSTAFAR_PTRACE_STAMP(5);
-        if (MUSTAFAR_PRIO) __builtin_amdgcn_s_setprio(0);   // (the first block is done)
+        __builtin_amdgcn_s_setprio(0);   // (the first block is done)
     }
     if (a.pair_slabs) {
         // ---- a slab per pair: each wave stores its output half as it holds it and the (maximum, sum) of its two heads -- no exchange, no
@@ -3107,10 +2514,8 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_leanpair_kernel(
 //     prefetch another: no vector address arithmetic;
 //   * MASK is a template parameter (the unmasked launch carries no mask arithmetic).
 // Same grid, slabs and window workgroups as decode_onepass_leanpair_kernel: a drop-in for it (`mustafar_tune(8, 0)` selects the old kernel).
-#ifndef MUSTAFAR_SB_PRIO
-#define MUSTAFAR_SB_PRIO 3   // s_setprio 1 from the start of a trip to: 1 = the end of its key phases, 2 = the end of its softmax step, 3 = the last chunk of
-                             // its value phases (c3, kernel us: 42.6 / 42.3 / 42.0 / 40.8 for 0 / 1 / 2 / 3); 0 = never raised (experiment knob: tools/build_variant.sh)
-#endif
+// Issue priority: s_setprio 1 from the start of a trip to the last chunk of its value phases (c3, kernel us: never raised 42.6, to the end of
+// the key phases 42.3, to the end of the softmax step 42.0, this 40.8).
 template <int W>
 struct FVec;
 template <> struct FVec<1> { typedef float type; };
@@ -3142,19 +2547,9 @@ __device__ __forceinline__ uint32_t ld_at(const void* __restrict__ sbase, uint32
 {
     return *reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(sbase) + voff);
 }
-#ifndef MUSTAFAR_SB_TRIPLOOP
-#define MUSTAFAR_SB_TRIPLOOP 1
-#endif
-#ifndef MUSTAFAR_SPEC
-#define MUSTAFAR_SPEC 0           // (experiment, measured slower: the speculative first-chunk request of DESIGN 4.1 item 25 is compiled in only with -DMUSTAFAR_SPEC=1)
-#endif
-#ifndef MUSTAFAR_SPEC_LINES
-#define MUSTAFAR_SPEC_LINES 16    // (experiment: 128-byte lines of the speculative first-chunk request, a power of two <= 64; MUSTAFAR_SPEC_BACK bytes in front of the prediction)
-#define MUSTAFAR_SPEC_BACK 512
-#endif
 template <int ENG, bool EXT = false, int G = 4, bool MASK = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
                                                                      // decode_onepass_leanpair_kernel; round 5 carried an uninstantiated online form here -- removed in round 6)
-__global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
+__global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
     const uint32_t* __restrict__ k_nz_off, const uint64_t* __restrict__ v_bmp, const unsigned char* __restrict__ v_nz,
     const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_nz_off, OneArgs a, int64_t k_bmp_stride,
@@ -3280,16 +2675,13 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
     for (int j = 0; j < HW; j++) { m_run[j] = -INFINITY; l_lane[j] = 0.f; }
     const bool late_round = (int)(blockIdx.y * gridDim.x + blockIdx.x) >= a.hi_prio_from;   // (workgroup-uniform)
     if (late_round) __builtin_amdgcn_s_setprio(3);
-    else if (MUSTAFAR_SB_PRIO) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(1);
     asm volatile("; sb_trips_begin");   // (markers for tools/isa_breakdown.py --markers: a comment in the ISA, no instruction)
-#if MUSTAFAR_SB_TRIPLOOP
     // ONE trip, written as a loop the compiler may not unroll: a scheduling region boundary around the trip.  It computes the same thing as the bare block;
     // what it changes is where the register allocator reloads its 30-odd spilled scalars (bare block: 14 more v_readlane, several of them inside the steps of
     // the phases: ~1 us at c3, profiles/r06_probes.txt item 6).  Correctness does not hang on it (round 6, item 1: the DOT guard does that job).
 #pragma unroll 1
-    for (int trip = 0; trip < 1; trip++)
-#endif
-    {
+    for (int trip = 0; trip < 1; trip++) {
         const int tA = pb0;
         const bool actA = tA < pb_end, actB = tA + 1 < pb_end;   // (wave-uniform)
         const int tAc = actA ? tA : tb0;                          // (an idle pair addresses the workgroup's first block and computes nothing)
@@ -3312,14 +2704,6 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
             const uint32_t* kiA = ki + (int64_t)tAc * kTilesPerTb;
             uint32_t bndK = ld_at(kiA, off_bnd);
             const uint32_t pfKA = ld_at(kbA, off_bmp);
-            uint32_t pfS = 0;
-            if (MUSTAFAR_SPEC && a.spec_k_bytes > 0 && k_nz_stride && !(EXT && tb0 >= a.nb0)) {
-                // speculative request for the first key chunk (behind the bounds load in program order: the bounds' wait does not cover it): 32 lines of
-                // 128 bytes from 1 KiB in front of where block tAc's half would start if every block had the average length, clamped to the head's region
-                const int64_t pred = (int64_t)tAc * a.spec_k_bytes + (odd ? a.spec_k_bytes / 2 : 0) - MUSTAFAR_SPEC_BACK + (lane & (MUSTAFAR_SPEC_LINES - 1)) * 128;
-                const int64_t last = (int64_t)k_nz_stride * 16 - 4;
-                pfS = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(kn + ((uint32_t)(pred < 0 ? 0 : pred > last ? last : pred) & ~3u)));
-            }
             if constexpr (MASK) {
                 mkA = mrow[tAc * 64 + lane];
                 if (actB) mkB = mrow[tBc * 64 + lane];
@@ -3338,11 +2722,9 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
                 lean_pair_phase<ENG, kD * 2, false, G>(lds, lds_addr, kbA, kiA, kn, qb, bndK, lane, sA, sB MUSTAFAR_PTRACE_ARG, ctab_q, reqKB, reqVA);
                 prefetch_done(pfKA);
                 prefetch_done(pfKB);
-                if (MUSTAFAR_SPEC) prefetch_done(pfS);
             } else {
                 lean_block_phase<ENG, kD * 2, false, 0, 2, G, const void*, 0>(lds, lds_addr, kbA, kiA, kn, qb, bndK, lane, sA, sA MUSTAFAR_PTRACE_ARG, ctab_q, reqVA);
                 prefetch_done(pfKA);
-                if (MUSTAFAR_SPEC) prefetch_done(pfS);
             }
             fvG oA, oB;
             if constexpr (G == 1) { oA = sA[0]; oB = sB[0]; }
@@ -3353,7 +2735,6 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
             xch_out[0] = oA;
             xch_out[64] = oB;
         }
-        if (MUSTAFAR_SB_PRIO == 1 && !late_round) __builtin_amdgcn_s_setprio(0);
         MUSTAFAR_PTRACE_STAMP(2);
         __syncthreads();
         if (actA && has_heads) {
@@ -3383,7 +2764,6 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
             }
             if constexpr (ENG != 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my e stores have reached L2 before the pair's scalar loads
         }
-        if (MUSTAFAR_SB_PRIO == 2 && !late_round) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         MUSTAFAR_PTRACE_STAMP(3);
         if (actA) {
@@ -3391,7 +2771,7 @@ __global__ MUSTAFAR_LP_BOUNDS void decode_onepass_sb_kernel(
             if (actB) {
                 uint32_t pfVB = 0;
                 auto reqVB = [&]() { pfVB = ld_at(vbA + kTilesPerTb, off_bmp); };
-                auto dropPrio = [&]() { if (MUSTAFAR_SB_PRIO == 3 && !late_round) __builtin_amdgcn_s_setprio(0); };   // (in front of the last chunk: the trip is nearly done)
+                auto dropPrio = [&]() { if (!late_round) __builtin_amdgcn_s_setprio(0); };   // (in front of the last chunk: the trip is nearly done)
                 lean_pair_phase<ENG, 64 * 2, true, G>(lds, lds_addr, vbA, viA, vn, eA, bndV, lane, acc, acc MUSTAFAR_PTRACE_ARG, ctab_e, reqVB, dropPrio);
                 prefetch_done(pfVA);
                 prefetch_done(pfVB);
@@ -3741,7 +3121,7 @@ __global__ __launch_bounds__(kThreads, 4) void decode_onepass_small_kernel(
 // calls.  N = rows per head of the dense operand: 1, or the hook's 8 (llama_mustafar_kernel.py:273: rows 1..7 are zero padding and
 // are written as exact zeros unless a row holds a non-zero, in which case it is computed like row 0).
 template <int G, int ENG, int N, bool WIN = false>   // WIN: the launch carries window workgroups (fused two-launch decode); as value_lean_kernel
-__global__ MUSTAFAR_LP_BOUNDS void key_lean_kernel(
+__global__ __launch_bounds__(kThreads, kLpWaves) void key_lean_kernel(
     const uint64_t* __restrict__ bmp, const unsigned char* __restrict__ nz, const uint32_t* __restrict__ idx,
     const uint32_t* __restrict__ nz_off, const h16* __restrict__ q, h16* __restrict__ out, int T, int groups, int ldc, WinArgs wa,
     int64_t bmp_stride, int64_t idx_stride, uint32_t nz_stride)
@@ -3840,24 +3220,13 @@ __global__ MUSTAFAR_LP_BOUNDS void key_lean_kernel(
 // The reference entry point Value_SplitK_API (kernel/csrc/SpMM_API.cu:193-254 -> Value_Kernel, SpMM_Kernel.cuh:421-676) on the
 // machinery of the one-pass launch's value phase: two waves share a 64-token block (one 64-channel half of the output each), a
 // workgroup (two pairs) walks its token chunk two blocks at a time, every address inside a block is a base pointer + an immediate
-// (one pointer per head for the probabilities: their rows are N * ldb halfs apart, a runtime quantity), non-temporal stream loads,
+// (for the probabilities one base pointer + a scalar byte offset per further head, CoefStride: their rows are N * ldb halfs apart, a runtime quantity), non-temporal stream loads,
 // 8 waves per SIMD, issue priority by progress.  v_fma_mix: exact products.  Slabs, flags and the combine pass as value_spmv_kernel.
-#ifndef MUSTAFAR_VL_STRIDE
-#define MUSTAFAR_VL_STRIDE 1   // the probabilities' rows through one base pointer + a scalar offset per head (0: a pointer per head, round 4 / 5a)
-#endif
-#ifndef MUSTAFAR_VL_PFCOEF
-#define MUSTAFAR_VL_PFCOEF 1   // the probabilities of a pair's blocks prefetched into L2 at the top of the trip (round 6; 0: not)
-#endif
-#if MUSTAFAR_VL_STRIDE
-#define MUSTAFAR_VL_COEF CoefStride
-#else
-#define MUSTAFAR_VL_COEF CoefPtrs
-#endif
 // WIN: the launch carries window workgroups (fused two-launch decode, N == 1).  An instantiation of its own: within this kernel's 64
 // vector registers the window path spills to scratch, and a kernel with a private segment -- even one its SpMV workgroups never touch --
 // is launched with scratch; the reference entry point (no window) must not pay for that.
 template <int G, int N, bool WIN = false>
-__global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
+__global__ __launch_bounds__(kThreads, kLpWaves) void value_lean_kernel(
     const uint64_t* __restrict__ bmp, const unsigned char* __restrict__ nz, const uint32_t* __restrict__ idx,
     const uint32_t* __restrict__ nz_off, const h16* __restrict__ p, h16* __restrict__ out, float* __restrict__ ws,
     uint32_t* __restrict__ flags, int T, int groups, int BH, int tb_per_wg, int direct, int ldb, WinArgs wa,
@@ -3887,7 +3256,6 @@ __global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
     // chunks' slabs and computes, chunk by chunk, the rows that hold a non-zero.  With the hook's zero pads (model :313) it reads ~14 vectors per
     // thread and leaves -- in the tail of the launch, where the chip has wave slots to spare.  (Rounds 4-5: every workgroup read its pad slice in
     // FRONT of row 0 -- three barriers and a trip to memory before its first stream request: c3, N = 8, 48.4 us per call against 26 for N = 1.)
-    constexpr int kPadGroup = MUSTAFAR_PAD_GROUP;
     const int hb_per_kv = groups / G;
     const int gy_main = N > 1 ? (BH / groups) * hb_per_kv : (int)gridDim.y;
     const bool pad_wg = N > 1 && (int)blockIdx.y >= gy_main;
@@ -3928,7 +3296,7 @@ __global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
 #pragma unroll
         for (int h = 0; h < G; h++) acc[h] = 0.f;
         if (live) {
-            if (MUSTAFAR_PRIO) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
             // round 5: a pair takes a contiguous half of the workgroup's blocks and walks it TWO blocks at a time as one pipeline of four
             // chunks (lean_pair_phase: the next block's first chunk is in flight while this block's last one is worked on -- what the
             // round-1 kernel's cross-block prefetch bought it over round 4's lean form); one body for both waves (biased pointers)
@@ -3940,7 +3308,6 @@ __global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
             const uint32_t off_bmp = (lane & 7) * 64u;
             const bool lanesB = lane >= 8 && lane < 16;
             const uint32_t head_bytes = (uint32_t)N * (uint32_t)ldb * 2u;   // (rows of consecutive heads; < 2^32: N * ldb < 2^31 halfs is checked by the launcher's T limit)
-            (void)head_bytes;
 #pragma unroll 1
             for (int tb = pb0; tb < pb_end; tb += 2) {   // (wave-uniform; no barrier inside the loop: the pairs run freely)
                 const uint64_t* vbt = vbo + (int64_t)tb * kTilesPerTb;
@@ -3949,36 +3316,27 @@ __global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
                 uint32_t bnd = ld_at(vit, off_bnd);
                 if (two && lanesB) bnd = ld_at(vit + kTilesPerTb, off_bnd);
                 const uint32_t pfA = ld_at(vbt, off_bmp);
-                MUSTAFAR_VL_COEF<G> cb;
-#if MUSTAFAR_VL_STRIDE
+                CoefStride<G> cb;
                 cb.base = p + ((int64_t)bh0 * N + n) * ldb + (int64_t)tb * 64;
 #pragma unroll
                 for (int h = 1; h < G; h++) cb.off[h - 1] = (uint32_t)h * head_bytes;
-#else
-#pragma unroll
-                for (int h = 0; h < G; h++) cb.p[h] = p + ((int64_t)(bh0 + h) * N + n) * ldb + (int64_t)tb * 64;
-#endif
-#if MUSTAFAR_VL_STRIDE && MUSTAFAR_VL_PFCOEF
                 // round 6: the probabilities of these (<= 2) blocks, 128 bytes per block and head, asked into L2 by a vector load NOW -- the steps read them with
                 // scalar loads inside their one wait, and a row the softmax kernel wrote a moment ago (or one 127 KiB from its neighbour: the hook's 8-row
                 // operand) is not in L2 when they do: us per call at c3, same box, without / with: 8 rows 34.0-34.3 / 28.0-28.2, one row 26.1-26.9 / 24.9-25.0; c4 51.0 / 49.6 and 45.0 / 41.4-42.9 (profiles/r06_probes.txt item 9).  Lanes 0..2G-1: (head, block); behind the
                 // bounds and the bitmap lines in program order, so no wait of theirs covers it.
                 const uint32_t pfP = ld_at(cb.base, (uint32_t)(((lane & (2 * G - 1)) >> 1) * head_bytes + ((lane & 1) && two ? 128u : 0u)));
-#endif
                 if (two) {
                     uint32_t pfB = 0;
                     auto reqB = [&]() { pfB = ld_at(vbt + kTilesPerTb, off_bmp); };
-                    lean_pair_phase<0, 0, true, G, decltype(reqB), NoMid, MUSTAFAR_VL_COEF<G>, 64 * 2>(lds, lds_addr, vbt, vit, vn, cb, bnd, lane, acc, acc MUSTAFAR_PTRACE_ARG, 0u,
+                    lean_pair_phase<0, 0, true, G, decltype(reqB), NoMid, CoefStride<G>, 64 * 2>(lds, lds_addr, vbt, vit, vn, cb, bnd, lane, acc, acc MUSTAFAR_PTRACE_ARG, 0u,
                                                                                                            reqB, NoMid());
                     prefetch_done(pfB);
                 } else {
-                    lean_block_phase<0, 0, true, 0, 2, G, MUSTAFAR_VL_COEF<G>>(lds, lds_addr, vbt, vit, vn, cb, bnd, lane, acc, acc MUSTAFAR_PTRACE_ARG);
+                    lean_block_phase<0, 0, true, 0, 2, G, CoefStride<G>>(lds, lds_addr, vbt, vit, vn, cb, bnd, lane, acc, acc MUSTAFAR_PTRACE_ARG);
                 }
                 prefetch_done(pfA);
-#if MUSTAFAR_VL_STRIDE && MUSTAFAR_VL_PFCOEF
                 prefetch_done(pfP);
-#endif
-                if (MUSTAFAR_PRIO) __builtin_amdgcn_s_setprio(0);   // (the first blocks are done)
+                __builtin_amdgcn_s_setprio(0);   // (the first blocks are done)
             }
         }
         __syncthreads();   // every wave is done with its stage window (and with the previous row's sums)
@@ -4004,13 +3362,8 @@ __global__ MUSTAFAR_LP_BOUNDS void value_lean_kernel(
         if (pad_wg) {
             const int cw = tb_per_wg * 64;                              // tokens (columns of the dense operand) per chunk
             const int col0 = slab0 * cw, ncols = min(T, col0 + nck * cw) - col0;
-#ifdef MUSTAFAR_PROBE_NOPADREAD   // (timing probe: the pad workgroups are dispatched and publish "nothing live" without reading anything -- wrong for non-zero pads)
-            all = 0u;
-            (void)col0; (void)ncols;
-#else
             all = (uint32_t)__builtin_amdgcn_readfirstlane(
                 (int)pad_group_mask<G, N>(p, ldb, bh0, col0, ncols, cw, reinterpret_cast<uint32_t*>(smem)));   // bits 8 c + n: pad row n over chunk c
-#endif
             if (!direct && (int)threadIdx.x < nck)
                 flags[(slab0 + (int)threadIdx.x) * gy_main + by] = ((all >> (8 * threadIdx.x)) & 0xfeu) | 1u;   // (row 0: every slab, always; no window rows when N > 1)
             if (all == 0u && !direct) { MUSTAFAR_TRACE_END(); return; }
@@ -4035,22 +3388,39 @@ inline int pick_g(int groups) { return (groups % 4 == 0) ? 4 : (groups % 2 == 0)
 // included; MUSTAFAR_FMA_ENGINE=valu), 1 = matrix pipe as a 4-wide FMA unit (v_mfma_f32_4x4x4_16B_f16; opt-in, MFMA left off by
 // default as the north_star asks: MUSTAFAR_FMA_ENGINE=mfma or mustafar_set_fma_engine(1)).
 inline int fma_engine();
-int g_key_lean = -1;    // the two reference entry points on the lean pair machinery (round 4): MUSTAFAR_KEY_LEAN / MUSTAFAR_VALUE_LEAN = 0 | 1
-inline bool key_lean()
+
+// ------------------------------------------------------------------------------------------------ run-time knobs
+// A process default lives in a g_* variable: -1 until its environment variable is read, ONCE, at first use (`parse` sees the
+// string, `unset` is the value without it); mustafar_tune / mustafar_set_* overwrite the variable and win from then on.
+template <class F>
+inline int env_knob(int& g, const char* name, int unset, F parse)
 {
-    if (g_key_lean < 0) {
-        const char* e = getenv("MUSTAFAR_KEY_LEAN");
-        g_key_lean = e ? atoi(e) != 0 : 1;
+    if (g < 0) {
+        const char* e = getenv(name);
+        g = e ? parse(e) : unset;
     }
-    return g_key_lean != 0;
+    return g;
 }
+inline int env_bool(int& g, const char* name, int unset) { return env_knob(g, name, unset, [](const char* e) { return atoi(e) != 0 ? 1 : 0; }); }
+inline int env_int(int& g, const char* name, int unset) { return env_knob(g, name, unset, [](const char* e) { return atoi(e); }); }
+
+// CUs of the current device (256 if the runtime will not say), asked once, at the first call that needs it -- not when the library is loaded
+inline int cu_count()
+{
+    static const int n = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return cus > 0 ? cus : 256;
+    }();
+    return n;
+}
+
+int g_key_lean = -1;    // the two reference entry points on the lean pair machinery (round 4): MUSTAFAR_KEY_LEAN / MUSTAFAR_VALUE_LEAN = 0 | 1
+inline bool key_lean() { return env_bool(g_key_lean, "MUSTAFAR_KEY_LEAN", 1) != 0; }
 int g_key_split = -1;   // 0 = automatic; MUSTAFAR_KEY_SPLIT=1|2 forces
 inline int key_split(int ntb, int gy)
 {
-    if (g_key_split < 0) {
-        const char* e = getenv("MUSTAFAR_KEY_SPLIT");
-        g_key_split = e ? atoi(e) : 0;
-    }
+    env_int(g_key_split, "MUSTAFAR_KEY_SPLIT", 0);
     if (g_key_split == 1 || g_key_split == 2) return g_key_split;
     if (fma_engine() == 1) return 1;   // matrix-pipe engine: one wave per block at every size (tools/sweep_forms.sh: c3 19.1 vs 20.2 us, c5 57 vs 65)
     // One wave per token block unless that grid is small (<= 2048 workgroups; the chip holds 256 CUs x 6 of them, see
@@ -4062,11 +3432,7 @@ inline int key_split(int ntb, int gy)
 int g_window_mode = -1;   // bit 0: key side rides, bit 1: value side rides
 inline int window_ride_mask()
 {
-    if (g_window_mode < 0) {
-        const char* e = getenv("MUSTAFAR_WINDOW");
-        g_window_mode = !e ? 3 : e[0] == 'r' ? 0 : e[0] == 'k' ? 1 : e[0] == 'v' ? 2 : 3;
-    }
-    return g_window_mode;
+    return env_knob(g_window_mode, "MUSTAFAR_WINDOW", 3, [](const char* e) { return e[0] == 'r' ? 0 : e[0] == 'k' ? 1 : e[0] == 'v' ? 2 : 3; });
 }
 // Where the window workgroups sit in the grid: in front of the SpMV rows in the key launch (the softmax behind it waits
 // for their scores anyway, and they are done in the first microseconds), behind them in the value launch (they are
@@ -4075,19 +3441,15 @@ inline int window_ride_mask()
 int g_window_last = -1;   // bit 0: key launch, bit 1: value launch
 inline bool window_rows_last(int side)
 {
-    if (g_window_last < 0) {
-        const char* e = getenv("MUSTAFAR_WINDOW_POS");
-        g_window_last = !e ? 2 : e[0] == 'l' ? 3 : e[0] == 'k' ? 1 : e[0] == 'v' ? 2 : 0;
-    }
+    env_knob(g_window_last, "MUSTAFAR_WINDOW_POS", 2, [](const char* e) { return e[0] == 'l' ? 3 : e[0] == 'k' ? 1 : e[0] == 'v' ? 2 : 0; });
     return (g_window_last >> side) & 1;
 }
-// Structure of the fused decode entry point: 1 = one-pass launch (decode_onepass_kernel + onepass_finish_kernel),
+// Structure of the fused decode entry point: 1 = one-pass launch (a decode_onepass_*_kernel + a row kernel that merges the slabs),
 // 0 = key SpMV -> softmax rows -> value SpMV -> sum, 2 = by size (default).  MUSTAFAR_ONEPASS=0|1|auto, mustafar_set_onepass().
-// Measured (round 2, fused + graph, tokens/s one-pass vs two-launch).  VALU engine: c2 1566 vs 1282, c3 3970 vs 3890,
-// c4 1194 vs 1285, c5 2561 vs 2819 -- the one-pass launch saves the softmax launch, a boundary and a ramp, which is what
-// counts while a launch is tens of microseconds, and loses once the launches are long (its pair form pays two barriers per
-// block).  Matrix-pipe engine (e stays in LDS, no barriers): c3 5200 vs 4590, c4 1676 vs 1543, c5 3672 vs 3391 -- one-pass
-// at every size.  `by size` = that rule.
+// Since round 3 every engine and group count has a one-pass form that wins at every size (tokens/s one-pass vs two launches --
+// dot2: c3 5110 vs 4180, c4 1540 vs 1350, c5 3470 vs 3130; fma_mix: c4 1416 vs 1353, c5 3111 vs 3131; matrix pipe, round 2:
+// c3 5200 vs 4590, c4 1676 vs 1543, c5 3672 vs 3391), so `by size` means one-pass wherever the launch can run: T > 0 and
+// ld_scores % 32 == 0.  (Round 2's kernel lost to two launches at c4 / c5 on the VALU engine; it is gone, DESIGN.md.)
 // Process DEFAULTS live in the g_* variables (environment, mustafar_set_fma_engine / mustafar_set_onepass); a fused call may carry
 // its own choice in its `flags` argument, in force for that call only (t_engine / t_onepass: set and cleared by decode_attention
 // on the calling thread).
@@ -4097,77 +3459,34 @@ int g_onepass = -1;
 inline int onepass_mode()
 {
     if (t_onepass >= 0) return t_onepass;
-    if (g_onepass < 0) {
-        const char* e = getenv("MUSTAFAR_ONEPASS");
-        g_onepass = !e ? 2 : e[0] == '0' ? 0 : e[0] == '1' ? 1 : 2;
-    }
-    return g_onepass;
+    return env_knob(g_onepass, "MUSTAFAR_ONEPASS", 2, [](const char* e) { return e[0] == '0' ? 0 : e[0] == '1' ? 1 : 2; });
 }
-inline bool onepass_enabled(int64_t kv_heads, int T);
-int g_onepass_wgs = -1;   // MUSTAFAR_ONEPASS_WGS=n overrides the workgroup target of the one-pass launch
-inline int onepass_target_wgs(bool pair)
-{
-    if (g_onepass_wgs < 0) {
-        const char* e = getenv("MUSTAFAR_ONEPASS_WGS");
-        g_onepass_wgs = e ? atoi(e) : 0;
-    }
-    return g_onepass_wgs > 0 ? g_onepass_wgs : (pair ? 4096 : 0);   // (VALU pair form: flat from 4096 workgroups up at c3; 0: fixed blocks per workgroup)
-}
-// GQA-4 one-pass launches on the vector engines: MUSTAFAR_ONEPASS_LEAN=2 (default) the lean kernel at the pair grain, 1 the lean
-// kernel with whole blocks per wave, 0 the round-2 pair form; MUSTAFAR_LEAN_TBW=n: blocks per wave (1) / block pairs per
-// workgroup (2) instead of the automatic choice (raised when the slabs would not fit).
-int g_finish1 = [] { const char* e = getenv("MUSTAFAR_FINISH1"); return e ? atoi(e) != 0 : 1; }();   // round 5: the one-thread-per-channel row kernel for rows of <= 64 slabs (mustafar_tune(10, v))
-int g_sb = [] { const char* e = getenv("MUSTAFAR_SB"); return e ? atoi(e) != 0 : 1; }();   // round 5: the super-block pair form (mustafar_tune(8, 0): round 4's pair kernel)
-int g_small = [] { const char* e = getenv("MUSTAFAR_SMALL"); return e ? atoi(e) : 1; }();   // round 6: decode_onepass_small_kernel: 1 = for launches of at most small_waves() waves (default), 2 = for every launch of two
-                                                                                          // blocks per workgroup, 0 = never (mustafar_tune(11, v))
-inline int small_waves()   // one wave per SIMD: 4 x the CU count (asked of the runtime at the first fused call, not when the library is loaded)
-{
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return (cus > 0 ? cus : 256) * 4;
-    }();
-    return n;
-}
-int g_spec_k_bytes = 0; // mustafar_tune(12, bytes): experiment, see OneArgs::spec_k_bytes
+int g_onepass_wgs = -1;   // MUSTAFAR_ONEPASS_WGS=n overrides the workgroup count of the one-pass launch (0: automatic); mustafar_tune(2, n)
+inline int onepass_wgs() { return env_int(g_onepass_wgs, "MUSTAFAR_ONEPASS_WGS", 0); }
+// One-pass launches: MUSTAFAR_LEAN_TBW=n / mustafar_tune(1, n): n block pairs per workgroup instead of the automatic choice
+// (raised when the slabs would not fit).
+int g_finish1 = -1;   // round 5: the one-thread-per-channel row kernel for rows of <= 64 slabs (MUSTAFAR_FINISH1, mustafar_tune(10, v))
+inline bool finish1() { return env_bool(g_finish1, "MUSTAFAR_FINISH1", 1) != 0; }
+int g_sb = -1;        // round 5: the super-block pair form (MUSTAFAR_SB=0, mustafar_tune(8, 0): round 4's pair kernel)
+inline bool sb_form() { return env_bool(g_sb, "MUSTAFAR_SB", 1) != 0; }
+int g_small = -1;     // round 6: decode_onepass_small_kernel: 1 = for launches of at most small_waves() waves (default), 2 = for every launch of two
+                      // blocks per workgroup, 0 = never (MUSTAFAR_SMALL, mustafar_tune(11, v))
+inline int small_mode() { return env_int(g_small, "MUSTAFAR_SMALL", 1); }
+inline int small_waves() { return cu_count() * 4; }   // one wave per SIMD
 int g_late_prio = 1;    // mustafar_tune(9, 0): no raised priority for a small last round of workgroups (experiments)
 int g_pair_slabs = 0;   // pair form, mustafar_tune(4, 1): a slab per pair instead of one per workgroup (kernel 1.1 us shorter at c3, row kernel 1.5 us longer)
 // g_lean_win_last: the pair form's window workgroups sit BEHIND the SpMV rows of the grid (mustafar_tune(3, 0): in front, round 3a).
 // In front they hold 434 of the chip's 2048 workgroup slots for their ~10 us while the SpMV rows wait; behind, they fill the tail
 // (matrix pipe c3 37.1 -> 36.2 us, c4 61.4 -> 60.0, c5 119.0 -> 115.3; dot2 +-0 at c3 / c4, 139.2 -> 137.3 at c5).
-int g_lean = -1, g_lean_tbw = -1, g_lean_win_last = 1;
-inline int onepass_lean()
-{
-    if (g_lean < 0) {
-        const char* e = getenv("MUSTAFAR_ONEPASS_LEAN");
-        g_lean = !e ? 2 : (e[0] == '0') ? 0 : (e[0] == '1') ? 1 : 2;
-    }
-    return g_lean;
-}
-inline int onepass_lean_tbw()
-{
-    if (g_lean_tbw < 0) {
-        const char* e = getenv("MUSTAFAR_LEAN_TBW");
-        g_lean_tbw = e ? atoi(e) : 0;
-    }
-    return g_lean_tbw;
-}
+int g_lean_tbw = -1, g_lean_win_last = 1;
+inline int onepass_lean_tbw() { return env_int(g_lean_tbw, "MUSTAFAR_LEAN_TBW", 0); }
 int g_engine = -1;
 inline int fma_engine()
 {
     if (t_engine >= 0) return t_engine;
-    if (g_engine < 0) {
-        const char* e = getenv("MUSTAFAR_FMA_ENGINE");
-        g_engine = !e ? 2 : (e[0] == 'm' || e[0] == 'M' || e[0] == '1') ? 1 : (e[0] == 'v' || e[0] == 'V' || e[0] == '0') ? 0 : 2;
-    }
-    return g_engine;
-}
-
-inline bool onepass_enabled(int64_t kv_heads, int T)
-{
-    const int mode = onepass_mode();
-    if (mode != 2) return mode == 1;
-    return true;   // (decode_attention narrows this for the round-2 pair form, the only one that loses to two launches at c4 / c5)
+    return env_knob(g_engine, "MUSTAFAR_FMA_ENGINE", 2, [](const char* e) {
+        return (e[0] == 'm' || e[0] == 'M' || e[0] == '1') ? 1 : (e[0] == 'v' || e[0] == 'V' || e[0] == '0') ? 0 : 2;
+    });
 }
 
 // Optional live timing of the two SpMV kernels inside mustafar_decode_attention (bench.py's roofline leg): HIP
@@ -4250,11 +3569,7 @@ constexpr int kValueWaves = 8;
 int g_value_split = -1;
 inline int value_split()
 {
-    if (g_value_split < 0) {
-        const char* e = getenv("MUSTAFAR_VALUE_SPLIT");
-        g_value_split = e ? (atoi(e) == 1 ? 1 : 2) : 0;
-    }
-    if (g_value_split) return g_value_split;
+    if (env_knob(g_value_split, "MUSTAFAR_VALUE_SPLIT", 0, [](const char* e) { return atoi(e) == 1 ? 1 : 2; })) return g_value_split;
     return fma_engine() == 1 ? 1 : 2;   // the MFMA form needs > 80 VGPRs: 8-wave workgroups would drop to 4 waves per SIMD
 }
 // round 4: the lean pair form of the value entry point (value_lean_kernel, v_fma_mix engine) was opt-in -- MUSTAFAR_VALUE_LEAN=1 /
@@ -4272,17 +3587,14 @@ int g_value_lean = -1;
 int g_value_lean8 = 1;   // round 6: the lean form also for the hook's 8 padded rows (mustafar_tune(13, 0): round 1's kernel for N = 8, as rounds 1-5)
 inline int value_lean_mode()
 {
-    if (g_value_lean < 0) {
-        const char* e = getenv("MUSTAFAR_VALUE_LEAN");
-        g_value_lean = e ? (atoi(e) != 0 ? 1 : 0) : 2;
-    }
+    env_bool(g_value_lean, "MUSTAFAR_VALUE_LEAN", 2);
     return fma_engine() == 1 ? 0 : g_value_lean;
 }
-// Round 6: with the probabilities prefetched (MUSTAFAR_VL_PFCOEF) the lean form wins at every size -- c5 (32 k workgroup-blocks), us per call, lean / round 1's kernel:
+// Round 6: with the probabilities prefetched (value_lean_kernel, pfP) the lean form wins at every size -- c5 (32 k workgroup-blocks), us per call, lean / round 1's kernel:
 // one row 83.4 / 92.5, eight rows 83.6 / 95.9 (round 5, without the prefetch: 80.6 / 78.6, and the size limit of 24 k workgroup-blocks that came from it) -- so "by size"
 // (mode 2, the default) now means: lean whenever the vector engines run, for N = 1 and -- mustafar_tune(13, .) -- the hook's 8 padded rows.
 inline bool value_lean() { return value_lean_mode() != 0; }   // (the workgroup shape follows it, value_tb_stride)
-inline bool value_lean_for(int N, int64_t /*wg_blocks*/) { const int m = value_lean_mode(); return m == 1 || (m == 2 && (N == 1 || g_value_lean8)); }
+inline bool value_lean_for(int N) { const int m = value_lean_mode(); return m == 1 || (m == 2 && (N == 1 || g_value_lean8)); }
 inline int value_tb_stride() { return value_lean() ? kWaves / 2 : value_split() == 2 ? kValueWaves / 2 : kWaves; }   // token blocks in flight per workgroup
 
 // One place that picks the value kernel instantiation.
@@ -4298,10 +3610,9 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
         grid.y += wa.rows;
         if (window_rows_last(1)) wa.rows = -wa.rows;
     }
-    if ((N == 1 || N == 8) && value_lean_for(N, (int64_t)(grid.y - (wa.rows < 0 ? -wa.rows : wa.rows)) * (T / 64))) {
-#ifndef MUSTAFAR_PROBE_NOPADWG   // (timing probe: no pad workgroups at all -- the slabs' row masks stay unwritten)
-        if (N > 1) grid.y += (grid.y * ((grid.x + MUSTAFAR_PAD_GROUP - 1) / MUSTAFAR_PAD_GROUP) + grid.x - 1) / grid.x;
-#endif   // (the pad workgroups behind the row-0 workgroups, one per head group and four chunks: value_lean_kernel)
+    if ((N == 1 || N == 8) && value_lean_for(N)) {
+        // (the pad workgroups behind the row-0 workgroups, one per head group and four chunks: value_lean_kernel)
+        if (N > 1) grid.y += (grid.y * ((grid.x + kPadGroup - 1) / kPadGroup) + grid.x - 1) / grid.x;
 #define MUSTAFAR_LVL(GG)                                                                                                         \
     do {                                                                                                                         \
         if (N == 1 && wa.rows != 0)                                                                                                              \
@@ -4309,8 +3620,6 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
                                   flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);                    \
         else if (N == 1) hipExtLaunchKernelGGL((value_lean_kernel<GG, 1>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,  \
                                           flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);            \
-        else if (MUSTAFAR_PROBE_N1AS8) hipExtLaunchKernelGGL((value_lean_kernel<GG, 1>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,  \
-                                          flags, T, groups, Batch_Size, tb_per_wg, direct, 8 * ldb, wa, bmp_stride, idx_stride, nz_stride);        \
         else        hipExtLaunchKernelGGL((value_lean_kernel<GG, 8>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,  \
                                           flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);            \
     } while (0)
@@ -4486,82 +3795,57 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
     auto knew = static_cast<const h16*>(k_new);
     auto vnew = static_cast<const h16*>(v_new);
     const float inv_sqrt_d0 = (float)(1.0 / (double)sqrt_d);
-    // Structure by size (mode 2): the lean kernels (GQA-4, vector engines) and the matrix-pipe form run one-pass at every size
-    // (round 3, tokens/s one-pass vs two launches -- dot2: c3 5110 vs 4180, c4 1540 vs 1350, c5 3470 vs 3130; fma_mix: c4 1416 vs
-    // 1353, c5 3111 vs 3131); the round-2 pair form (G < 4) while kv-heads x T is small (c2: 1650 vs 1310)
-    // (the matrix-pipe engine has the pair form only: lean == 1 keeps its round-2 whole-block kernel, as lean == 0 does)
-    // (G < 4 -- MHA, GQA-2 -- has the pair form only, on the v_fma_mix engine: round 4; before, its fused calls ran round 2's
-    // decode_onepass_kernel, which reads neither extents nor a device-side T)
-    const bool lean_form = G == 4 ? onepass_lean() != 0 && !(fma_engine() == 1 && onepass_lean() == 1) : onepass_lean() == 2;
     const int eng = G == 4 ? fma_engine() : 0;
-    const bool small = (int64_t)(Batch_Size / groups) * T <= 768000;
-    // appended extents are read by the pair form of the one-pass launch only
-    if (extents && !(T > 0 && lean_form && onepass_lean() == 2 && onepass_enabled(Batch_Size / groups, T) && (ld_scores & 31) == 0))
-        return MUSTAFAR_EINVAL;
-    if (T > 0 && onepass_enabled(Batch_Size / groups, T) && (onepass_mode() == 1 || lean_form || fma_engine() == 1 || small) &&
-        (ld_scores & 31) == 0) {
-        // ---- one-pass form: every wave runs key phase -> softmax step -> value phase on its token blocks; slabs merged per row
+    // appended extents are read by the one-pass launch only
+    if (extents && !(T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0)) return MUSTAFAR_EINVAL;
+    if (T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0) {
+        // ---- one-pass form: every wave runs key phase -> softmax step -> value phase on its token blocks; slabs merged per row.
+        // Pair grain: two waves per block, two blocks per workgroup at a time, for every engine and group count (G < 4 -- MHA,
+        // GQA-2 -- on the v_fma_mix engine).
         const int ntb = T / 64;
-        if (lean_form) {
-            // lean forms (GQA-4, vector engines).  2 (default): pair grain -- two waves per block, two blocks per workgroup at a
-            // time; 1: a wave owns `tbw` consecutive whole blocks.  Four waves merge into one slab either way.
-            const bool lp = onepass_lean() == 2;
-            const int nchunks = (window_capacity + kOneWinChunk - 1) / kOneWinChunk;
-            int per_wg;   // 64-token blocks per workgroup
-            if (lp) {
-                // two block pairs per workgroup (each pair of waves runs its block loop twice) unless that leaves fewer than 1024
-                // workgroups: start-up and merge code are paid once per two blocks and the row kernel folds half the slabs.  With the
-                // window workgroups BEHIND the SpMV rows (below) this is the better shape at c3 too -- round 3a, window rows first:
-                // 3968 workgroups of one pair each (tokens/s, four vs two blocks per workgroup, windows last: matrix pipe c3 6204 vs
-                // 6050, c4 1877 vs 1719, c5 4070 vs 3900; dot2 c3 5122 vs 4992).  MUSTAFAR_ONEPASS_WGS / MUSTAFAR_LEAN_TBW override
-                // (round 5, super-block form: from 768 workgroups -- three per CU -- on; Llama-3-8B 4k x batch 8 is 960 workgroups of four blocks:
-                // 23.5 vs 24.6 us; at 480 (c2) and 248 (8k x batch 1) two blocks per workgroup win, 13.3 vs 15.4 and 11.1 vs 14.6 us)
-                per_wg = (int64_t)((ntb + 3) / 4) * gy >= (g_sb ? 768 : 1024) ? 4 : 2;
-                (void)onepass_target_wgs(true);   // (reads MUSTAFAR_ONEPASS_WGS once)
-                if (g_onepass_wgs > 0) {
-                    const int want = (g_onepass_wgs + gy - 1) / gy;
-                    per_wg = ((ntb + want - 1) / want + 1) / 2 * 2;
-                }
-                if (onepass_lean_tbw() > 0) per_wg = 2 * onepass_lean_tbw();
-            } else {
-                per_wg = kWaves * (onepass_lean_tbw() > 0 ? onepass_lean_tbw() : 1);
-            }
-            const int step = lp ? 2 : kWaves;
-            const int spw = lp && g_pair_slabs && !(g_sb && per_wg <= 4) ? 2 : 1;   // slabs per workgroup (the super-block form always merges its pairs)
-            while (spw * ((ntb + per_wg - 1) / per_wg) + nchunks > kMaxSlabs) per_wg += step;
-            const int S1 = (ntb + per_wg - 1) / per_wg;   // workgroups per head group
-            const int NS = spw * S1;                      // their slabs
-            float* ws_o = static_cast<float*>(workspace);
-            float* ws_ml = ws_o + (int64_t)(NS + nchunks) * Batch_Size * kD;
-            const int win_rows = (gy * nchunks + S1 - 1) / S1;
-            if (extents && (!lp || (per_wg != 2 && per_wg != 4))) return MUSTAFAR_EINVAL;   // a workgroup's blocks stay inside one extent
-            OneArgs a{qh, sc, ws_o, ws_ml, kwin, vwin, knew, vnew, window_len_extra, mask, T, groups, Batch_Size, lp ? per_wg : per_wg / kWaves,
-                      ld_scores, window_len, window_capacity, nchunks, g_lean_win_last ? -win_rows : win_rows, inv_sqrt_d0, spw == 2};
-            a.spec_k_bytes = g_spec_k_bytes;
-            if (extents) {
-                a.k_ext = k_ext;
-                a.v_ext = v_ext;
-                a.nb0 = T_base / 64;
-                a.t_dev = T_device;
-            }
-            const dim3 grid(S1, gy + win_rows);
-            {   // the last round of SpMV workgroups, when it is a small fraction of a resident round (8 workgroups per CU): raised priority
-                static const int slots = [] {
-                    int dev = 0, cus = 256;
-                    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                    return (cus > 0 ? cus : 256) * 8;
-                }();
-                const int64_t W = (int64_t)S1 * gy, full = W / slots * slots;
-                if (g_late_prio && full > 0 && W - full > 0 && (W - full) * 4 <= slots && !(a.win_rows > 0)) a.hi_prio_from = (int)full;
-            }
-            hipEvent_t e0 = prof ? g_prof.ev[4 * g_prof.n] : nullptr, e1 = prof ? g_prof.ev[4 * g_prof.n + 1] : nullptr;
-            auto kz = static_cast<const unsigned char*>(kc.nz), vz = static_cast<const unsigned char*>(vc.nz);
-            bool small_form = false;
+        const int nchunks = (window_capacity + kOneWinChunk - 1) / kOneWinChunk;
+        // 64-token blocks per workgroup: two block pairs per workgroup (each pair of waves runs its block loop twice) unless that leaves fewer than 1024
+        // workgroups: start-up and merge code are paid once per two blocks and the row kernel folds half the slabs.  With the
+        // window workgroups BEHIND the SpMV rows (below) this is the better shape at c3 too -- round 3a, window rows first:
+        // 3968 workgroups of one pair each (tokens/s, four vs two blocks per workgroup, windows last: matrix pipe c3 6204 vs
+        // 6050, c4 1877 vs 1719, c5 4070 vs 3900; dot2 c3 5122 vs 4992).  MUSTAFAR_ONEPASS_WGS / MUSTAFAR_LEAN_TBW override
+        // (round 5, super-block form: from 768 workgroups -- three per CU -- on; Llama-3-8B 4k x batch 8 is 960 workgroups of four blocks:
+        // 23.5 vs 24.6 us; at 480 (c2) and 248 (8k x batch 1) two blocks per workgroup win, 13.3 vs 15.4 and 11.1 vs 14.6 us)
+        int per_wg = (int64_t)((ntb + 3) / 4) * gy >= (sb_form() ? 768 : 1024) ? 4 : 2;
+        if (onepass_wgs() > 0) {
+            const int want = (onepass_wgs() + gy - 1) / gy;
+            per_wg = ((ntb + want - 1) / want + 1) / 2 * 2;
+        }
+        if (onepass_lean_tbw() > 0) per_wg = 2 * onepass_lean_tbw();
+        const int spw = g_pair_slabs && !(sb_form() && per_wg <= 4) ? 2 : 1;   // slabs per workgroup (the super-block form always merges its pairs)
+        while (spw * ((ntb + per_wg - 1) / per_wg) + nchunks > kMaxSlabs) per_wg += 2;
+        const int S1 = (ntb + per_wg - 1) / per_wg;   // workgroups per head group
+        const int NS = spw * S1;                      // their slabs
+        float* ws_o = static_cast<float*>(workspace);
+        float* ws_ml = ws_o + (int64_t)(NS + nchunks) * Batch_Size * kD;
+        const int win_rows = (gy * nchunks + S1 - 1) / S1;
+        if (extents && per_wg != 2 && per_wg != 4) return MUSTAFAR_EINVAL;   // a workgroup's blocks stay inside one extent
+        OneArgs a{qh, sc, ws_o, ws_ml, kwin, vwin, knew, vnew, window_len_extra, mask, T, groups, Batch_Size, per_wg,
+                  ld_scores, window_len, window_capacity, nchunks, g_lean_win_last ? -win_rows : win_rows, inv_sqrt_d0, spw == 2};
+        if (extents) {
+            a.k_ext = k_ext;
+            a.v_ext = v_ext;
+            a.nb0 = T_base / 64;
+            a.t_dev = T_device;
+        }
+        const dim3 grid(S1, gy + win_rows);
+        {   // the last round of SpMV workgroups, when it is a small fraction of a resident round (8 workgroups per CU): raised priority
+            const int slots = cu_count() * 8;
+            const int64_t W = (int64_t)S1 * gy, full = W / slots * slots;
+            if (g_late_prio && full > 0 && W - full > 0 && (W - full) * 4 <= slots && !(a.win_rows > 0)) a.hi_prio_from = (int)full;
+        }
+        hipEvent_t e0 = prof ? g_prof.ev[4 * g_prof.n] : nullptr, e1 = prof ? g_prof.ev[4 * g_prof.n + 1] : nullptr;
+        auto kz = static_cast<const unsigned char*>(kc.nz), vz = static_cast<const unsigned char*>(vc.nz);
+        bool small_form = false;
 #define MUSTAFAR_LL(KERNEL)                                                                                                           \
     hipExtLaunchKernelGGL(KERNEL, grid, dim3(kThreads), 0, st, e0, e1, 0, kc.bmp, kz, kc.idx, kc.nz_offset,                            \
                           vc.bmp, vz, vc.idx, vc.nz_offset, a, kc.bmp_head_stride, kc.idx_head_stride, (uint32_t)kc.nz_head_stride,    \
                           vc.bmp_head_stride, vc.idx_head_stride, (uint32_t)vc.nz_head_stride)
-            if (lp) {
 #define MUSTAFAR_LP(EXTV)                                                                                   \
     do {                                                                                                    \
         if (G == 2)        MUSTAFAR_LL((decode_onepass_leanpair_kernel<0, EXTV, 2>));                       \
@@ -4570,14 +3854,14 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
         else if (eng == 1) MUSTAFAR_LL((decode_onepass_leanpair_kernel<1, EXTV>));                          \
         else               MUSTAFAR_LL((decode_onepass_leanpair_kernel<0, EXTV>));                          \
     } while (0)
-                // (G = 1 without extents: the plain instantiation comes out of the register allocator with a 68-byte private segment it
-                // never touches, and a kernel with a private segment is launched with scratch (+1 % measured on the GQA-4 form); the
-                // extents instantiation has none and serves the same launch with every block in the base views)
-                if (!extents && G == 1) a.nb0 = ntb;
-                if (g_sb && per_wg == 2 && eng != 1 && onepass_lean_tbw() <= 0 && (g_small == 2 || (g_small == 1 && (int64_t)S1 * gy * kWaves <= small_waves()))) {
-                    // round 6: the form without a memory wait inside the phases, for launches that do not even put one wave on every SIMD (c1;
-                    // Llama-3-8B 4k x batch 1): there its shorter chain wins 10 %; from two waves per SIMD on (8k x batch 1, c2) its extra
-                    // v_readlane per step cost more than the waits they replace (profiles/r06_probes.txt item 3).  mustafar_tune(11, 2): always
+        // (G = 1 without extents: the plain instantiation comes out of the register allocator with a 68-byte private segment it
+        // never touches, and a kernel with a private segment is launched with scratch (+1 % measured on the GQA-4 form); the
+        // extents instantiation has none and serves the same launch with every block in the base views)
+        if (!extents && G == 1) a.nb0 = ntb;
+        if (sb_form() && per_wg == 2 && eng != 1 && onepass_lean_tbw() <= 0 && (small_mode() == 2 || (small_mode() == 1 && (int64_t)S1 * gy * kWaves <= small_waves()))) {
+            // round 6: the form without a memory wait inside the phases, for launches that do not even put one wave on every SIMD (c1;
+            // Llama-3-8B 4k x batch 1): there its shorter chain wins 10 %; from two waves per SIMD on (8k x batch 1, c2) its extra
+            // v_readlane per step cost more than the waits they replace (profiles/r06_probes.txt item 3).  mustafar_tune(11, 2): always
 #define MUSTAFAR_SM(EXTV, MASKV)                                                                              \
     do {                                                                                                      \
         if (G == 2)        MUSTAFAR_LL((decode_onepass_small_kernel<0, EXTV, 2, MASKV>));                      \
@@ -4585,11 +3869,11 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
         else if (eng == 2) MUSTAFAR_LL((decode_onepass_small_kernel<2, EXTV, 4, MASKV>));                      \
         else               MUSTAFAR_LL((decode_onepass_small_kernel<0, EXTV, 4, MASKV>));                      \
     } while (0)
-                    if (extents) { if (mask.ptr) MUSTAFAR_SM(true, true); else MUSTAFAR_SM(true, false); }
-                    else         { if (mask.ptr) MUSTAFAR_SM(false, true); else MUSTAFAR_SM(false, false); }
+            if (extents) { if (mask.ptr) MUSTAFAR_SM(true, true); else MUSTAFAR_SM(true, false); }
+            else         { if (mask.ptr) MUSTAFAR_SM(false, true); else MUSTAFAR_SM(false, false); }
 #undef MUSTAFAR_SM
-                    small_form = true;
-                } else if (g_sb && per_wg <= 4) {   // round 5: the super-block pair form (same grid, slabs and window workgroups; a pair walks its <= 2 blocks once)
+            small_form = true;
+        } else if (sb_form() && per_wg <= 4) {   // round 5: the super-block pair form (same grid, slabs and window workgroups; a pair walks its <= 2 blocks once)
 #define MUSTAFAR_SB(EXTV, MASKV)                                                                            \
     do {                                                                                                    \
         if (G == 2)        MUSTAFAR_LL((decode_onepass_sb_kernel<0, EXTV, 2, MASKV>));                       \
@@ -4598,88 +3882,29 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
         else if (eng == 1) MUSTAFAR_LL((decode_onepass_sb_kernel<1, EXTV, 4, MASKV>));                       \
         else               MUSTAFAR_LL((decode_onepass_sb_kernel<0, EXTV, 4, MASKV>));                       \
     } while (0)
-                    if (extents || G == 1) { if (mask.ptr) MUSTAFAR_SB(true, true); else MUSTAFAR_SB(true, false); }
-                    else                   { if (mask.ptr) MUSTAFAR_SB(false, true); else MUSTAFAR_SB(false, false); }
+            if (extents || G == 1) { if (mask.ptr) MUSTAFAR_SB(true, true); else MUSTAFAR_SB(true, false); }
+            else                   { if (mask.ptr) MUSTAFAR_SB(false, true); else MUSTAFAR_SB(false, false); }
 #undef MUSTAFAR_SB
-                } else if (extents || G == 1) MUSTAFAR_LP(true);
-                else                          MUSTAFAR_LP(false);
+        } else if (extents || G == 1) MUSTAFAR_LP(true);
+        else                          MUSTAFAR_LP(false);
 #undef MUSTAFAR_LP
-            } else {
-                if (fma_engine() == 2) MUSTAFAR_LL((decode_onepass_lean_kernel<2>));
-                else                   MUSTAFAR_LL((decode_onepass_lean_kernel<0>));
-            }
 #undef MUSTAFAR_LL
-            // (the row kernel's own start / stop timestamps go into the record's second event pair: mustafar_profile_end2)
-            if (NS + nchunks <= 64 && g_finish1)
-                hipExtLaunchKernelGGL(onepass_finish1_kernel, dim3(Batch_Size), dim3(128), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                      prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-            else if (NS + nchunks <= 64)
-                hipExtLaunchKernelGGL(onepass_finish_kernel<1>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                      prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-            else if (NS + nchunks <= 128)
-                hipExtLaunchKernelGGL(onepass_finish_kernel<2>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                      prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-            else
-                hipExtLaunchKernelGGL(onepass_finish_kernel<>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                      prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-            if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
-            t_last_choice = eng | (1 << 4) | ((lp ? (small_form ? 4 : g_sb && per_wg <= 4 ? 3 : 2) : 1) << 8);
-            return (int)hipGetLastError();
-        }
-        const bool pair = fma_engine() != 1 || G != 4;                      // two waves per block unless the matrix-pipe engine runs
-        const int round = pair ? kWaves / 2 : kWaves;                     // token blocks a workgroup has in flight
-        // workgroups of the SpMV part: ~onepass_target_wgs(), every workgroup whole rounds of its waves (Split_K only sizes the
-        // workspace here: the slab count below never exceeds it by more than the rounding)
-        (void)Split_K;
-        int tb_per_wg;
-        if (onepass_target_wgs(pair) > 0) {
-            const int want = (onepass_target_wgs(pair) + gy - 1) / gy;
-            tb_per_wg = (ntb + want - 1) / want;
-        } else {
-            // matrix-pipe form: two whole blocks per wave, or one where that fills the last round of waves much better (the chip
-            // holds 6 of these waves per SIMD: c4 with two blocks per wave runs 1.33 rounds, with one 2.65: 67 -> 63 us; c3 and c5
-            // stay at two: 0.65 and 2.67 rounds)
-            static const int slots = [] {
-                int dev = 0, cus = 256;
-                if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                return (cus > 0 ? cus : 256) * 4 * 6;
-            }();
-            auto fill = [&](int tb) {
-                const double rounds = (double)gy * ((ntb + tb - 1) / tb) * kWaves / slots;
-                return rounds / ceil(rounds);
-            };
-            tb_per_wg = fill(4) > fill(8) + 0.1 ? 4 : 8;
-        }
-        tb_per_wg = (tb_per_wg + round - 1) / round * round;
-        const int S1 = (ntb + tb_per_wg - 1) / tb_per_wg;
-        const int nchunks = (window_capacity + kOneWinChunk - 1) / kOneWinChunk;
-        if (S1 + nchunks <= kMaxSlabs) {
-            float* ws_o = static_cast<float*>(workspace);
-            float* ws_ml = ws_o + (int64_t)(S1 + nchunks) * Batch_Size * kD;
-            const int win_rows = (gy * nchunks + S1 - 1) / S1;
-            const OneArgs a{qh, sc, ws_o, ws_ml, kwin, vwin, knew, vnew, window_len_extra, mask, T, groups, Batch_Size, tb_per_wg, ld_scores,
-                            window_len, window_capacity, nchunks, win_rows, inv_sqrt_d0};
-            const dim3 grid(S1, gy + win_rows);
-            hipEvent_t e0 = prof ? g_prof.ev[4 * g_prof.n] : nullptr, e1 = prof ? g_prof.ev[4 * g_prof.n + 1] : nullptr;
-            auto kz = static_cast<const unsigned char*>(kc.nz), vz = static_cast<const unsigned char*>(vc.nz);
-#define MUSTAFAR_L1(GG, MFF)                                                                                                     \
-    hipExtLaunchKernelGGL((decode_onepass_kernel<GG, MFF, !MFF>), grid, dim3(kThreads), 0, st, e0, e1, 0, kc.bmp, kz, kc.idx, kc.nz_offset,  \
-                          vc.bmp, vz, vc.idx, vc.nz_offset, a, kc.bmp_head_stride, kc.idx_head_stride, (uint32_t)kc.nz_head_stride,    \
-                          vc.bmp_head_stride, vc.idx_head_stride, (uint32_t)vc.nz_head_stride)
-            switch (G) {
-                case 4:
-                    if (fma_engine() == 1) MUSTAFAR_L1(4, true);
-                    else              MUSTAFAR_L1(4, false);
-                    break;
-                case 2: MUSTAFAR_L1(2, false); break;
-                default: MUSTAFAR_L1(1, false); break;
-            }
-#undef MUSTAFAR_L1
-            if (prof) { g_prof.onepass++; g_prof.n++; }
-            onepass_finish_kernel<><<<Batch_Size, 256, 0, st>>>(ws_o, ws_ml, S1 + nchunks, static_cast<h16*>(out), Batch_Size);
-            t_last_choice = (fma_engine() == 1 && G == 4 ? 1 : 0) | (1 << 4);
-            return (int)hipGetLastError();
-        }
+        // (the row kernel's own start / stop timestamps go into the record's second event pair: mustafar_profile_end2)
+        if (NS + nchunks <= 64 && finish1())
+            hipExtLaunchKernelGGL(onepass_finish1_kernel, dim3(Batch_Size), dim3(128), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
+                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
+        else if (NS + nchunks <= 64)
+            hipExtLaunchKernelGGL(onepass_finish_kernel<1>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
+                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
+        else if (NS + nchunks <= 128)
+            hipExtLaunchKernelGGL(onepass_finish_kernel<2>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
+                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
+        else
+            hipExtLaunchKernelGGL(onepass_finish_kernel<>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
+                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
+        if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
+        t_last_choice = eng | (1 << 4) | ((small_form ? 4 : sb_form() && per_wg <= 4 ? 3 : 2) << 8);
+        return (int)hipGetLastError();
     }
     // ---- two-launch form.  With a compressed part the dense-window work rides in the two SpMV launches (window workgroups);
     // without one (T == 0) the two row kernels do it themselves.
@@ -4817,11 +4042,10 @@ int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint3
     const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
     if (f_eng > 3u || f_str > 2u || (flags & ~0x37u)) return 0;
     if (f_str == 1u || (f_str == 0u && onepass_mode() == 0)) return 0;   // two launches asked for (by the call or by the process default)
-    (void)onepass_target_wgs(true);   // (reads MUSTAFAR_ONEPASS_WGS: the shape rule below depends on it)
     // rows so long that four blocks per workgroup leave more slabs than the row kernel folds (T > ~127 k tokens; ld_scores >= T
     // stands in for T): decode_attention then gives a workgroup more blocks, which may straddle extents -> not served
     if (((ld_scores / 64 + 3) / 4) + kMaxWindow / kOneWinChunk > kMaxSlabs) return 0;
-    return num_key_value_groups >= 1 && onepass_lean() == 2 && (ld_scores & 31) == 0 && g_onepass_wgs <= 0 &&
+    return num_key_value_groups >= 1 && (ld_scores & 31) == 0 && onepass_wgs() <= 0 &&   // (MUSTAFAR_ONEPASS_WGS changes the shape rule)
            (onepass_lean_tbw() == 0 || onepass_lean_tbw() == 1 || onepass_lean_tbw() == 2);
 }
 
@@ -4915,13 +4139,14 @@ int mustafar_get_onepass(void) { return onepass_mode(); }
 
 int mustafar_last_decode_choice(void) { return t_last_choice; }
 
-// Tuning knobs of the experiment scripts (tools/): 0 = lean one-pass form on / off, 1 = blocks per wave of the lean form
-// (0 = automatic), 2 = workgroup target of the pair form (0 = automatic).  Not part of the operator interface.
+// Tuning knobs of the experiment scripts (tools/) and of the tests that pin a form: 0 = one-pass generation (only 2, the pair
+// grain, exists: a no-op; 0 and 1 selected kernels that were removed), 1 = block pairs per workgroup of the one-pass launch
+// (0 = automatic), 2 = its workgroup target (0 = automatic); the others at their variables.  Not part of the operator interface.
 int mustafar_tune(int knob, int value)
 {
     if (value < 0) return MUSTAFAR_EINVAL;
     switch (knob) {
-        case 0: g_lean = value > 2 ? 2 : value; return 0;
+        case 0: return value >= 2 ? 0 : MUSTAFAR_EINVAL;
         case 1: g_lean_tbw = value; return 0;
         case 2: g_onepass_wgs = value; return 0;
         case 3: g_lean_win_last = value ? 1 : 0; return 0;
@@ -4931,7 +4156,6 @@ int mustafar_tune(int knob, int value)
         case 8: g_sb = value ? 1 : 0; return 0;
         case 9: g_late_prio = value ? 1 : 0; return 0;
         case 10: g_finish1 = value ? 1 : 0; return 0;
-        case 12: g_spec_k_bytes = value < 0 ? 0 : value; return 0;
         case 13: g_value_lean8 = value ? 1 : 0; return 0;   // (round 6: 1 = the value entry point's 8-row calls on the lean form with pad workgroups behind the row-0 workgroups, 0 = round 1's kernel)
         case 11: g_small = value < 0 ? 0 : value > 2 ? 2 : value; return 0;   // (round 6: 0 = never the small-launch kernel, 1 = below one wave per SIMD, 2 = for every launch of two blocks per workgroup)
         default: return MUSTAFAR_EINVAL;

@@ -141,7 +141,7 @@ def test_engines_agree_on_ordinary_data_and_small_weights_survive_dot2(hq, hkv, 
 
 @pytest.mark.parametrize("hq,hkv,L0,bsz", [(8, 2, 1056, 2), (32, 32, 3872, 1)])
 def test_replays_with_alternating_queries_on_one_scratch(hq, hkv, L0, bsz):
-    """The e round trip (spmv.hip: INVARIANT at decode_onepass_lean_kernel / the pair form of round 2 for G < 4): a captured
+    """The e round trip (spmv.hip: INVARIANT at decode_onepass_leanpair_kernel, every group count): a captured
     one-pass step replayed 34 times, the query alternating between two very different ones; the score scratch, the slab
     workspace and every address are the same in all replays.  (8, 2): GQA-4, the lean pair kernel; (32, 32): c2's geometry, G = 1.)"""
     from mustafar_amd import _lib

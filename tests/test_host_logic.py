@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -134,6 +136,24 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert L.mustafar_prune_magnitude(None, one, one, 4, 64, 10) == 1
     assert L.mustafar_prune_magnitude(None, one, one, 4, 128, 0) == 1
     assert L.mustafar_compress_bitmap_key(None, one, 2, 100, 128, one, one, one) == 1
+
+
+def test_tune_knobs_of_removed_kernels_are_rejected_and_the_rest_still_set():
+    """mustafar_tune(0, .) chose among three one-pass generations; only 2 (the pair grain) exists: restoring the default stays a no-op,
+    the two removed kernels and the removed speculative-request knob (12) are MUSTAFAR_EINVAL.  Every knob the GPU tests use still
+    takes a value.  In a child process: a knob that was set no longer follows its environment variable, and the suite's
+    process may be running under one.  No launch."""
+    code = ("from mustafar_amd import _lib\n"
+            "L = _lib.load()\n"
+            "assert L.mustafar_tune(0, 2) == 0\n"
+            "assert L.mustafar_tune(0, 0) == 1\n"
+            "assert L.mustafar_tune(0, 1) == 1\n"
+            "assert L.mustafar_tune(12, 64) == 1\n"
+            "for knob, value in ((1, 0), (6, 1), (7, 2), (8, 1), (10, 1), (11, 1), (13, 1)):\n"
+            "    assert L.mustafar_tune(knob, value) == 0, knob\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
 
 
 def test_wrapper_checks_match_reference_messages():

@@ -2,7 +2,7 @@
 """Wave timeline of ONE one-pass decode launch (bench.py's c3 layer by default): when every wave starts and ends, how long its
 key phase, softmax step and value phase take, how many waves share a SIMD over the span.
 
-    python tools/wave_trace_onepass.py [--cfg c3] [--set valu valu:lean=0 dot2 mfma]
+    python tools/wave_trace_onepass.py [--cfg c3] [--set valu valu:tbw=1 dot2 mfma]
 """
 import argparse
 import ctypes
@@ -55,7 +55,6 @@ def main():
         kv = dict(p.split("=") for p in parts[1:])
         _lib.check(lib.mustafar_set_fma_engine(ENG[parts[0]]), "engine")
         _lib.check(lib.mustafar_set_onepass(int(kv.get("onepass", 1))), "onepass")
-        _lib.check(lib.mustafar_tune(0, int(kv.get("lean", 2))), "lean")
         _lib.check(lib.mustafar_tune(1, int(kv.get("tbw", 0))), "tbw")
         _lib.check(lib.mustafar_tune(2, int(kv.get("wgs", 0))), "wgs")
         _lib.check(lib.mustafar_tune(3, int(kv.get("winlast", 1))), "winlast")
@@ -77,7 +76,7 @@ def main():
         kern = (rec[:, 9] >> np.uint64(56)).astype(int)
         print(f"== {a.cfg} {st}: call {e0.elapsed_time(e1) * 1e3:.1f} us, records {len(rec)} (kernels {sorted(set(kern.tolist()))})")
         base = rec[:, 0].min()
-        for k, name in ((7, "lean pair"), (3, "lean"), (4, "pair form"), (6, "matrix-pipe form"), (5, "window workgroups")):
+        for k, name in ((7, "lean pair"), (5, "window workgroups")):
             r = rec[kern == k]
             if not len(r):
                 continue
