@@ -22,8 +22,11 @@
  *              mustafar_compress_pack_{key,value}) and the fused decode through mustafar_decode_attention_hd.  At D = 64 the
  *              K tile id is (token/64)*64 + d and the V tile id (token/64)*64 + token%64 (one tile per token): bmp [B', t],
  *              idx [B', t + 1].  Row pointers (x, out, windows, k_new) must be 16-byte aligned (rows are moved as 16-byte pieces).
+ *              Growth by extents (ABI 108): mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd and
+ *              mustafar_decode_attention_extents_hd.
  *              Everything else returns MUSTAFAR_EINVAL for D = 64: the two reference SpMV entry points (D = 128 in the reference),
- *              the one-pass conversion, mustafar_cache_append_*, the trigger batch and the cache-view / extent decode forms.
+ *              the one-pass conversion, mustafar_cache_append_*, mustafar_trigger_compress_batch and the D = 128 cache-view /
+ *              extent decode forms.
  */
 #ifndef MUSTAFAR_HIP_H
 #define MUSTAFAR_HIP_H
@@ -354,6 +357,46 @@ int mustafar_trigger_compress_batch(void* stream, int n, const mustafar_trigger_
 int mustafar_trigger_finish_batch(void* stream, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop);
 
 /*
+ * head_dim 64 grows by extents too (ABI 108).  Format at D = 64: one tile per token and side, so a 256-token extent has 256 bitmaps
+ * and 257 offsets per head (bmp_head_stride / idx_head_stride 0 = exactly that).
+ *
+ * mustafar_trigger_compress_batch_hd: the arguments of mustafar_trigger_compress_batch; D must be 64 and t 256.  n launches back to
+ *   back, one per item, no host work in between (n = 1: the layer-by-layer trigger).  A launch takes the RAW rows [0, 256) of both
+ *   windows (head h `head_stride` elements behind head h - 1, rows of 64 contiguous halfs, 16-byte aligned, head_stride % 8 == 0) to a
+ *   finished extent: prune (kth = max(1, int(sparsity * 64)); 0 = already pruned), bitmaps, offsets, packed stream.  One workgroup owns
+ *   one head's extent and knows its whole stream length before it writes a byte: no workgroup waits for another, so overflow_flag bit 1
+ *   never occurs and `scratch` is unused (NULL allowed).  Written through k_dst / v_dst (nz_head_stride != 0, nz 16-byte aligned):
+ *   bmp[h][0..256), idx[h][0..256], nz_offset[h] = h * nz_head_stride (where nz_offset is not NULL), the stream at the head's region and
+ *   *_head_total[h] (halfs).  *_region_halfs: the room of a region, REQUIRED here (0 < region_halfs <= 8 * nz_head_stride).  A head that
+ *   needs more sets bit 0 of overflow_flag, still writes its bitmaps, offsets and head_total (the length it needs) and writes NO stream
+ *   bytes; the other heads are complete.  Repeat at the measured size: the call is idempotent.
+ * mustafar_trigger_finish_batch_hd: mustafar_trigger_finish_batch with the row width as an argument (the D = 128 call moves rows of 128
+ *   halfs whatever head_stride says, and so does mustafar_window_drop_front).  D = 128 forwards; D = 64 lists every item's views in its
+ *   table slots (NULL: not listed) and slides rows [drop, len) of 64 halfs to the front, in stream order; the buffers keep their addresses.
+ * mustafar_decode_attention_extents_hd: mustafar_decode_attention_extents for a given head_dim.  128 forwards.  64: the D = 64 kernel's
+ *   EXT instantiation -- same run shape, slabs and sum order as mustafar_decode_attention_hd at the same T, so the same bits.  Block
+ *   tb < T_base / 64 comes from the base views (any strides; nz_head_stride 0: nz_offset is loaded), block T_base / 64 + 4 i + j is block
+ *   j of table entry i, resolved per block with scalar loads (a workgroup's run may cross base -> extent and extent -> extent).
+ *   Validation as mustafar_decode_attention_hd, and T_base > 0, T_base % 256 == 0, (T - T_base) % 256 == 0, (T - T_base) / 256 <= 512,
+ *   tables not NULL when T > T_base.  T == T_base without T_device: the plain launch over the base.  With T_device the grid, slabs,
+ *   blocks per workgroup and mask columns are sized for the capacity T; blocks at or beyond *T_device / 64 are skipped (a workgroup with
+ *   no block in use leaves slabs of weight zero).  Mask columns, the convention of the D = 128 extents launch: compressed token t reads
+ *   column t, window row w reads column *T_device + w -- the tokens IN USE, not the capacity -- so a mask row is the model's own
+ *   [0, kv_len) row whatever the capacity.  mustafar_last_decode_choice() reports form 6 when the EXT instantiation ran (5: the plain one).
+ */
+int mustafar_trigger_compress_batch_hd(void* stream, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int D,
+                                       int kth_k, int kth_v, int64_t k_region_halfs, int64_t v_region_halfs, void* scratch);
+int mustafar_trigger_finish_batch_hd(void* stream, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop,
+                                     int D);
+int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                         const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                         const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                         int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                                         int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                         const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                         int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim);
+
+/*
  * FMA engine, process default (a fused call may carry its own in `flags`):
  *   2 = v_dot2_f32_f16 on pairs of tiles (default; GQA-4 one-pass decode launches).  One instruction does two tiles of one head, so
  *       the FMA phase costs 2 + 1.5 cheap instead of 4 vector instructions per tile.  For normal fp16 inputs the instruction is a
@@ -380,7 +423,7 @@ int mustafar_get_fma_engine(void);
 int mustafar_set_onepass(int mode);
 int mustafar_get_onepass(void);
 /* What the last fused call on the calling thread launched: FMA engine that ran (0 v_fma_mix_f32, 1 matrix pipe, 2 v_dot2_f32_f16)
- * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block: both removed, the codes no longer occur; 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that, 5 the head_dim 64 kernel of mustafar_decode_attention_hd);
+ * | structure << 4 (0 two launches, 1 one-pass) | one-pass form << 8 (0 round-2 forms, 1 lean whole-block: both removed, the codes no longer occur; 2 lean pair grain, 3 super-block pair form: round 5, the default from 768 workgroups on, 4 the small-launch form: round 6, the default below that, 5 the head_dim 64 kernel of mustafar_decode_attention_hd, 6 its extents instantiation: mustafar_decode_attention_extents_hd);
  * -1 before the first call.  For tests and tools: a call's `flags` and the process defaults can be checked against what ran. */
 int mustafar_last_decode_choice(void);
 /* Tuning knobs for the measurement scripts under tools/ (launch shapes of the one-pass forms); not an operator interface.

@@ -1,0 +1,218 @@
+"""The head_dim-64 compressed cache that grows by extents (MustafarConfig(hd64_extents=True)).
+
+At D = 64 the cache is the reference's tuple `[bitmaps, idxs, nzs, nz_offset]`, and the reference's 256-token trigger re-copies all of
+it (`hook.append_compressed`: a `torch.cat` per array and head), so every array moves and a captured decode graph dies with every
+trigger.  `ExtentCache64` keeps one side (K or V) of one layer the way `CompressedArena` keeps it at D = 128 once extents are on:
+
+  * the BASE is the reference-layout arrays of the prefill, exactly as the two-pass conversion makes them.  Nothing is ever appended
+    to it in place, so it needs no spare room and no strides;
+  * a trigger compresses its 256 window rows into a small cache of their own, an EXTENT (mustafar_trigger_compress_batch_hd: one launch
+    per layer from the raw rows), and lists the extent's view in a DEVICE table of `MAX_EXTENTS` mustafar_cache_view entries that
+    mustafar_decode_attention_extents_hd reads.  The table is created with the cache -- before any graph can name it (a table created
+    inside a capture would live in the graph's pool and be zero-filled again by every replay) -- and an entry is written once;
+  * the extents of ONE trigger of ALL layers are carved from one pooled allocation (`ExtentPool64`) together with the layers' status
+    words `[flag, K lengths, V lengths]`, which one copy brings to the host.  Regions are housed tight -- the base's measured halfs per
+    token + 4 %, as cache.py does at D = 128; a worst-case region would be as large as the dense rows -- and a layer whose flag shows
+    bit 0 (a head outgrew its region: rows full of ties) is redone on its own at the measured size before any window slides.
+
+`to_reference()` concatenates base and extents the way the model appends (`hook.append_compressed`): the same tensors, bit for bit,
+that the tuple path holds after the same triggers.  `consolidate()` (a full table) goes through that reference layout -- torch.cat on
+the device, one copy of the cache, every address new, so a captured graph must be taken again; a device-side consolidation as
+cache.py has at D = 128 is left for later (512 extents are 128 k generated tokens).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Optional
+
+import torch
+
+from . import _lib
+
+D = 64
+EXT_TOKENS = 256
+VIEW_BYTES = ctypes.sizeof(_lib.CacheView)
+
+
+def _round_up(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def _head_lengths(idx: torch.Tensor, heads: int) -> torch.Tensor:
+    """Every head's stream length in halfs, on the host (the last offset entry of its row, half2 units)."""
+    return (idx.view(heads, -1)[:, -1].to(torch.int64) * 2).cpu()
+
+
+class Extent64:
+    """One 256-token extent of one side: views into a pool's storage (which they keep alive) + the heads' stream lengths."""
+
+    def __init__(self, storage: torch.Tensor, heads: int, region_halfs: int):
+        self.storage, self.heads, self.region = storage, heads, region_halfs
+        off = ExtentPool64.layout(heads, region_halfs)[0]
+        self.bmp = storage[off["bmp"]:off["bmp"] + heads * 256 * 8].view(torch.int64).view(heads, 256)
+        self.idx = storage[off["idx"]:off["idx"] + heads * 257 * 4].view(torch.int32).view(heads, 257)
+        self.nz_offset = storage[off["nz_offset"]:off["nz_offset"] + heads * 4].view(torch.int32)
+        self.nz = storage[off["nz"]:off["nz"] + heads * region_halfs * 2].view(torch.float16).view(heads, region_halfs)
+        self.view = _lib.CacheView(self.bmp.data_ptr(), self.nz.data_ptr(), self.idx.data_ptr(), self.nz_offset.data_ptr(), 256, 257,
+                                   region_halfs // 8)
+        self.used: Optional[torch.Tensor] = None   # int64 [heads] on the host, set when the trigger's status has been read
+
+    def reference(self) -> list:
+        """[bitmaps, idxs, per-head streams, None]: what `_compress` returns for these 256 tokens (append_compressed reads the first three)."""
+        from .hook import FlatStreams
+        return [self.bmp.reshape(-1), self.idx.reshape(-1), FlatStreams([self.nz[h, :int(self.used[h])] for h in range(self.heads)]), None]
+
+
+class ExtentPool64:
+    """ONE allocation for the 2 x n extents of one trigger of n layers (K, V per layer; one region size) and the layers' status words
+    (int64 [n][1 + 2 heads]: flag in the low 4 bytes, K lengths, V lengths).  Only the status words are initialised (zeroed): the
+    compression launch writes every other word it or the decode launch reads."""
+
+    def __init__(self, n_layers: int, heads: int, device, region_halfs: int):
+        assert region_halfs > 0 and region_halfs % 8 == 0
+        self.n, self.heads, self.device, self.region = n_layers, heads, device, region_halfs
+        _, self.ext_bytes = self.layout(heads, region_halfs)
+        self.status_words = 1 + 2 * heads
+        ne = 2 * n_layers
+        self.buf = torch.empty(ne * self.ext_bytes + n_layers * self.status_words * 8, dtype=torch.uint8, device=device)
+        self.status = self.buf[ne * self.ext_bytes:].view(torch.int64).view(n_layers, self.status_words)
+        self.status.zero_()
+        self._host = torch.empty((n_layers, self.status_words), dtype=torch.int64).pin_memory()
+
+    @staticmethod
+    def layout(heads: int, region_halfs: int):
+        off, pos = {}, 0
+        for name, size in (("bmp", heads * 256 * 8), ("idx", heads * 257 * 4), ("nz_offset", heads * 4), ("nz", heads * region_halfs * 2)):
+            off[name] = pos
+            pos = _round_up(pos + size, 256)
+        return off, pos
+
+    def extent(self, j: int) -> Extent64:   # j = 2 * layer + side
+        return Extent64(self.buf[j * self.ext_bytes:(j + 1) * self.ext_bytes], self.heads, self.region)
+
+    def totals_ptr(self, j: int) -> int:
+        return self.status.data_ptr() + ((j // 2) * self.status_words + 1 + (j % 2) * self.heads) * 8
+
+    def flag_ptr(self, layer: int) -> int:
+        return self.status.data_ptr() + layer * self.status_words * 8
+
+    def read_status(self) -> torch.Tensor:
+        """ONE copy into pinned memory + ONE wait."""
+        self._host.copy_(self.status, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._host
+
+
+class ExtentCache64:
+    MAX_EXTENTS = 512   # entries of the device table (mustafar_decode_attention_extents_hd takes at most 512)
+
+    def __init__(self, base: list, which: str, heads: int, tokens: int):
+        """base: the reference-layout `[bitmaps, idxs, FlatStreams, nz_offset]` of `tokens` tokens (a multiple of 256)."""
+        assert which in ("key", "value") and tokens > 0 and tokens % 256 == 0
+        self.base, self.which, self.heads, self.tokens = base, which, heads, tokens
+        bmp, idx, nzs, off = base
+        self.device = bmp.device
+        flat = nzs.flat
+        self.base_used = _head_lengths(idx, heads)
+        self._flat = flat   # (kept: the view below holds its address)
+        self.base_view = _lib.CacheView(bmp.data_ptr(), flat.data_ptr() if flat is not None and flat.numel() else None, idx.data_ptr(),
+                                        off.data_ptr(), 0, 0, 0)
+        self.table = torch.zeros(self.MAX_EXTENTS * VIEW_BYTES, dtype=torch.uint8, device=self.device)
+        self.extents: List[Extent64] = []
+
+    @property
+    def total_tokens(self) -> int:
+        return self.tokens + EXT_TOKENS * len(self.extents)
+
+    def view_ptr(self):
+        return ctypes.byref(self.base_view)
+
+    def slot_ptr(self, i: int) -> int:
+        return self.table.data_ptr() + i * VIEW_BYTES
+
+    def signature(self) -> tuple:
+        """Addresses a captured decode graph holds for this cache (extents are found through the table at run time)."""
+        return (self.base[0].data_ptr(), self.base[1].data_ptr(), self.base_view.nz, self.tokens, self.table.data_ptr())
+
+    def expected_region(self) -> int:
+        """Halfs a 256-token extent is expected to need in its fullest head: the base's measured halfs per token + 4 % (cache.py:
+        `_expected_append`), a little room for padding, a multiple of 8."""
+        per_token = float(self.base_used.max()) / self.tokens
+        return _round_up(int(EXT_TOKENS * per_token * 1.04) + 256, 8)
+
+    # ---- the trigger of all layers -----------------------------------------------------------------------------------------------
+    @staticmethod
+    def append_extents(pairs, rows, kth_k: int, kth_v: int, window_len: int) -> None:
+        """pairs: [(k_cache, v_cache), ...] one per layer; rows: [(k_buf, v_buf), ...] the window buffers [B, Hkv, cap, 64] with
+        `window_len` valid rows.  Rows [0, 256) of every buffer become an extent of its cache; both windows slide by 256 rows in place.
+        One library call issues every layer's compression, one copy brings every flag and length, a layer that overflowed is redone on
+        its own at the measured size, and only then one call lists the extents in the tables and slides the windows."""
+        n = len(pairs)
+        if n == 0:
+            return
+        k0 = pairs[0][0]
+        H, dev = k0.heads, k0.device
+        for (kc, vc), (kr, vr) in zip(pairs, rows):
+            if len(kc.extents) >= kc.MAX_EXTENTS or len(kc.extents) != len(vc.extents) or kc.tokens != vc.tokens or kc.heads != H or vc.heads != H:
+                raise RuntimeError("ExtentCache64.append_extents: extent table full (consolidate() first) or K / V out of step")
+            if kr.shape != vr.shape or kr.dtype != torch.float16 or kr.dim() != 4 or kr.shape[0] * kr.shape[1] != H or kr.shape[3] != D or \
+                    kr.shape[2] < window_len or window_len < 256 or not kr.is_contiguous() or not vr.is_contiguous() or kr.shape != rows[0][0].shape:
+                raise RuntimeError("ExtentCache64.append_extents expects contiguous fp16 [B, Hkv, rows >= window_len >= 256, 64] buffers of one shape")
+        L = _lib.load()
+        head_stride = rows[0][0].shape[2] * D
+        region = max(max(kc.expected_region(), vc.expected_region()) for kc, vc in pairs)
+        pool = ExtentPool64(n, H, dev, region)
+
+        def item(it, i, p, j):
+            (kc, vc), (kr, vr) = pairs[i], rows[i]
+            ek, ev = p.extent(2 * j), p.extent(2 * j + 1)
+            it.k_window, it.v_window = kr.data_ptr(), vr.data_ptr()
+            it.k_dst, it.v_dst = ek.view, ev.view
+            it.k_table_slot, it.v_table_slot = kc.slot_ptr(len(kc.extents)), vc.slot_ptr(len(vc.extents))
+            it.k_head_total, it.v_head_total, it.overflow_flag = p.totals_ptr(2 * j), p.totals_ptr(2 * j + 1), p.flag_ptr(j)
+            return ek, ev
+
+        items = (_lib.TriggerItem * n)()
+        made = [item(items[i], i, pool, i) for i in range(n)]
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(L.mustafar_trigger_compress_batch_hd(st, n, items, head_stride, H, 256, D, kth_k, kth_v, region, region, None),
+                       "mustafar_trigger_compress_batch_hd")
+            host = pool.read_status().clone()
+            for i in range(n):
+                if not int(host[i, 0]) & 1:
+                    continue
+                # a head outgrew its region: this layer alone, at the length the launch measured (the raw rows are still in place)
+                need = _round_up(int(host[i, 1:].max()), 8)
+                own = ExtentPool64(1, H, dev, need)
+                one = (_lib.TriggerItem * 1)()
+                made[i] = item(one[0], i, own, 0)
+                _lib.check(L.mustafar_trigger_compress_batch_hd(st, 1, one, head_stride, H, 256, D, kth_k, kth_v, need, need, None),
+                           "mustafar_trigger_compress_batch_hd")
+                again = own.read_status()
+                if int(again[0, 0]) & 0xffffffff:
+                    raise RuntimeError("ExtentCache64.append_extents: the repeat at the measured size overflowed: this is a bug")
+                host[i] = again[0]
+                items[i] = one[0]
+            _lib.check(L.mustafar_trigger_finish_batch_hd(st, n, items, head_stride, H, window_len, 256, D), "mustafar_trigger_finish_batch_hd")
+        for i, ((kc, vc), (ek, ev)) in enumerate(zip(pairs, made)):
+            ek.used, ev.used = host[i, 1:1 + H].clone(), host[i, 1 + H:1 + 2 * H].clone()
+            kc.extents.append(ek)
+            vc.extents.append(ev)
+
+    # ---- back to the reference layout ----------------------------------------------------------------------------------------------
+    def to_reference(self) -> list:
+        """`[bitmaps, idxs, FlatStreams, nz_offset]` of base + extents, built the way the model appends (hook.append_compressed)."""
+        from .hook import append_compressed
+        ref, tokens = self.base, self.tokens
+        for e in self.extents:
+            ref = append_compressed(ref, e.reference(), self.heads, tokens, EXT_TOKENS, D)
+            tokens += EXT_TOKENS
+        return ref
+
+    def consolidate(self) -> "ExtentCache64":
+        """One base holding everything, through the reference layout (module docstring): a copy of the cache, new addresses, a new
+        and empty table."""
+        if not self.extents:
+            return self
+        return type(self)(self.to_reference(), self.which, self.heads, self.total_tokens)

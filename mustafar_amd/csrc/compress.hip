@@ -1149,6 +1149,24 @@ int mustafar_trigger_finish_batch(void* stream, int n, const mustafar_trigger_it
     return (int)hipGetLastError();
 }
 
+// head_dim 64 (ABI 108): the trigger as ONE launch per layer (headdim64.hip: a workgroup owns a head's extent, nothing waits) and its
+// finish.  The D = 128 finish multiplies rows by 128 halfs, so the D = 64 one is a call of its own with the row width as an argument.
+int mustafar_trigger_compress_batch_hd(void* stream, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int D,
+                                       int kth_k, int kth_v, int64_t k_region_halfs, int64_t v_region_halfs, void* scratch)
+{
+    (void)scratch;   // (no workgroup waits for another: nothing to exchange)
+    if (D != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    return mustafar_hd64::trigger_compress_batch(static_cast<hipStream_t>(stream), n, items, head_stride, Bp, t, kth_k, kth_v, k_region_halfs,
+                                                 v_region_halfs);
+}
+
+int mustafar_trigger_finish_batch_hd(void* stream, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop, int D)
+{
+    if (D == kD) return mustafar_trigger_finish_batch(stream, n, items, head_stride, Bp, len, drop);
+    if (D != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    return mustafar_hd64::trigger_finish_batch(static_cast<hipStream_t>(stream), n, items, head_stride, Bp, len, drop);
+}
+
 int mustafar_cache_rehouse(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens,
                            int64_t stream_halfs)
 {

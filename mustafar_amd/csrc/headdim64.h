@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/mustafar_hip.h"
+
 namespace mustafar_hd64 {
 
 constexpr int kD = 64;
@@ -25,6 +27,18 @@ int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32
            void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
            const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev);
 int64_t workspace_bytes(int T, int Batch_Size, int groups);
+// the same over base views + device tables of 256-token extents (mustafar_decode_attention_extents_hd); *ran_extents: the EXT
+// instantiation was launched (false: T == T_base, the plain one over the base)
+int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                   const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, const void* q, void* k_window, void* v_window,
+                   const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                   void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+                   const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, const int32_t* T_device, hipEvent_t* ev,
+                   bool* ran_extents);
+// the 256-token trigger: n launches, raw window rows -> one extent per layer and side; the finish lists the views and slides the windows
+int trigger_compress_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
+                           int64_t k_region_halfs, int64_t v_region_halfs);
+int trigger_finish_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop);
 
 }  // namespace mustafar_hd64
 

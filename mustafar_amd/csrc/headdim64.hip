@@ -36,6 +36,7 @@ constexpr int kScanThreads = 256;
 constexpr int kWinChunk = 64;       // window rows per window workgroup
 constexpr int kMaxWindow = 1024;    // the window capacity the slab count is sized for (as at D = 128)
 constexpr int kMaxSlabs = 1024;     // slabs of a row (compressed workgroups + window chunks)
+constexpr int kMaxExtents = 512;    // entries of the device tables the EXT decode launch reads
 constexpr int kWgTarget = 4096;     // workgroups (= waves) a launch aims for: four per SIMD on 256 CUs
 
 __device__ __forceinline__ bool nonzero_h(uint32_t v) { return (v & 0x7fffu) != 0; }   // -0.0 is zero, NaN is not
@@ -62,17 +63,10 @@ __device__ __forceinline__ float wave_sum(float v)
 // Lane = row of 64 halfs (32 words).  thr = k-th smallest magnitude (torch.kthvalue(|x|, k), model :103), found bit by bit from the MSB:
 // thr |= b iff fewer than k magnitudes are < (thr | b).  SWAR compare: with the guard bit 0x8000 set in each half, (m | H) - (c | c << 16)
 // keeps the guard bit of a half iff that magnitude >= c (no borrow crosses the halves).  out = |x| >= thr ? x : sign-preserving zero.
-__global__ __launch_bounds__(64) void prune64_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int64_t n_rows, int kth)
+// row_threshold / prune_row: the search and the rule on a row held in registers (prune64_kernel and the one-launch trigger).
+__device__ __forceinline__ uint32_t row_threshold(const uint32_t (&raw)[32], int kth)
 {
-    const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (row >= n_rows) return;
     const uint32_t H = 0x80008000u, ONES = 0x00010001u;
-    uint32_t raw[32];
-#pragma unroll
-    for (int p = 0; p < 8; p++) {
-        const uint4 v = x[row * 8 + p];
-        raw[4 * p] = v.x; raw[4 * p + 1] = v.y; raw[4 * p + 2] = v.z; raw[4 * p + 3] = v.w;
-    }
     uint32_t thr = 0;
 #pragma unroll 1
     for (int bit = 14; bit >= 0; bit--) {
@@ -84,12 +78,34 @@ __global__ __launch_bounds__(64) void prune64_kernel(const uint4* __restrict__ x
         const int below = 64 - (int)((ge & 0xffffu) + (ge >> 16));
         if (below < kth) thr = c;
     }
+    return thr;
+}
+__device__ __forceinline__ void prune_row(uint32_t (&raw)[32], uint32_t thr)
+{
+    const uint32_t H = 0x80008000u, ONES = 0x00010001u;
     const uint32_t tt = thr | (thr << 16);
 #pragma unroll
     for (int j = 0; j < 32; j++) {
         const uint32_t keep = (((raw[j] | H) - tt) >> 15) & ONES;   // bit 0 / bit 16: that half is kept
         raw[j] &= ((keep << 16) - keep) | H;                         // kept halves whole, pruned ones keep their sign bit only
     }
+}
+__device__ __forceinline__ void load_row(const uint4* __restrict__ src, uint32_t (&raw)[32])
+{
+#pragma unroll
+    for (int p = 0; p < 8; p++) {
+        const uint4 v = src[p];
+        raw[4 * p] = v.x; raw[4 * p + 1] = v.y; raw[4 * p + 2] = v.z; raw[4 * p + 3] = v.w;
+    }
+}
+
+__global__ __launch_bounds__(64) void prune64_kernel(const uint4* __restrict__ x, uint4* __restrict__ out, int64_t n_rows, int kth)
+{
+    const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (row >= n_rows) return;
+    uint32_t raw[32];
+    load_row(x + row * 8, raw);
+    prune_row(raw, row_threshold(raw, kth));
 #pragma unroll
     for (int p = 0; p < 8; p++) out[row * 8 + p] = make_uint4(raw[4 * p], raw[4 * p + 1], raw[4 * p + 2], raw[4 * p + 3]);
 }
@@ -259,6 +275,130 @@ __global__ __launch_bounds__(64) void pack64_kernel(const uint16_t* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the 256-token trigger in one launch
+// RAW window rows -> a finished 256-token extent (mustafar_trigger_compress_batch_hd).  grid (kv head, side: 0 = K, 1 = V), 256 threads:
+// wave w = 64-token block w, lane = row; the row's 32 words stay in registers from the load to the packed stream.  Threshold and rule as
+// prune64_kernel (kth = 0: the rows are pruned already); K tile d of a block = the ballot of channel d over the lanes, V tile = the
+// lane's own row; tile lengths ceil8(nnz); a wave prefix gives the offsets inside the block and the four block totals cross through
+// LDS, so the workgroup knows its head's stream length before it writes a byte: no workgroup waits for another one.  A head that needs
+// more than region_halfs sets bit 0 of *flag and writes bitmaps, offsets and head_total (the length it needs) but no stream bytes.
+struct ExtSide {
+    const uint16_t* x;        // window rows: head h at x + h * head_stride, row r 64 halfs behind row r - 1
+    uint64_t* bmp;            // [B'][bmp_stride]
+    uint32_t* idx;            // [B'][idx_stride]
+    uint16_t* nz;             // head h's region at nz + 8 * h * nz_stride halfs
+    uint32_t* nz_offset;      // [B'] (or nullptr): h * nz_stride is stored there
+    int64_t* head_total;      // [B'] halfs
+    int64_t bmp_stride, idx_stride, region_halfs;
+    uint32_t nz_stride;       // uint4 units
+    int kth;
+};
+
+__global__ __launch_bounds__(256) void hd64_extent_compress_kernel(ExtSide ks, ExtSide vs, int64_t head_stride, int32_t* __restrict__ flag)
+{
+    __shared__ int32_t s_tot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = blockIdx.x;
+    const bool key = blockIdx.y == 0;
+    const ExtSide& s = key ? ks : vs;
+    uint32_t w[32];
+    load_row(reinterpret_cast<const uint4*>(s.x + (int64_t)h * head_stride + (int64_t)(wave * 64 + lane) * kD), w);
+    if (s.kth > 0) prune_row(w, row_threshold(w, s.kth));
+    uint64_t mine = 0;
+    if (key) {
+#pragma unroll
+        for (int d = 0; d < 64; d++) {
+            const uint64_t b = __ballot(nonzero_h(w[d >> 1] >> (16 * (d & 1))));
+            if (lane == d) mine = __builtin_bitreverse64(b);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 32; j++) {
+            mine |= (uint64_t)nonzero_h(w[j]) << (63 - 2 * j);
+            mine |= (uint64_t)nonzero_h(w[j] >> 16) << (62 - 2 * j);
+        }
+    }
+    const int32_t own = ((__popcll(mine) + 7) & ~7) >> 1;   // half2 units
+    int32_t c = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t u = __shfl_up(c, o);
+        if (lane >= o) c += u;
+    }
+    if (lane == 63) s_tot[wave] = c;
+    __syncthreads();
+    int32_t base = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (k < wave) base += s_tot[k];
+        total += s_tot[k];
+    }
+    uint32_t* idx_h = s.idx + (int64_t)h * s.idx_stride;
+    s.bmp[(int64_t)h * s.bmp_stride + wave * 64 + lane] = mine;
+    idx_h[wave * 64 + lane + 1] = (uint32_t)(base + c);
+    if (threadIdx.x == 0) {
+        idx_h[0] = 0;
+        s.head_total[h] = 2 * (int64_t)total;
+        if (s.nz_offset) s.nz_offset[h] = (uint32_t)h * s.nz_stride;
+    }
+    if (s.region_halfs > 0 && 2 * (int64_t)total > s.region_halfs) {   // (workgroup-uniform)
+        if (threadIdx.x == 0) atomicOr(flag, 1);
+        return;
+    }
+    uint16_t* nz_h = s.nz + 8 * (int64_t)h * s.nz_stride;
+    const int32_t st = base + c - own;   // start of tile `lane` of this block (half2 units)
+    if (key) {
+#pragma unroll
+        for (int d = 0; d < 64; d++) {
+            const uint64_t m = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(mine >> 32), d) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, d);
+            const int32_t sd = __builtin_amdgcn_readlane(st, d);
+            pack_tile(nz_h + 2 * (int64_t)sd, m, (uint16_t)(w[d >> 1] >> (16 * (d & 1))), lane);
+        }
+    } else {   // the lane's own row: its non-zeros in channel order, then zeros up to ceil8(nnz)
+        uint16_t* dst = nz_h + 2 * (int64_t)st;
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < 64; j++) {
+            const uint16_t v = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+            if (nonzero_h(v)) dst[n++] = v;
+        }
+        for (; n < 2 * own; n++) dst[n] = 0;
+    }
+}
+
+// The tail of a trigger at D = 64 (mustafar_trigger_finish_batch_hd): one workgroup lists the extent's view in its slot of the device
+// table, all slide their head's window rows [drop, len) to the front.  The ranges may overlap: ascending pieces, each read in full
+// before it is written.
+__global__ __launch_bounds__(256) void hd64_trigger_finish_kernel(uint16_t* k_win, uint16_t* v_win, int64_t head_stride, int len, int drop,
+                                                                  mustafar_cache_view k_view, mustafar_cache_view v_view,
+                                                                  mustafar_cache_view* k_slot, mustafar_cache_view* v_slot)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        mustafar_cache_view* slot = blockIdx.y ? v_slot : k_slot;
+        if (slot) *slot = blockIdx.y ? v_view : k_view;
+    }
+    if (drop <= 0 || len <= drop) return;
+    uint16_t* win = (blockIdx.y ? v_win : k_win) + blockIdx.x * head_stride;
+    const int n16 = (len - drop) * (kD / 8);
+    const uint4* src = reinterpret_cast<const uint4*>(win + (int64_t)drop * kD);
+    uint4* dst = reinterpret_cast<uint4*>(win);
+    for (int base = 0; base < n16; base += 4 * 256) {   // (workgroup-uniform trip count)
+        uint4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int p = base + threadIdx.x + i * 256;
+            if (p < n16) v[i] = src[p];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int p = base + threadIdx.x + i * 256;
+            if (p < n16) dst[p] = v[i];
+        }
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ fused decode
 struct DecArgs {
     const h16* q;          // [BH, 64]
@@ -275,6 +415,40 @@ struct DecArgs {
     int T, BH, bpw, S1, w_len, w_cap;
     float inv_sqrt_d;
 };
+
+// Operands of the EXT instantiation (mustafar_decode_attention_extents_hd): the base arrays arrive through the kernel's eight pointers,
+// the blocks behind T_base through two DEVICE tables of mustafar_cache_view, four blocks per entry.  The plain instantiation carries
+// an empty struct in its place and compiles to what it was.
+struct ExtArgs {
+    const mustafar_cache_view* k_ext;
+    const mustafar_cache_view* v_ext;
+    const int32_t* t_dev;                // compressed tokens in use (a.T is then the capacity) or nullptr
+    int64_t k_bmp_stride, k_idx_stride, v_bmp_stride, v_idx_stride;   // head strides of the base rows
+    uint32_t k_nz_stride, v_nz_stride;   // != 0: the base's head h starts at h * stride (uint4 units) instead of k_off[h]
+    int T_base;
+};
+struct NoExt {};
+template <bool EXT> struct ExtOf { typedef NoExt type; };
+template <> struct ExtOf<true> { typedef ExtArgs type; };
+static_assert(sizeof(mustafar_cache_view) == 56, "the EXT kernel reads a table entry as seven 8-byte words");
+
+// One side of a 64-token block as the phases read it: bitmaps and offsets of its 64 tiles (scalar loads), the head's stream.
+struct BlockRef {
+    cu64_p bmp;
+    cu32_p idx;
+    const uint4* nz;
+};
+// Block j (0..3) of a table entry, head kvh: every field a scalar load (the entry is wave-uniform), offsets relative to the extent.
+__device__ __forceinline__ BlockRef extent_block(const mustafar_cache_view* entry, int kvh, int j)
+{
+    const cu64_p f = (cu64_p)reinterpret_cast<const uint64_t*>(entry);   // bmp, nz, idx, nz_offset, bmp stride, idx stride, nz stride
+    const int64_t bs = f[4] ? (int64_t)f[4] : 256, is = f[5] ? (int64_t)f[5] : 257;
+    BlockRef r;
+    r.bmp = (cu64_p)(reinterpret_cast<const uint64_t*>(f[0]) + kvh * bs + j * 64);
+    r.idx = (cu32_p)(reinterpret_cast<const uint32_t*>(f[2]) + kvh * is + j * 64);
+    r.nz = reinterpret_cast<const uint4*>(f[1]) + (int64_t)kvh * (int64_t)f[6];
+    return r;
+}
 
 // x = fp16(fp16(score) * (1/sqrt d)) (model :284; the product with the fp32 reciprocal, as at D = 128), then the hook's mask: an fp16
 // addition clamped at finfo(fp16).min (model :293-301).
@@ -312,11 +486,12 @@ __device__ __forceinline__ uint32_t stage_block(const uint4* __restrict__ head_n
     return i0;
 }
 
-template <int G, bool MASK>
+template <int G, bool MASK, bool EXT>
 __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restrict__ k_bmp, const uint4* __restrict__ k_nz,
                                                          const uint32_t* __restrict__ k_idx, const uint32_t* __restrict__ k_off,
                                                          const uint64_t* __restrict__ v_bmp, const uint4* __restrict__ v_nz,
-                                                         const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_off, DecArgs a)
+                                                         const uint32_t* __restrict__ v_idx, const uint32_t* __restrict__ v_off, DecArgs a,
+                                                         typename ExtOf<EXT>::type e)
 {
     __shared__ uint4 s_buf[512];        // a block's key or value stream (at most 4096 halfs)
     __shared__ h16 s_q[G * 64];
@@ -336,15 +511,46 @@ __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restr
 
     if (x < a.S1) {
         // ---- compressed blocks [tb0, tb1) of kv head kvh
-        const int ntb = a.T / 64;
-        const int tb0 = x * a.bpw, tb1 = min(ntb, tb0 + a.bpw);
-        const uint4* kz = k_nz + k_off[kvh];
-        const uint4* vz = v_nz + v_off[kvh];
+        int ntb = a.T / 64;   // blocks the launch is sized for; EXT with a device-side T: the blocks in use
+        if constexpr (EXT) { if (e.t_dev) ntb = min(ntb, __builtin_amdgcn_readfirstlane(*e.t_dev) >> 6); }
+        const int tb0 = x * a.bpw, tb1 = min(ntb, tb0 + a.bpw);   // (tb0 >= ntb: no block in use, the slabs keep weight zero)
+        const uint4* kz;
+        const uint4* vz;
+        int ntb_base = 0;
+        if constexpr (EXT) {
+            ntb_base = e.T_base >> 6;
+            kz = k_nz + (e.k_nz_stride ? (int64_t)kvh * e.k_nz_stride : (int64_t)k_off[kvh]);
+            vz = v_nz + (e.v_nz_stride ? (int64_t)kvh * e.v_nz_stride : (int64_t)v_off[kvh]);
+        } else {
+            kz = k_nz + k_off[kvh];
+            vz = v_nz + v_off[kvh];
+        }
         for (int tb = tb0; tb < tb1; tb++) {
-            const int64_t tile0 = (int64_t)kvh * a.T + (int64_t)tb * 64;
-            const cu64_p kb = (cu64_p)(k_bmp + tile0);
-            const cu32_p ki = (cu32_p)(k_idx + tile0 + kvh);
-            const uint32_t k0 = stage_block(kz, ki, s_buf, lane);
+            cu64_p kb, vb;
+            cu32_p ki, vi;
+            const uint4* kzb = kz;
+            const uint4* vzb = vz;
+            if constexpr (EXT) {   // resolved per block: a run may cross base -> extent and extent -> extent
+                if (tb < ntb_base) {
+                    kb = (cu64_p)(k_bmp + kvh * e.k_bmp_stride + (int64_t)tb * 64);
+                    ki = (cu32_p)(k_idx + kvh * e.k_idx_stride + (int64_t)tb * 64);
+                    vb = (cu64_p)(v_bmp + kvh * e.v_bmp_stride + (int64_t)tb * 64);
+                    vi = (cu32_p)(v_idx + kvh * e.v_idx_stride + (int64_t)tb * 64);
+                } else {
+                    const int xb = tb - ntb_base;
+                    const BlockRef kr = extent_block(e.k_ext + (xb >> 2), kvh, xb & 3);
+                    const BlockRef vr = extent_block(e.v_ext + (xb >> 2), kvh, xb & 3);
+                    kb = kr.bmp; ki = kr.idx; kzb = kr.nz;
+                    vb = vr.bmp; vi = vr.idx; vzb = vr.nz;
+                }
+            } else {
+                const int64_t tile0 = (int64_t)kvh * a.T + (int64_t)tb * 64;
+                kb = (cu64_p)(k_bmp + tile0);
+                ki = (cu32_p)(k_idx + tile0 + kvh);
+                vb = (cu64_p)(v_bmp + tile0);
+                vi = (cu32_p)(v_idx + tile0 + kvh);
+            }
+            const uint32_t k0 = stage_block(kzb, ki, s_buf, lane);
             __syncthreads();
             float s[G];
 #pragma unroll
@@ -366,9 +572,7 @@ __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restr
             }
             __syncthreads();   // (s_buf is read; the value stream goes there next)
             softmax_step<G>(xs, M, L, o, s_e, lane);
-            const cu64_p vb = (cu64_p)(v_bmp + tile0);
-            const cu32_p vi = (cu32_p)(v_idx + tile0 + kvh);
-            const uint32_t v0 = stage_block(vz, vi, s_buf, lane);
+            const uint32_t v0 = stage_block(vzb, vi, s_buf, lane);
             __syncthreads();
 #pragma unroll 16
             for (int r = 0; r < 64; r++) {   // value phase: lane = channel, tile r = token r
@@ -385,6 +589,8 @@ __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restr
         // ---- window chunk: rows [w0, w0 + 64) of the dense window (the step's new row appended at w_len - 1)
         const int w_len = a.w_extra ? min(a.w_len + *a.w_extra, a.w_cap) : a.w_len;
         const int w0 = (x - a.S1) * kWinChunk;
+        int T_used = a.T;   // the window rows' mask columns follow the compressed tokens IN USE (as the D = 128 extents launch)
+        if constexpr (EXT) { if (e.t_dev) T_used = __builtin_amdgcn_readfirstlane(*e.t_dev); }
         if (w0 < w_len) {
             const int w = w0 + lane;
             const bool valid = w < w_len;
@@ -407,7 +613,7 @@ __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restr
 #pragma unroll
                 for (int c = 0; c < kD; c++) s = __builtin_fmaf((float)kh[c], (float)s_q[g * 64 + c], s);
                 float xv = scaled(s, a.inv_sqrt_d);
-                if (MASK && valid) xv = masked(xv, mrow[g][a.T + w]);
+                if (MASK && valid) xv = masked(xv, mrow[g][T_used + w]);
                 xs[g] = valid ? xv : -INFINITY;
             }
             softmax_step<G>(xs, M, L, o, s_e, lane);
@@ -533,11 +739,14 @@ int64_t workspace_bytes(int T, int Batch_Size, int groups)
     return (int64_t)(S1 + kMaxWindow / kWinChunk) * Batch_Size * (kD + 2) * (int64_t)sizeof(float);
 }
 
-int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
-           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
-           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
-           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev)
+namespace {
+
+// Validation and launches shared by the two decode entry points.  ext == nullptr: the plain instantiation over one set of arrays.
+int launch_decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
+                  const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
+                  void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
+                  void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+                  const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, const ExtArgs* ext)
 {
     if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
     if (T < 0 || (T & 63) || groups < 1 || groups > 8 || Batch_Size < 1 || Batch_Size % groups || window_len < 1 ||
@@ -547,7 +756,9 @@ int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32
     if (!q || !k_window || !v_window || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
     // window rows (and the new rows) are read as 16-byte pieces
     if (!aligned16(k_window) || !aligned16(v_window) || (k_new && !aligned16(k_new))) return MUSTAFAR_EINVAL;
-    if (T > 0 && (!k_bmp || !k_nz || !k_idx || !k_nz_offset || !v_bmp || !v_nz || !v_idx || !v_nz_offset)) return MUSTAFAR_EINVAL;
+    if (T > 0 && (!k_bmp || !k_nz || !k_idx || !v_bmp || !v_nz || !v_idx)) return MUSTAFAR_EINVAL;
+    if (T > 0 && !(ext && ext->k_nz_stride) && !k_nz_offset) return MUSTAFAR_EINVAL;
+    if (T > 0 && !(ext && ext->v_nz_stride) && !v_nz_offset) return MUSTAFAR_EINVAL;
     const int Bp = Batch_Size / groups, ntb = T / 64;
     const int bpw = blocks_per_wg(ntb, Bp);
     const int S1 = ntb > 0 ? (ntb + bpw - 1) / bpw : 0;
@@ -562,14 +773,16 @@ int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32
     hipEvent_t e0 = ev ? ev[0] : nullptr, e1 = ev ? ev[1] : nullptr, e2 = ev ? ev[2] : nullptr, e3 = ev ? ev[3] : nullptr;
     auto kb = k_bmp, vb = v_bmp;
     auto kz = static_cast<const uint4*>(k_nz), vz = static_cast<const uint4*>(v_nz);
+#define MUSTAFAR_HD64_L(GG, MM, EE, TAIL)                                                                                                \
+    hipExtLaunchKernelGGL((hd64_decode_kernel<GG, MM, EE>), grid, dim3(64), 0, st, e0, e1, 0, kb, kz, k_idx, k_nz_offset, vb, vz, v_idx, \
+                          v_nz_offset, a, TAIL)
 #define MUSTAFAR_HD64(GG)                                                                                                              \
     do {                                                                                                                               \
-        if (attention_mask)                                                                                                            \
-            hipExtLaunchKernelGGL((hd64_decode_kernel<GG, true>), grid, dim3(64), 0, st, e0, e1, 0, kb, kz, k_idx, k_nz_offset, vb, vz, \
-                                  v_idx, v_nz_offset, a);                                                                              \
-        else                                                                                                                           \
-            hipExtLaunchKernelGGL((hd64_decode_kernel<GG, false>), grid, dim3(64), 0, st, e0, e1, 0, kb, kz, k_idx, k_nz_offset, vb,   \
-                                  vz, v_idx, v_nz_offset, a);                                                                          \
+        if (ext) {                                                                                                                     \
+            if (attention_mask) MUSTAFAR_HD64_L(GG, true, true, *ext); else MUSTAFAR_HD64_L(GG, false, true, *ext);                     \
+        } else {                                                                                                                       \
+            if (attention_mask) MUSTAFAR_HD64_L(GG, true, false, NoExt{}); else MUSTAFAR_HD64_L(GG, false, false, NoExt{});             \
+        }                                                                                                                              \
     } while (0)
     switch (groups) {
         case 1: MUSTAFAR_HD64(1); break;
@@ -582,8 +795,105 @@ int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32
         default: MUSTAFAR_HD64(8); break;
     }
 #undef MUSTAFAR_HD64
+#undef MUSTAFAR_HD64_L
     hipExtLaunchKernelGGL(hd64_finish_kernel, dim3(Batch_Size), dim3(256), 0, st, e2, e3, 0, ws_o, ws_ml, S1 + nchunks, Batch_Size,
                           static_cast<h16*>(out));
+    return (int)hipGetLastError();
+}
+
+// A 256-token extent's view as the trigger writes through it: equally spaced regions, rows of at least 256 / 257 entries.
+bool extent_view_ok(const mustafar_cache_view& v, int Bp, int64_t region_halfs)
+{
+    if (!v.bmp || !v.idx || !v.nz || !aligned16(v.nz) || v.nz_head_stride <= 0 || (int64_t)Bp * v.nz_head_stride > 0xffffffffll) return false;
+    if ((v.bmp_head_stride && v.bmp_head_stride < 256) || (v.idx_head_stride && v.idx_head_stride < 257)) return false;
+    return region_halfs > 0 && region_halfs <= 8 * v.nz_head_stride;
+}
+
+}  // namespace
+
+int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
+           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
+           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
+           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev)
+{
+    return launch_decode(st, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new, window_len,
+                         window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra,
+                         attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr);
+}
+
+int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                   const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, const void* q, void* k_window, void* v_window,
+                   const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                   void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
+                   const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, const int32_t* T_device, hipEvent_t* ev,
+                   bool* ran_extents)
+{
+    *ran_extents = false;
+    if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255) || (T - T_base) / 256 > kMaxExtents)
+        return MUSTAFAR_EINVAL;
+    if (T_device && T == T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
+    if (T == T_base) {   // no appended extent: the plain launch over the base (whose rows must then be exactly T long)
+        if ((k_base->bmp_head_stride && k_base->bmp_head_stride != T) || (k_base->idx_head_stride && k_base->idx_head_stride != T + 1) ||
+            (v_base->bmp_head_stride && v_base->bmp_head_stride != T) || (v_base->idx_head_stride && v_base->idx_head_stride != T + 1))
+            return MUSTAFAR_EINVAL;
+        return launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx, v_base->nz_offset,
+                             q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T,
+                             Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr);
+    }
+    if (!k_extents || !v_extents) return MUSTAFAR_EINVAL;
+    const mustafar_cache_view* b[2] = {k_base, v_base};
+    for (int i = 0; i < 2; i++)
+        if ((b[i]->bmp_head_stride && b[i]->bmp_head_stride < T_base) || (b[i]->idx_head_stride && b[i]->idx_head_stride < T_base + 1) ||
+            b[i]->nz_head_stride < 0 || b[i]->nz_head_stride > 0xffffffffll)
+            return MUSTAFAR_EINVAL;
+    const ExtArgs e{k_extents, v_extents, T_device,
+                    k_base->bmp_head_stride ? k_base->bmp_head_stride : T_base, k_base->idx_head_stride ? k_base->idx_head_stride : T_base + 1,
+                    v_base->bmp_head_stride ? v_base->bmp_head_stride : T_base, v_base->idx_head_stride ? v_base->idx_head_stride : T_base + 1,
+                    (uint32_t)k_base->nz_head_stride, (uint32_t)v_base->nz_head_stride, T_base};
+    const int err = launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx,
+                                  v_base->nz_offset, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
+                                  workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
+                                  heads_per_mask_row, ev, &e);
+    *ran_extents = err == 0;
+    return err;
+}
+
+int trigger_compress_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
+                           int64_t k_region_halfs, int64_t v_region_halfs)
+{
+    if (n < 1 || !items || Bp < 1 || t != 256 || head_stride < (int64_t)t * kD || (head_stride & 7) || kth_k < 0 || kth_k > kD || kth_v < 0 ||
+        kth_v > kD)
+        return MUSTAFAR_EINVAL;
+    for (int i = 0; i < n; i++) {   // every item is checked before anything is launched
+        const mustafar_trigger_item& it = items[i];
+        if (!it.k_window || !it.v_window || !aligned16(it.k_window) || !aligned16(it.v_window) || !it.k_head_total || !it.v_head_total ||
+            !it.overflow_flag || !extent_view_ok(it.k_dst, Bp, k_region_halfs) || !extent_view_ok(it.v_dst, Bp, v_region_halfs))
+            return MUSTAFAR_EINVAL;
+    }
+    for (int i = 0; i < n; i++) {
+        const mustafar_trigger_item& it = items[i];
+        const ExtSide ks{static_cast<const uint16_t*>(it.k_window), it.k_dst.bmp, it.k_dst.idx, static_cast<uint16_t*>(it.k_dst.nz),
+                         it.k_dst.nz_offset, it.k_head_total, it.k_dst.bmp_head_stride ? it.k_dst.bmp_head_stride : 256,
+                         it.k_dst.idx_head_stride ? it.k_dst.idx_head_stride : 257, k_region_halfs, (uint32_t)it.k_dst.nz_head_stride, kth_k};
+        const ExtSide vs{static_cast<const uint16_t*>(it.v_window), it.v_dst.bmp, it.v_dst.idx, static_cast<uint16_t*>(it.v_dst.nz),
+                         it.v_dst.nz_offset, it.v_head_total, it.v_dst.bmp_head_stride ? it.v_dst.bmp_head_stride : 256,
+                         it.v_dst.idx_head_stride ? it.v_dst.idx_head_stride : 257, v_region_halfs, (uint32_t)it.v_dst.nz_head_stride, kth_v};
+        hd64_extent_compress_kernel<<<dim3(Bp, 2), 256, 0, st>>>(ks, vs, head_stride, it.overflow_flag);
+    }
+    return (int)hipGetLastError();
+}
+
+int trigger_finish_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop)
+{
+    if (n < 1 || !items || Bp < 1 || drop < 0 || len < drop || head_stride < (int64_t)len * kD || (head_stride & 7)) return MUSTAFAR_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!items[i].k_window || !items[i].v_window || !aligned16(items[i].k_window) || !aligned16(items[i].v_window)) return MUSTAFAR_EINVAL;
+    for (int i = 0; i < n; i++) {
+        const mustafar_trigger_item& it = items[i];
+        hd64_trigger_finish_kernel<<<dim3(Bp, 2), 256, 0, st>>>(static_cast<uint16_t*>(it.k_window), static_cast<uint16_t*>(it.v_window),
+                                                                head_stride, len, drop, it.k_dst, it.v_dst, it.k_table_slot, it.v_table_slot);
+    }
     return (int)hipGetLastError();
 }
 

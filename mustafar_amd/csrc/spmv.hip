@@ -3659,7 +3659,7 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
 
 extern "C" {
 
-int mustafar_abi_version(void) { return 107; }   // 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
+int mustafar_abi_version(void) { return 108; }   // 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
 
 int Key_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const void* NZ, const uint32_t* idx,
                    const uint32_t* NZ_offset, const void* B, void* C, int M_Global, int N_Global, int K_Global,
@@ -4035,6 +4035,34 @@ int mustafar_decode_attention_extents(void* stream, const mustafar_cache_view* k
     return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
                             out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
                             mask_row_stride, heads_per_mask_row, flags, k_extents, v_extents, T_base, T_device);
+}
+
+int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                         const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                         const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                         int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                                         int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                         const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                         int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim)
+{
+    if (head_dim == kD)
+        return mustafar_decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new,
+                                                 window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
+                                                 num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
+                                                 heads_per_mask_row, flags, T_device);
+    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;   // as mustafar_decode_attention_hd
+    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
+    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
+    bool ran_extents = false;
+    const int err = mustafar_hd64::decode_extents(static_cast<hipStream_t>(stream), k_base, v_base, T_base, k_extents, v_extents, q, k_window,
+                                                  v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K,
+                                                  T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
+                                                  heads_per_mask_row, T_device, prof ? g_prof.ev + 4 * g_prof.n : nullptr, &ran_extents);
+    if (err) return err;
+    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
+    t_last_choice = 0 | (1 << 4) | ((ran_extents ? 6 : 5) << 8);
+    return 0;
 }
 
 int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint32_t flags)

@@ -30,6 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib, compression, mustafar_package
 from .cache import CompressedArena
+from .cache64 import ExtentCache64
 
 
 def _operator_module():
@@ -76,6 +77,9 @@ class MustafarConfig:
     # one process run what each of them asks for.
     engine: Optional[str] = None
     structure: Optional[str] = None
+    # head_dim 64, api="fused", arena=False only: the compressed cache grows by 256-token extents (cache64.py) instead of being
+    # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
+    hd64_extents: bool = False
 
 
 def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
@@ -201,6 +205,10 @@ class MustafarAttention:
             # the reference SpMV entry points are head_dim 128 only; head_dim 64 decodes through its own fused kernel
             raise ValueError("head_dim 64 is supported with MustafarConfig(api='fused', arena=False) only "
                              f"(got api={config.api!r}, arena={config.arena})")
+        if config.hd64_extents and not (config.head_dim == 64 and config.api == "fused" and not config.arena):
+            raise ValueError("hd64_extents is the head_dim 64 cache that grows by extents: it needs "
+                             f"MustafarConfig(head_dim=64, api='fused', arena=False) (got head_dim={config.head_dim}, api={config.api!r}, "
+                             f"arena={config.arena})")
         self.Reduction_Workspace = None   # model :658: a 1-element fp16 tensor shared by all layers
 
     # ---- pruning (model :77-153) -----------------------------------------------------------------------------
@@ -266,9 +274,14 @@ class MustafarAttention:
         return attn_output, self.build_cache(key_states, value_states)
 
     # ---- fused decode (extension) ---------------------------------------------------------------------------
+    EXTENT_CACHE_64 = ExtentCache64   # the cache class of hd64_extents (tests subclass it with a small table)
+
     def to_fused(self, past):
         """Wrap the two local windows of a reference-layout `past` into appendable buffers."""
         k_c, k_w, v_c, v_w, C, L = past
+        if self.cfg.hd64_extents and C and not isinstance(k_c, ExtentCache64):   # (creates the device tables: before any capture)
+            Bkv = k_w.shape[0] * k_w.shape[1] if not isinstance(k_w, Window) else k_w.buf.shape[0] * k_w.buf.shape[1]
+            k_c, v_c = self.EXTENT_CACHE_64(k_c, "key", Bkv, C), self.EXTENT_CACHE_64(v_c, "value", Bkv, C)
         if self.cfg.arena and C and not isinstance(k_c, CompressedArena):
             k_c = CompressedArena.from_reference(k_c, "key", C, None, self._slack())
             v_c = CompressedArena.from_reference(v_c, "value", C, None, self._slack())
@@ -329,6 +342,9 @@ class MustafarAttention:
         length up to `t_capacity`: after a trigger (run eagerly, outside the graph) the caller adds 256 to `t_device` and takes
         256 off `step_counter` (tests/test_gpu_extents.py)."""
         cfg = self.cfg
+        if cfg.hd64_extents:
+            return self._decode_fused_ext64(query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
+                                            defer_trigger)
         bsz, _, q_len, D = query_states.shape
         assert q_len == 1 and (D == 128 or (D == 64 and self.head_dim == 64))
         BH, Bkv, groups = bsz * self.num_heads, bsz * self.num_key_value_heads, self.num_key_value_groups
@@ -450,6 +466,112 @@ class MustafarAttention:
             C += 256
         return out, (k_c, k_w, v_c, v_w, C, kv_seq_len)
 
+    # ---- head_dim 64 over a cache that grows by extents (MustafarConfig(hd64_extents=True); cache64.py) ---------------------------------
+    def _decode_fused_ext64(self, query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
+                            defer_trigger):
+        """decode_fused for ExtentCache64 caches: the plain D = 64 launch while the cache is its base alone, the extents launch once
+        extents exist or whenever `t_device` is passed; the trigger through run_triggers' batched form."""
+        cfg = self.cfg
+        bsz, _, q_len, D = query_states.shape
+        assert q_len == 1 and D == 64
+        BH, groups = bsz * self.num_heads, self.num_key_value_groups
+        k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
+        cap_T = C
+        if t_device is not None:
+            if step_counter is None:
+                raise ValueError("decode_fused: t_device is for captured graphs and needs step_counter (an eager call passes neither)")
+            if t_capacity is None or not isinstance(k_c, ExtentCache64) or t_capacity <= k_c.tokens or t_capacity < C or \
+                    (t_capacity - k_c.tokens) % 256 or (t_capacity - k_c.tokens) // 256 > k_c.MAX_EXTENTS:
+                raise ValueError("decode_fused: t_device needs an extent cache and t_capacity = base tokens + a multiple of 256 (at most the "
+                                 "table's entries), not below the compressed length")
+            cap_T = t_capacity
+        kv_seq_len = past[-1] + 1
+        w_len = k_w.len + 1
+        k_w.reserve(w_len)
+        v_w.reserve(w_len)
+        if k_w.cap != v_w.cap:
+            raise RuntimeError("key/value windows must have the same capacity")
+        dev = query_states.device
+        L = _lib.load()
+        ws_bytes = L.mustafar_decode_workspace_bytes_hd(cap_T, BH, groups, 1, D)
+        ld = (cap_T + k_w.cap + 31) // 32 * 32
+        scores, ws = self._scratch(dev, BH, ld, ws_bytes)
+        out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
+        q = query_states if query_states.is_contiguous() else query_states.contiguous()
+        kn = key_states if key_states.is_contiguous() else key_states.contiguous()
+        vn = value_states if value_states.is_contiguous() else value_states.contiguous()
+        if kn.data_ptr() % 16:
+            kn = kn.clone()
+        mask_ptr, mask_stride = None, 0
+        if attention_mask is not None:
+            need = cap_T + w_len if step_counter is None else cap_T + k_w.cap
+            if attention_mask.dim() != 4 or attention_mask.shape[:3] != (bsz, 1, q_len) or attention_mask.shape[3] < need or \
+                    (step_counter is None and attention_mask.shape[3] != kv_seq_len):
+                raise ValueError(f"Attention mask should be of size {(bsz, 1, q_len, kv_seq_len)}, but is {tuple(attention_mask.size())}")
+            if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
+                raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
+            if attention_mask.stride(3) != 1:
+                attention_mask = attention_mask.contiguous()
+            mask_ptr, mask_stride = attention_mask.data_ptr(), attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3]
+        tail = (q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(), w_len, k_w.cap,
+                scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(), 1, cap_T, BH, groups, math.sqrt(D),
+                step_counter.data_ptr() if step_counter is not None else None, mask_ptr, mask_stride, self.num_heads,
+                _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure])
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if isinstance(k_c, ExtentCache64) and (k_c.extents or t_device is not None):
+                err = L.mustafar_decode_attention_extents_hd(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.table.data_ptr(),
+                                                             v_c.table.data_ptr(), *tail,
+                                                             t_device.data_ptr() if t_device is not None else None, D)
+            elif isinstance(k_c, ExtentCache64):
+                kb, vb = k_c.base_view, v_c.base_view
+                err = L.mustafar_decode_attention_hd(st, kb.bmp, kb.nz, kb.idx, kb.nz_offset, vb.bmp, vb.nz, vb.idx, vb.nz_offset, *tail, D)
+            else:
+                err = L.mustafar_decode_attention_hd(st, *([None] * 8), *tail, D)
+        _lib.check(err, "mustafar_decode_attention_extents_hd")
+        if step_counter is not None:
+            return out, (k_c, k_w, v_c, v_w, C, kv_seq_len - 1)
+        k_w.len = v_w.len = w_len
+        new = (k_c, k_w, v_c, v_w, C, kv_seq_len)
+        if not defer_trigger and self.trigger_due(new):
+            new = self._run_triggers_ext64([new])[0]
+        return out, new
+
+    def _run_triggers_ext64(self, pasts):
+        """The trigger of every layer that is due.  A cache that is still empty (C = 0) gets its base from the window rows the
+        reference's way (prune, two-pass conversion: the base is reference-layout arrays); every other layer's 256 rows become an
+        extent, all layers in one batched call (ExtentCache64.append_extents).  A full table is consolidated first."""
+        cfg, D = self.cfg, self.head_dim
+        kth_k, kth_v = compression.kth_from_sparsity(cfg.k_sparsity, D), compression.kth_from_sparsity(cfg.v_sparsity, D)
+        out = list(pasts)
+        groups = {}
+        for i, p in enumerate(pasts):
+            if not self.trigger_due(p):
+                continue
+            k_c, k_w, v_c, v_w, C, L = p
+            Bkv = k_w.buf.shape[0] * k_w.buf.shape[1]
+            if C == 0:
+                k_blk = self.dh_prune_key(k_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)
+                v_blk = self.dh_prune_value(v_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)
+                k_c = self.EXTENT_CACHE_64(_compress(k_blk, "key"), "key", Bkv, 256)
+                v_c = self.EXTENT_CACHE_64(_compress(v_blk, "value"), "value", Bkv, 256)
+                k_w.drop_front(256)
+                v_w.drop_front(256)
+                out[i] = (k_c, k_w, v_c, v_w, 256, L)
+                continue
+            if len(k_c.extents) >= k_c.MAX_EXTENTS:   # table full: one copy of the cache (new addresses), then extents again
+                k_c, v_c = k_c.consolidate(), v_c.consolidate()
+                out[i] = (k_c, k_w, v_c, v_w, C, L)
+            groups.setdefault((k_w.len, tuple(k_w.buf.shape)), []).append(i)
+        for (wl, _), idxs in groups.items():   # (one group in a model: every layer's window has the same shape and length)
+            ExtentCache64.append_extents([(out[i][0], out[i][2]) for i in idxs], [(out[i][1].buf, out[i][3].buf) for i in idxs],
+                                         kth_k, kth_v, wl)
+            for i in idxs:
+                k_c, k_w, v_c, v_w, C, L = out[i]
+                k_w.len = v_w.len = wl - 256
+                out[i] = (k_c, k_w, v_c, v_w, C + 256, L)
+        return out
+
     # ---- the 256-token trigger of all layers at once (round 4) ----------------------------------------------------------------------
     def trigger_due(self, past) -> bool:
         """The step that produced `past` (its kv_seq_len already counted) reached the trigger of model :324."""
@@ -478,6 +600,8 @@ class MustafarAttention:
         cache, slide the windows.  All layers in two library calls and one host read (cache.py: append_extent_pairs) where the cache
         grows by extents; layer by layer otherwise.  Returns the new list of pasts."""
         cfg, D = self.cfg, self.head_dim
+        if cfg.hd64_extents:
+            return self._run_triggers_ext64(pasts)
         kth_k, kth_v = compression.kth_from_sparsity(cfg.k_sparsity, D), compression.kth_from_sparsity(cfg.v_sparsity, D)
         out = list(pasts)
         due = [i for i, p in enumerate(pasts) if self.trigger_due(p)]
@@ -535,7 +659,7 @@ class MustafarAttention:
             return self.decode_fused(query_states, key_states, value_states, past, attention_mask=attention_mask)
         if isinstance(past[1], Window):   # a fused cache handed to the unfused path
             past = (past[0], past[1].view(), past[2], past[3].view(), past[4], past[5])
-        if isinstance(past[0], CompressedArena):
+        if isinstance(past[0], (CompressedArena, ExtentCache64)):
             past = (past[0].to_reference(), past[1], past[2].to_reference(), past[3], past[4], past[5])
         bsz, _, q_len, D = query_states.shape
         total_batch_size = bsz * self.num_heads

@@ -7,6 +7,14 @@ Prints ONE JSON line.  Per cache length L (prefill of L tokens, then decode):
   bytes_per_layer   bytes the step must read per layer: compressed K / V streams + bitmaps + offsets, dense window rows, q and out
   frac_8tbs_kernel  bytes_per_layer / kernel_us over 8 TB/s;  frac_8tbs_step  16 x bytes_per_layer per step over 8 TB/s
 and, at L = 8192, prune_convert_us_per_layer: device-synchronised wall time of one layer's prefill prune + two-pass conversion of K and V.
+--generate N (with --gen-length L, default 8192; default N = 0: leg off) adds a generate leg: N tokens from a prefill of L (600 tokens: three
+triggers), timed two ways, alternated A B A B in one process:
+  extents   MustafarConfig(hd64_extents=True): ONE captured graph of the step with a device-side T, replayed through every trigger;
+            the trigger step runs eagerly for all layers (decode_fused(defer_trigger=True) + run_triggers: one batched call)
+  tuple     the parent's way: the tuple cache, the trigger inside the eager step, every array moved, so the graph is captured again
+Each reports tok_s over the whole generate (host wall time, device-synchronised at the end) and trigger_step_ms, the mean wall time of a
+step that fires a trigger (recapture included for the tuple way); and ext_kernel_us / plain_kernel_us: the decode launch of the EXT
+instantiation against the plain one at the same T with no extent listed.
 Needs an MI355X; it does not fall back to anything.  Usage: python tools/bench_headdim64.py [--lengths 4096,8192,32768] [--steps 64]
 """
 from __future__ import annotations
@@ -118,21 +126,120 @@ def run_length(L: int, steps: int, dev) -> dict:
             "prune_convert_us_per_layer": round(sorted(conv_us[1:])[len(conv_us[1:]) // 2], 1)}
 
 
+def _kernel_us(Lb, fn, n=4):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    _lib.check(Lb.mustafar_profile_begin(n * LAYERS), "mustafar_profile_begin")
+    for _ in range(n):
+        fn()
+    k_us, v_us, f_us, recs = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _lib.check(Lb.mustafar_profile_end2(ctypes.byref(k_us), ctypes.byref(v_us), ctypes.byref(f_us), ctypes.byref(recs)), "mustafar_profile_end2")
+    return k_us.value
+
+
+def generate(L: int, n_tokens: int, extents: bool, dev, kernel_ab: bool = False) -> dict:
+    """One generate of n_tokens from a prefill of L tokens (the same random data for both ways)."""
+    R = 32
+    attn = MustafarAttention(MustafarConfig(num_attention_heads=HQ, num_key_value_heads=HKV, head_dim=D, k_sparsity=S, v_sparsity=S,
+                                            api="fused", residual_length=R, hd64_extents=extents))
+    g = torch.Generator(device=dev).manual_seed(L + 1)
+    pasts = []
+    for layer in range(LAYERS):
+        K = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+        V = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+        pasts.append(attn.to_fused(attn.build_cache(K, V)))
+        del K, V
+    q = torch.randn((BATCH, HQ, 1, D), generator=g, device=dev).half()
+    kn = torch.randn((BATCH, HKV, 1, D), generator=g, device=dev).half()
+    vn = torch.randn((BATCH, HKV, 1, D), generator=g, device=dev).half()
+    ctr = torch.zeros((1,), dtype=torch.int32, device=dev)
+    Lb = _lib.load()
+    C0 = pasts[0][4]
+    n_trig = sum(1 for i in range(n_tokens) if (L + i + 1 - R - C0) % 256 == 0)
+    cap = C0 + 256 * max(1, n_trig)
+    t_dev = torch.tensor([C0], dtype=torch.int32, device=dev)
+    kw = dict(step_counter=ctr, t_device=t_dev, t_capacity=cap) if extents else dict(step_counter=ctr)
+    res = {}
+    if kernel_ab and extents:   # the EXT instantiation with no extent listed against the plain launch, same T
+        res["plain_kernel_us"] = round(_kernel_us(Lb, lambda: [attn.decode_fused(q, kn, vn, p, step_counter=ctr) for p in pasts]), 3)
+        assert Lb.mustafar_last_decode_choice() >> 8 == 5
+        t_dev.fill_(C0)
+        ab = dict(step_counter=ctr, t_device=t_dev, t_capacity=C0 + 256)
+        res["ext_kernel_us"] = round(_kernel_us(Lb, lambda: [attn.decode_fused(q, kn, vn, p, **ab) for p in pasts]), 3)
+        assert Lb.mustafar_last_decode_choice() >> 8 == 6
+        res["kernel_T"] = C0
+
+    def capture():
+        ctr.zero_()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for p in pasts:
+                attn.decode_fused(q, kn, vn, p, **kw)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for p in pasts:
+                attn.decode_fused(q, kn, vn, p, **kw)
+            Lb.mustafar_counter_add(torch.cuda.current_stream().cuda_stream, ctr.data_ptr(), 1)
+        return graph
+
+    graph = capture()
+    torch.cuda.synchronize()
+    since, trig_ms = 0, []
+    t_start = time.perf_counter()
+    for i in range(n_tokens):
+        n = pasts[0][5] + since + 1
+        if (n - R - pasts[0][4]) % 256 == 0 and pasts[0][1].len + since + 1 >= 256:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pasts = [attn.advance(p, since) for p in pasts]
+            since = 0
+            if extents:   # the step eagerly, then the trigger of all layers in one batched call; the graph lives on
+                pasts = [attn.decode_fused(q, kn, vn, p, defer_trigger=True)[1] for p in pasts]
+                pasts = attn.run_triggers(pasts)
+                t_dev.add_(256)
+                ctr.add_(1 - 256)
+            else:         # the step with its trigger inside, then a new capture: every array has moved
+                pasts = [attn.decode_fused(q, kn, vn, p)[1] for p in pasts]
+                graph = capture()
+            torch.cuda.synchronize()
+            trig_ms.append((time.perf_counter() - t0) * 1e3)
+        else:
+            graph.replay()
+            since += 1
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t_start
+    res.update({"way": "extents" if extents else "tuple", "tok_s": round(BATCH * n_tokens / wall, 1), "triggers": len(trig_ms),
+                "trigger_step_ms": round(sum(trig_ms) / max(1, len(trig_ms)), 3)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lengths", default="4096,8192,32768")
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--generate", type=int, default=0)
+    ap.add_argument("--gen-length", type=int, default=8192)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_headdim64 needs a GPU")
     dev = torch.device("cuda:0")
     res = []
-    for L in (int(v) for v in args.lengths.split(",")):
+    for L in (int(v) for v in args.lengths.split(",") if v):
         res.append(run_length(L, args.steps, dev))
         torch.cuda.empty_cache()
     out = {"workload": "llama-3.2-1b decode, head_dim 64", "layers": LAYERS, "q_heads": HQ, "kv_heads": HKV, "head_dim": D, "batch": BATCH,
            "k_sparsity": S, "v_sparsity": S, "device": torch.cuda.get_device_name(dev), "results": res,
            "prune_convert_us_per_layer_L8192": next((r["prune_convert_us_per_layer"] for r in res if r["L"] == 8192), None)}
+    if args.generate > 0:   # A B A B: extents, tuple, extents, tuple
+        runs = []
+        for rep in range(2):
+            for ext in (True, False):
+                runs.append(generate(args.gen_length, args.generate, ext, dev, kernel_ab=rep == 0))
+                torch.cuda.empty_cache()
+        out["generate"] = {"L": args.gen_length, "tokens": args.generate, "runs": runs}
     print(json.dumps(out))
 
 
