@@ -24,6 +24,8 @@
  *              idx [B', t + 1].  Row pointers (x, out, windows, k_new) must be 16-byte aligned (rows are moved as 16-byte pieces).
  *              Growth by extents (ABI 108): mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd and
  *              mustafar_decode_attention_extents_hd.
+ *              The prefill from raw rows and the gather of 256-token pieces (ABI 109): mustafar_prefill_compress_hd and
+ *              mustafar_cache_gather_hd.
  *              Everything else returns MUSTAFAR_EINVAL for D = 64: the two reference SpMV entry points (D = 128 in the reference),
  *              the one-pass conversion, mustafar_cache_append_*, mustafar_trigger_compress_batch and the D = 128 cache-view /
  *              extent decode forms.
@@ -395,6 +397,47 @@ int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view
                                          int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
                                          const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                          int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim);
+
+/*
+ * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
+ * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
+ *
+ * mustafar_prefill_compress_hd: ONE launch for one layer, grid (kv head, 256-token chunk, K / V): the launch of
+ *   mustafar_trigger_compress_batch_hd with a chunk index.  Chunk c of head h reads the raw rows [256 c, 256 c + 256) at
+ *   x + h * head_stride + c * 256 * 64 (head_stride: whatever the caller's buffer has -- in a prefill L * 64 with only the first t rows of a
+ *   head compressed; rows 16-byte aligned, head_stride % 8 == 0, head_stride >= t * 64) and writes an EXTENT OF ITS OWN exactly as the
+ *   trigger writes one: prune (kth = 0: already pruned), 256 bitmaps, 257 offsets starting at 0, nz_offset, the stream in the chunk's
+ *   region, the chunk's length.  t % 256 == 0, 0 < t <= 512 * 256.
+ *   k_stage / v_stage     HOST views of chunk 0's extent (as k_dst / v_dst of mustafar_trigger_item: nz_head_stride != 0, nz 16-byte
+ *                         aligned, bmp / idx strides 0 or >= 256 / 257).  Every array of chunk c lies c * {k,v}_chunk_bytes BYTES behind
+ *                         chunk 0's (chunk_bytes > 0, % 16 == 0): t / 256 equally spaced extents per side
+ *   k_pieces / v_pieces   DEVICE arrays of t / 256 mustafar_cache_view, or NULL: entry c is written with chunk c's view by this launch --
+ *                         the table mustafar_cache_gather_hd (or mustafar_decode_attention_extents_hd) reads
+ *   k_head_total / v_head_total   i64 [t / 256][B'] out: chunk c's length of head h in halfs at [c * B' + h]
+ *   *_region_halfs        the room of a (head, chunk) region, REQUIRED (0 < region_halfs <= 8 * nz_head_stride).  A (head, chunk) that
+ *                         needs more sets bit 0 of overflow_flag (device int, REQUIRED, zeroed by the caller), still writes its bitmaps,
+ *                         offsets and length (the length it needs) and writes NO stream bytes; every other (head, chunk) is complete.
+ *                         The call is idempotent: repeat it at the measured size.  No workgroup waits for another: bit 1 never occurs.
+ * mustafar_cache_gather_hd: ONE launch, grid (piece, kv head), nothing read on the host, no workgroup waits for another.  Gathers, one side
+ *   per call, an optional first cache of `first_tokens` tokens and the `n_pieces` 256-token pieces of a DEVICE table (entry i: tokens
+ *   [first_tokens + 256 i, first_tokens + 256 (i + 1)), offsets relative to the piece, nz_head_stride != 0 or nz_offset loaded; bmp / idx
+ *   strides 0 = 256 / 257) into `dst`, a reference-layout cache of first_tokens + 256 n_pieces tokens: bitmaps copied, offsets shifted by
+ *   the head's stream length in front of the piece (model :352-360) -- the first view's last offset and the last offsets of the pieces in
+ *   front, summed on the device --, streams copied head behind piece behind piece.
+ *   first      HOST view (any strides; nz_head_stride 0: nz_offset is loaded) or NULL with first_tokens == 0; first_tokens % 256 == 0
+ *   pieces     DEVICE table; n_pieces <= 512 (NULL with n_pieces == 0); first_tokens / 256 + n_pieces >= 1
+ *   dst        HOST view: bmp / idx strides 0 (exactly the tokens / tokens + 1) or larger (columns beyond are not written); the CALLER has
+ *              set nz_head_stride (!= 0: head h starts at h * nz_head_stride) or filled nz_offset (uint4 units) from the lengths it knows
+ *              on the host, and has sized nz for them; neither is written here.  idx[h][0] is written (0).
+ *   Alignment: streams move as 16-byte pieces.  Every tile's stream is padded to 8 halfs, so every length and offset is a multiple of
+ *   16 bytes; REQUIRED of the caller: nz of dst, first and every piece 16-byte aligned (head starts are in uint4 units already).
+ */
+int mustafar_prefill_compress_hd(void* stream, const void* k_x, const void* v_x, int64_t head_stride, int Bp, int t, int D, int kth_k, int kth_v,
+                                 const mustafar_cache_view* k_stage, const mustafar_cache_view* v_stage, int64_t k_chunk_bytes,
+                                 int64_t v_chunk_bytes, mustafar_cache_view* k_pieces, mustafar_cache_view* v_pieces, int64_t* k_head_total,
+                                 int64_t* v_head_total, int64_t k_region_halfs, int64_t v_region_halfs, int32_t* overflow_flag);
+int mustafar_cache_gather_hd(void* stream, const mustafar_cache_view* dst, const mustafar_cache_view* first, int first_tokens,
+                             const mustafar_cache_view* pieces, int n_pieces, int Bp, int D);
 
 /*
  * FMA engine, process default (a fused call may carry its own in `flags`):

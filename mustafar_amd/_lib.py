@@ -53,6 +53,9 @@ SIGNATURES = {
                                               ctypes.c_uint32, _vp, _i32]),
     "mustafar_trigger_compress_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "mustafar_trigger_finish_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32]),
+    "mustafar_prefill_compress_hd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _view_p, _view_p, _i64, _i64, _vp, _vp, _vp, _vp,
+                                           _i64, _i64, _vp]),
+    "mustafar_cache_gather_hd": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _i32, _i32, _i32]),
     "mustafar_decode_reads_extents": (_i32, [_i32, _i32, ctypes.c_uint32]),
     "mustafar_cache_append_bitmap_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_bitmap_value": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),

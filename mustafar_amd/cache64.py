@@ -16,9 +16,12 @@ trigger.  `ExtentCache64` keeps one side (K or V) of one layer the way `Compress
     bit 0 (a head outgrew its region: rows full of ties) is redone on its own at the measured size before any window slides.
 
 `to_reference()` concatenates base and extents the way the model appends (`hook.append_compressed`): the same tensors, bit for bit,
-that the tuple path holds after the same triggers.  `consolidate()` (a full table) goes through that reference layout -- torch.cat on
-the device, one copy of the cache, every address new, so a captured graph must be taken again; a device-side consolidation as
-cache.py has at D = 128 is left for later (512 extents are 128 k generated tokens).
+that the tuple path holds after the same triggers.  `consolidate()` (a full table: 512 extents are 128 k generated tokens) builds the
+same cache on the device: the reference-layout arrays at exact size from the lengths the host already holds (`base_used`, every
+extent's `used`), and ONE mustafar_cache_gather_hd launch over base + table that copies bitmaps, shifts offsets and moves every head's
+stream into place -- one copy of the cache, nothing read back, every address new, so a captured graph must be taken again.
+`consolidate(via_reference=True)` keeps the route through `to_reference()` (a `torch.cat` of the whole cache per extent) for comparison.
+The same launch ends a prefill compressed from the raw rows in 256-token chunks (`compression.compress_raw_pair_hd64`).
 """
 from __future__ import annotations
 
@@ -210,9 +213,29 @@ class ExtentCache64:
             tokens += EXT_TOKENS
         return ref
 
-    def consolidate(self) -> "ExtentCache64":
-        """One base holding everything, through the reference layout (module docstring): a copy of the cache, new addresses, a new
-        and empty table."""
+    def consolidate(self, via_reference: bool = False) -> "ExtentCache64":
+        """One base holding everything (module docstring): exact-size arrays, one gather launch over base + table; new addresses, a new
+        and empty table.  via_reference: through `to_reference()` instead (the same bits)."""
         if not self.extents:
             return self
-        return type(self)(self.to_reference(), self.which, self.heads, self.total_tokens)
+        if via_reference or self.base_view.nz is None:   # (a base without any stream: nothing for the launch to align on)
+            return type(self)(self.to_reference(), self.which, self.heads, self.total_tokens)
+        from .compression import pieces_of
+        from .hook import FlatStreams
+        T, H, dev = self.total_tokens, self.heads, self.device
+        used = self.base_used.clone()
+        for e in self.extents:
+            used += e.used
+        offs = [0] + torch.cumsum(used, 0).tolist()
+        if offs[-1] // 8 > 0xffffffff:
+            raise RuntimeError("ExtentCache64.consolidate: the packed stream exceeds what nz_offset (uint4 units, 32 bits) can address")
+        bmp = torch.empty((H * T,), dtype=torch.int64, device=dev)
+        idx = torch.empty((H * (T + 1),), dtype=torch.int32, device=dev)
+        packed = torch.empty((offs[-1],), dtype=torch.float16, device=dev)
+        nz_offset = torch.tensor([o // 8 for o in offs[:-1]], dtype=torch.int32, device=dev)
+        dst = _lib.CacheView(bmp.data_ptr(), packed.data_ptr(), idx.data_ptr(), nz_offset.data_ptr(), 0, 0, 0)
+        with torch.cuda.device(dev):
+            err = _lib.load().mustafar_cache_gather_hd(torch.cuda.current_stream(dev).cuda_stream, dst, self.base_view, self.tokens,
+                                                       self.table.data_ptr(), len(self.extents), H, D)
+        _lib.check(err, "mustafar_cache_gather_hd")
+        return type(self)([bmp, idx, FlatStreams(pieces_of(packed, offs), flat=packed), nz_offset], self.which, H, T)

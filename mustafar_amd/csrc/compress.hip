@@ -1167,6 +1167,26 @@ int mustafar_trigger_finish_batch_hd(void* stream, int n, const mustafar_trigger
     return mustafar_hd64::trigger_finish_batch(static_cast<hipStream_t>(stream), n, items, head_stride, Bp, len, drop);
 }
 
+// head_dim 64 (ABI 109): a prefill compressed from the raw rows in 256-token chunks, and the gather of 256-token pieces into one
+// reference-layout cache (the end of that prefill and ExtentCache64.consolidate()); both in headdim64.hip.
+int mustafar_prefill_compress_hd(void* stream, const void* k_x, const void* v_x, int64_t head_stride, int Bp, int t, int D, int kth_k, int kth_v,
+                                 const mustafar_cache_view* k_stage, const mustafar_cache_view* v_stage, int64_t k_chunk_bytes,
+                                 int64_t v_chunk_bytes, mustafar_cache_view* k_pieces, mustafar_cache_view* v_pieces, int64_t* k_head_total,
+                                 int64_t* v_head_total, int64_t k_region_halfs, int64_t v_region_halfs, int32_t* overflow_flag)
+{
+    if (D != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    return mustafar_hd64::prefill_compress(static_cast<hipStream_t>(stream), k_x, v_x, head_stride, Bp, t, kth_k, kth_v, k_stage, v_stage,
+                                           k_chunk_bytes, v_chunk_bytes, k_pieces, v_pieces, k_head_total, v_head_total, k_region_halfs,
+                                           v_region_halfs, overflow_flag);
+}
+
+int mustafar_cache_gather_hd(void* stream, const mustafar_cache_view* dst, const mustafar_cache_view* first, int first_tokens,
+                             const mustafar_cache_view* pieces, int n_pieces, int Bp, int D)
+{
+    if (D != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    return mustafar_hd64::cache_gather(static_cast<hipStream_t>(stream), dst, first, first_tokens, pieces, n_pieces, Bp);
+}
+
 int mustafar_cache_rehouse(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens,
                            int64_t stream_halfs)
 {

@@ -39,6 +39,14 @@ int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const must
 int trigger_compress_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
                            int64_t k_region_halfs, int64_t v_region_halfs);
 int trigger_finish_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int len, int drop);
+// a prefill in 256-token chunks: ONE launch, raw rows -> t / 256 extents per side in a staging of equally spaced extents; and the gather of
+// such pieces (behind an optional first cache) into one reference-layout cache: ONE launch, lengths read on the device
+int prefill_compress(hipStream_t st, const void* k_x, const void* v_x, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
+                     const mustafar_cache_view* k_stage, const mustafar_cache_view* v_stage, int64_t k_chunk_bytes, int64_t v_chunk_bytes,
+                     mustafar_cache_view* k_pieces, mustafar_cache_view* v_pieces, int64_t* k_head_total, int64_t* v_head_total,
+                     int64_t k_region_halfs, int64_t v_region_halfs, int32_t* overflow_flag);
+int cache_gather(hipStream_t st, const mustafar_cache_view* dst, const mustafar_cache_view* first, int first_tokens,
+                 const mustafar_cache_view* pieces, int n_pieces, int Bp);
 
 }  // namespace mustafar_hd64
 

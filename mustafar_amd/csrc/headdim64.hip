@@ -294,14 +294,13 @@ struct ExtSide {
     int kth;
 };
 
-__global__ __launch_bounds__(256) void hd64_extent_compress_kernel(ExtSide ks, ExtSide vs, int64_t head_stride, int32_t* __restrict__ flag)
+// The body both compression kernels share: 256 raw rows of head h at `rows` -> that head's part of the extent `s` describes.
+__device__ __forceinline__ void compress_256_rows(const ExtSide& s, const uint16_t* rows, int h, bool key, int32_t* __restrict__ flag)
 {
     __shared__ int32_t s_tot[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = blockIdx.x;
-    const bool key = blockIdx.y == 0;
-    const ExtSide& s = key ? ks : vs;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t w[32];
-    load_row(reinterpret_cast<const uint4*>(s.x + (int64_t)h * head_stride + (int64_t)(wave * 64 + lane) * kD), w);
+    load_row(reinterpret_cast<const uint4*>(rows + (int64_t)(wave * 64 + lane) * kD), w);
     if (s.kth > 0) prune_row(w, row_threshold(w, s.kth));
     uint64_t mine = 0;
     if (key) {
@@ -364,6 +363,108 @@ __global__ __launch_bounds__(256) void hd64_extent_compress_kernel(ExtSide ks, E
         }
         for (; n < 2 * own; n++) dst[n] = 0;
     }
+}
+
+__global__ __launch_bounds__(256) void hd64_extent_compress_kernel(ExtSide ks, ExtSide vs, int64_t head_stride, int32_t* __restrict__ flag)
+{
+    const int h = blockIdx.x;
+    const bool key = blockIdx.y == 0;
+    const ExtSide& s = key ? ks : vs;
+    compress_256_rows(s, s.x + (int64_t)h * head_stride, h, key, flag);
+}
+
+// ------------------------------------------------------------------------------------------------ a prefill in 256-token chunks
+// RAW rows [0, 256 n) of every head -> n finished extents per side (mustafar_prefill_compress_hd).  grid (kv head, chunk, side): the
+// trigger's body on chunk c's rows, x + h * head_stride + c * 256 * 64, into extent c of the staging -- every array of chunk c lies
+// c * chunk_bytes behind chunk 0's, its head totals at head_total + c * B'.  Each chunk is an extent of its own (offsets from 0), so
+// here too no workgroup waits for another one.  Head 0's workgroup lists the chunk's view in entry c of the side's device table (or
+// nullptr), which is what hd64_gather_kernel reads.
+__device__ __forceinline__ ExtSide chunk_of(const ExtSide& s, int c, int64_t chunk_bytes, int Bp)
+{
+    ExtSide r = s;
+    const int64_t by = (int64_t)c * chunk_bytes;
+    r.bmp = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(s.bmp) + by);
+    r.idx = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(s.idx) + by);
+    r.nz = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(s.nz) + by);
+    r.nz_offset = s.nz_offset ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(s.nz_offset) + by) : nullptr;
+    r.head_total = s.head_total + (int64_t)c * Bp;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void hd64_prefill_compress_kernel(ExtSide ks, ExtSide vs, int64_t head_stride, int64_t k_chunk_bytes,
+                                                                    int64_t v_chunk_bytes, mustafar_cache_view* k_pieces,
+                                                                    mustafar_cache_view* v_pieces, int32_t* __restrict__ flag)
+{
+    const int h = blockIdx.x, c = blockIdx.y, Bp = gridDim.x;
+    const bool key = blockIdx.z == 0;
+    const ExtSide s = chunk_of(key ? ks : vs, c, key ? k_chunk_bytes : v_chunk_bytes, Bp);
+    mustafar_cache_view* pieces = key ? k_pieces : v_pieces;
+    if (h == 0 && threadIdx.x == 0 && pieces)
+        pieces[c] = mustafar_cache_view{s.bmp, s.nz, s.idx, s.nz_offset, s.bmp_stride, s.idx_stride, (int64_t)s.nz_stride};
+    compress_256_rows(s, s.x + (int64_t)h * head_stride + (int64_t)c * 256 * kD, h, key, flag);
+}
+
+// ------------------------------------------------------------------------------------------------ gather
+// 256-token pieces, each with offsets relative to itself, -> ONE reference-layout cache (mustafar_cache_gather_hd): the end of a chunked
+// prefill and ExtentCache64.consolidate().  grid (piece, kv head), 256 threads, thread = token.  Pieces [0, n_first) are the 256-token
+// slices of the optional first view (a whole cache: its offsets already count from the head's start, shift 0); piece n_first + i is entry
+// i of the DEVICE table.  A table piece starts where the stream in front of it ends: the first view's last offset + the last offsets of
+// entries [0, i), one or two per thread and a workgroup sum -- read here, nothing on the host, no workgroup waits for another.  Bitmaps
+// are copied, offsets are copied + shift (piece 0 writes the head's entry 0), the stream moves as 16-byte pieces: every tile is padded
+// to 8 halfs, so every offset is a multiple of 16 bytes behind a head start that is one.
+struct GatherArgs {
+    mustafar_cache_view dst, first;      // strides resolved by the host (no zeros left in bmp / idx strides)
+    const mustafar_cache_view* pieces;
+    int first_tokens, n_pieces;
+};
+
+__device__ __forceinline__ const uint4* head_stream(const mustafar_cache_view& v, int h)
+{
+    const int64_t off = v.nz_head_stride ? (int64_t)h * v.nz_head_stride : (int64_t)v.nz_offset[h];
+    return static_cast<const uint4*>(v.nz) + off;
+}
+
+__global__ __launch_bounds__(256) void hd64_gather_kernel(GatherArgs a)
+{
+    __shared__ uint32_t s_sum[4];
+    const int p = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const int n_first = a.first_tokens >> 8;
+    const uint64_t* sb;
+    const uint32_t* si;
+    const uint4* sz;
+    uint32_t shift = 0;
+    if (p < n_first) {   // (workgroup-uniform)
+        sb = a.first.bmp + (int64_t)h * a.first.bmp_head_stride + p * 256;
+        si = a.first.idx + (int64_t)h * a.first.idx_head_stride + p * 256;
+        sz = head_stream(a.first, h);
+    } else {
+        const int i = p - n_first;
+        uint32_t part = 0;
+        for (int j = t; j < i; j += 256) {
+            const mustafar_cache_view e = a.pieces[j];
+            part += e.idx[(int64_t)h * (e.idx_head_stride ? e.idx_head_stride : 257) + 256];
+        }
+        if (t == 0 && n_first) part += a.first.idx[(int64_t)h * a.first.idx_head_stride + a.first_tokens];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+        if ((t & 63) == 0) s_sum[t >> 6] = part;
+        __syncthreads();
+        shift = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        const mustafar_cache_view e = a.pieces[i];
+        sb = e.bmp + (int64_t)h * (e.bmp_head_stride ? e.bmp_head_stride : 256);
+        si = e.idx + (int64_t)h * (e.idx_head_stride ? e.idx_head_stride : 257);
+        sz = head_stream(e, h);
+    }
+    const int64_t tok0 = (int64_t)p * 256;
+    uint32_t* di = a.dst.idx + (int64_t)h * a.dst.idx_head_stride + tok0;
+    a.dst.bmp[(int64_t)h * a.dst.bmp_head_stride + tok0 + t] = sb[t];
+    di[t + 1] = si[t + 1] + shift;
+    const uint32_t i0 = si[0], i1 = si[256];   // half2 units, multiples of 4
+    if (p == 0 && t == 0) di[0] = i0 + shift;   // (0: a cache's and an extent's offsets start there)
+    const uint4* src = sz + (i0 >> 2);
+    uint4* dst = const_cast<uint4*>(head_stream(a.dst, h)) + ((i0 + shift) >> 2);
+    const int n16 = (int)((i1 - i0) >> 2);   // <= 256 tiles x 64 halfs / 8 = 2048
+    for (int k = t; k < n16; k += 256) dst[k] = src[k];
 }
 
 // The tail of a trigger at D = 64 (mustafar_trigger_finish_batch_hd): one workgroup lists the extent's view in its slot of the device
@@ -881,6 +982,52 @@ int trigger_compress_batch(hipStream_t st, int n, const mustafar_trigger_item* i
                          it.v_dst.idx_head_stride ? it.v_dst.idx_head_stride : 257, v_region_halfs, (uint32_t)it.v_dst.nz_head_stride, kth_v};
         hd64_extent_compress_kernel<<<dim3(Bp, 2), 256, 0, st>>>(ks, vs, head_stride, it.overflow_flag);
     }
+    return (int)hipGetLastError();
+}
+
+int prefill_compress(hipStream_t st, const void* k_x, const void* v_x, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
+                     const mustafar_cache_view* k_stage, const mustafar_cache_view* v_stage, int64_t k_chunk_bytes, int64_t v_chunk_bytes,
+                     mustafar_cache_view* k_pieces, mustafar_cache_view* v_pieces, int64_t* k_head_total, int64_t* v_head_total,
+                     int64_t k_region_halfs, int64_t v_region_halfs, int32_t* overflow_flag)
+{
+    if (Bp < 1 || t < 256 || (t & 255) || t > kMaxExtents * 256 || head_stride < (int64_t)t * kD || (head_stride & 7) || kth_k < 0 ||
+        kth_k > kD || kth_v < 0 || kth_v > kD)
+        return MUSTAFAR_EINVAL;
+    if (!k_x || !v_x || !aligned16(k_x) || !aligned16(v_x) || !k_stage || !v_stage || !k_head_total || !v_head_total || !overflow_flag)
+        return MUSTAFAR_EINVAL;
+    // chunk c's arrays lie c * chunk_bytes behind chunk 0's: the stream regions stay 16-byte aligned, the other arrays 8 / 4
+    if (k_chunk_bytes <= 0 || (k_chunk_bytes & 15) || v_chunk_bytes <= 0 || (v_chunk_bytes & 15)) return MUSTAFAR_EINVAL;
+    if (!extent_view_ok(*k_stage, Bp, k_region_halfs) || !extent_view_ok(*v_stage, Bp, v_region_halfs)) return MUSTAFAR_EINVAL;
+    const ExtSide ks{static_cast<const uint16_t*>(k_x), k_stage->bmp, k_stage->idx, static_cast<uint16_t*>(k_stage->nz), k_stage->nz_offset,
+                     k_head_total, k_stage->bmp_head_stride ? k_stage->bmp_head_stride : 256,
+                     k_stage->idx_head_stride ? k_stage->idx_head_stride : 257, k_region_halfs, (uint32_t)k_stage->nz_head_stride, kth_k};
+    const ExtSide vs{static_cast<const uint16_t*>(v_x), v_stage->bmp, v_stage->idx, static_cast<uint16_t*>(v_stage->nz), v_stage->nz_offset,
+                     v_head_total, v_stage->bmp_head_stride ? v_stage->bmp_head_stride : 256,
+                     v_stage->idx_head_stride ? v_stage->idx_head_stride : 257, v_region_halfs, (uint32_t)v_stage->nz_head_stride, kth_v};
+    hd64_prefill_compress_kernel<<<dim3(Bp, t / 256, 2), 256, 0, st>>>(ks, vs, head_stride, k_chunk_bytes, v_chunk_bytes, k_pieces, v_pieces,
+                                                                       overflow_flag);
+    return (int)hipGetLastError();
+}
+
+int cache_gather(hipStream_t st, const mustafar_cache_view* dst, const mustafar_cache_view* first, int first_tokens,
+                 const mustafar_cache_view* pieces, int n_pieces, int Bp)
+{
+    if (!dst || Bp < 1 || first_tokens < 0 || (first_tokens & 255) || n_pieces < 0 || n_pieces > kMaxExtents || (first_tokens > 0) != (first != nullptr) ||
+        (n_pieces > 0 && !pieces) || first_tokens / 256 + n_pieces < 1 || first_tokens / 256 + n_pieces > 65535)
+        return MUSTAFAR_EINVAL;
+    const int64_t tokens = (int64_t)first_tokens + 256 * (int64_t)n_pieces;
+    GatherArgs a{*dst, first ? *first : mustafar_cache_view{}, pieces, first_tokens, n_pieces};
+    mustafar_cache_view* v[2] = {&a.dst, &a.first};
+    const int64_t held[2] = {tokens, first_tokens};
+    for (int i = 0; i < (first ? 2 : 1); i++) {
+        if (!v[i]->bmp || !v[i]->idx || !v[i]->nz || !aligned16(v[i]->nz) || v[i]->nz_head_stride < 0 ||
+            (int64_t)Bp * v[i]->nz_head_stride > 0xffffffffll || (!v[i]->nz_head_stride && !v[i]->nz_offset))
+            return MUSTAFAR_EINVAL;
+        if (!v[i]->bmp_head_stride) v[i]->bmp_head_stride = held[i];
+        if (!v[i]->idx_head_stride) v[i]->idx_head_stride = held[i] + 1;
+        if (v[i]->bmp_head_stride < held[i] || v[i]->idx_head_stride < held[i] + 1) return MUSTAFAR_EINVAL;
+    }
+    hd64_gather_kernel<<<dim3(first_tokens / 256 + n_pieces, Bp), 256, 0, st>>>(a);
     return (int)hipGetLastError();
 }
 

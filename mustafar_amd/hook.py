@@ -80,6 +80,10 @@ class MustafarConfig:
     # head_dim 64, api="fused", arena=False only: the compressed cache grows by 256-token extents (cache64.py) instead of being
     # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
     hd64_extents: bool = False
+    # head_dim 64, api="fused", arena=False only: the prefill is compressed from the raw K / V rows in 256-token chunks and gathered into
+    # the reference-layout arrays (compression.compress_raw_pair_hd64: one read of the rows, one host wait) instead of prune + two
+    # conversions.  The same tensors, bit for bit; off by default
+    hd64_raw_prefill: bool = False
 
 
 def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
@@ -209,6 +213,10 @@ class MustafarAttention:
             raise ValueError("hd64_extents is the head_dim 64 cache that grows by extents: it needs "
                              f"MustafarConfig(head_dim=64, api='fused', arena=False) (got head_dim={config.head_dim}, api={config.api!r}, "
                              f"arena={config.arena})")
+        if config.hd64_raw_prefill and not (config.head_dim == 64 and config.api == "fused" and not config.arena):
+            raise ValueError("hd64_raw_prefill is the head_dim 64 prefill compressed from the raw rows: it needs "
+                             f"MustafarConfig(head_dim=64, api='fused', arena=False) (got head_dim={config.head_dim}, api={config.api!r}, "
+                             f"arena={config.arena})")
         self.Reduction_Workspace = None   # model :658: a 1-element fp16 tensor shared by all layers
 
     # ---- pruning (model :77-153) -----------------------------------------------------------------------------
@@ -248,6 +256,17 @@ class MustafarAttention:
             k_compressed, v_compressed = CompressedArena.from_raw_pair(
                 ks, vs, compressed_length, compression.kth_from_sparsity(self.cfg.k_sparsity, D),
                 compression.kth_from_sparsity(self.cfg.v_sparsity, D), None, self._slack())
+            del ks, vs
+            k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()             # :427
+            v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()           # :435
+        elif compressed_length != 0 and self.cfg.hd64_raw_prefill:
+            # head_dim 64 from the raw rows: one chunked compression launch, one host wait, one gather per side (transposed views are
+            # made contiguous first, as for the arena above)
+            ks = key_states if key_states.is_contiguous() else key_states.contiguous()
+            vs = value_states if value_states.is_contiguous() else value_states.contiguous()
+            k_compressed, v_compressed = compression.compress_raw_pair_hd64(
+                ks, vs, compressed_length, compression.kth_from_sparsity(self.cfg.k_sparsity, D),
+                compression.kth_from_sparsity(self.cfg.v_sparsity, D))
             del ks, vs
             k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()             # :427
             v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()           # :435

@@ -15,6 +15,12 @@ triggers), timed two ways, alternated A B A B in one process:
 Each reports tok_s over the whole generate (host wall time, device-synchronised at the end) and trigger_step_ms, the mean wall time of a
 step that fires a trigger (recapture included for the tuple way); and ext_kernel_us / plain_kernel_us: the decode launch of the EXT
 instantiation against the plain one at the same T with no extent listed.
+--prefill (default off; --prefill-runs N, default 21) adds a prefill leg at L = 8192, one layer, alternated A B A B in one process behind
+a warm-up of 3 runs each, median wall time of N runs per way, every run ended by a device synchronise:
+  prefill_old_us    the parent's route: prune + two conversions of K and V (build_cache; its host waits included)
+  prefill_raw_us    MustafarConfig(hd64_raw_prefill=True): compression.compress_raw_pair_hd64 (its one wait included) + the windows
+and consolidate() of one side at a base of 7936 tokens plus 3 and plus 32 extents, on the device and through to_reference(), the same way.
+The results of both ways are compared bit for bit before anything is timed.
 Needs an MI355X; it does not fall back to anything.  Usage: python tools/bench_headdim64.py [--lengths 4096,8192,32768] [--steps 64]
 """
 from __future__ import annotations
@@ -216,13 +222,75 @@ def generate(L: int, n_tokens: int, extents: bool, dev, kernel_ab: bool = False)
     return res
 
 
+def _same_cache(a, b) -> bool:
+    return torch.equal(a[0].reshape(-1), b[0].reshape(-1)) and torch.equal(a[1].reshape(-1), b[1].reshape(-1)) and torch.equal(a[3], b[3]) and \
+        torch.equal(a[2].flat.view(torch.int16), b[2].flat.view(torch.int16))
+
+
+def _ab_median_us(fa, fb, runs: int, warm: int = 3):
+    """Median wall time (us) of fa and fb, alternated A B A B behind `warm` runs of each; every run ends in a device synchronise."""
+    def once(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+    for _ in range(warm):
+        once(fa)
+        once(fb)
+    ta, tb = [], []
+    for _ in range(runs):
+        ta.append(once(fa))
+        tb.append(once(fb))
+    return sorted(ta)[runs // 2], sorted(tb)[runs // 2]
+
+
+def prefill_leg(dev, runs: int) -> dict:
+    from mustafar_amd.cache64 import ExtentCache64
+    from mustafar_amd.compression import kth_from_sparsity
+    L, R = 8192, 32
+    cfg = dict(num_attention_heads=HQ, num_key_value_heads=HKV, head_dim=D, k_sparsity=S, v_sparsity=S, api="fused", residual_length=R)
+    old, raw = MustafarAttention(MustafarConfig(**cfg)), MustafarAttention(MustafarConfig(hd64_raw_prefill=True, **cfg))
+    g = torch.Generator(device=dev).manual_seed(8192)
+    K = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+    V = torch.randn((BATCH, HKV, L, D), generator=g, device=dev).half()
+    po, pr = old.build_cache(K, V), raw.build_cache(K, V)
+    assert po[4] == pr[4] == 7936 and _same_cache(po[0], pr[0]) and _same_cache(po[2], pr[2]), "the two prefill routes disagree"
+    assert torch.equal(po[1], pr[1]) and torch.equal(po[3], pr[3])
+    del po, pr
+    t_old, t_raw = _ab_median_us(lambda: old.build_cache(K, V), lambda: raw.build_cache(K, V), runs)
+    res = {"L": L, "runs": runs, "prefill_old_us": round(t_old, 1), "prefill_raw_us": round(t_raw, 1), "prefill_old_over_raw": round(t_old / t_raw, 3)}
+    kth = kth_from_sparsity(S, D)
+    Bp = BATCH * HKV
+    for n_ext in (3, 32):
+        past = raw.build_cache(K[:, :, :7936 + R].contiguous(), V[:, :, :7936 + R].contiguous())
+        kc, vc = ExtentCache64(past[0], "key", Bp, 7936), ExtentCache64(past[2], "value", Bp, 7936)
+        for i in range(n_ext):
+            kb = torch.randn((BATCH, HKV, 256 + R, D), generator=g, device=dev).half()
+            vb = torch.randn((BATCH, HKV, 256 + R, D), generator=g, device=dev).half()
+            ExtentCache64.append_extents([(kc, vc)], [(kb, vb)], kth, kth, 256 + R)
+        a, b = kc.consolidate(), kc.consolidate(via_reference=True)
+        assert a.tokens == b.tokens == 7936 + 256 * n_ext and _same_cache(a.base, b.base), "the two consolidations disagree"
+        del a, b
+        t_dev, t_ref = _ab_median_us(lambda: kc.consolidate(), lambda: kc.consolidate(via_reference=True), runs)
+        res[f"consolidate_{n_ext}_device_us"] = round(t_dev, 1)
+        res[f"consolidate_{n_ext}_reference_us"] = round(t_ref, 1)
+        del kc, vc, past
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lengths", default="4096,8192,32768")
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--generate", type=int, default=0)
     ap.add_argument("--gen-length", type=int, default=8192)
+    ap.add_argument("--prefill", action="store_true")
+    ap.add_argument("--prefill-runs", type=int, default=21)
     args = ap.parse_args()
+    if args.prefill_runs < 20:
+        raise SystemExit("--prefill-runs: at least 20 runs per way")
     if not torch.cuda.is_available():
         raise SystemExit("bench_headdim64 needs a GPU")
     dev = torch.device("cuda:0")
@@ -240,6 +308,8 @@ def main():
                 runs.append(generate(args.gen_length, args.generate, ext, dev, kernel_ab=rep == 0))
                 torch.cuda.empty_cache()
         out["generate"] = {"L": args.gen_length, "tokens": args.generate, "runs": runs}
+    if args.prefill:
+        out["prefill"] = prefill_leg(dev, args.prefill_runs)
     print(json.dumps(out))
 
 
