@@ -399,6 +399,49 @@ int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view
                                          int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim);
 
 /*
+ * Partial attention (ABI 110): the log-sum-exp of a fused decode call, window-less calls, and the merge of partial states.
+ *
+ * mustafar_decode_attention_lse_hd / mustafar_decode_attention_extents_lse_hd: every argument of mustafar_decode_attention_hd /
+ *   mustafar_decode_attention_extents_hd, then `lse`: fp32 [Batch_Size] out, or NULL.
+ *     lse[bh] = M + log(sum_t exp(x_t - M)),  M = max_t x_t, over every token the call attends to (compressed and window), x_t being what
+ *     the softmax of that call sees: fp16(fp16(score) / sqrt d), with the hook's mask added and clamped where a mask is given.
+ *   It is written by the row kernel that merges the slabs, from the (max, sum) pairs it reduces anyway: no further launch, no second
+ *   pass.  `out` is what the plain entry point writes, bit for bit.  lse == NULL: the launches and the bits of the plain entry point
+ *   (the row kernels' instantiation without an LSE); mustafar_last_decode_choice() is set as there.
+ *   The extents form with T == T_base (no T_device) reads the two base views alone, strides included: the form for one
+ *   mustafar_cache_view per side (D = 128: any T_base > 0 that is a multiple of 256).
+ *   Window-less calls, accepted by these two entry points only: window_len == 0 && window_capacity == 0 with k_window, v_window, k_new,
+ *   v_new and window_len_extra all NULL; T > 0 and ld_scores >= T.  No window workgroups and no window slabs are launched; mask
+ *   columns are [0, T).  Any other mixture of zero and non-zero window arguments: MUSTAFAR_EINVAL.
+ *   D = 128: the LSE (and a window-less call) is served by the one-pass forms -- every group count and engine, extents, T_device, the
+ *   small, super-block and lean-pair kernels, all four row-kernel variants.  A call that would run the two-launch form returns
+ *   MUSTAFAR_EINVAL before any launch when lse != NULL: T == 0, ld_scores % 32 != 0, MUSTAFAR_FLAG_TWO_LAUNCH, or a process default of
+ *   two launches.  D = 64: every shape the kernel takes (T == 0, empty window chunks, slabs of weight zero behind *T_device).
+ *
+ * mustafar_merge_attention_states: ONE launch.  Part i = attention over a token set of its own: normalised outputs fp16
+ *   [Batch_Size, head_dim] at outs + i * out_part_stride (halfs), LSEs fp32 [Batch_Size] at lses + i * lse_part_stride (floats).
+ *   Per row, in fp32:  M = max_i lse_i;  w_i = lse_i == -inf ? 0 : exp(lse_i - M);  out = fp16(sum_i w_i out_i / sum_i w_i);
+ *   lse_out = M + log(sum_i w_i).  Every part empty: out = 0, lse_out = -inf.  1 <= n_parts <= 64; head_dim 64 or 128; lse_out may be
+ *   NULL; strides at least a part's size when n_parts > 1; `out` must not lie inside the parts (nor lse_out inside the LSEs).
+ */
+int mustafar_decode_attention_lse_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                                     const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                                     const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                                     const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                                     void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                     const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                     int heads_per_mask_row, uint32_t flags, int head_dim, float* lse);
+int mustafar_decode_attention_extents_lse_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                             const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                             const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                             int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                                             int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                             const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                             int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim, float* lse);
+int mustafar_merge_attention_states(void* stream, const void* outs, int64_t out_part_stride, const float* lses, int64_t lse_part_stride,
+                                    int n_parts, int Batch_Size, int head_dim, void* out, float* lse_out);
+
+/*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
  * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
  *

@@ -532,6 +532,11 @@ struct NoExt {};
 template <bool EXT> struct ExtOf { typedef NoExt type; };
 template <> struct ExtOf<true> { typedef ExtArgs type; };
 static_assert(sizeof(mustafar_cache_view) == 56, "the EXT kernel reads a table entry as seven 8-byte words");
+// The row kernel's LSE output, carried the same way: the instantiation without one takes an empty struct and stays what it was.
+struct LseArg { float* ptr; };
+struct NoLse {};
+template <bool LSE> struct LseOf { typedef NoLse type; };
+template <> struct LseOf<true> { typedef LseArg type; };
 
 // One side of a 64-token block as the phases read it: bitmaps and offsets of its 64 tiles (scalar loads), the head's stream.
 struct BlockRef {
@@ -745,9 +750,11 @@ __global__ __launch_bounds__(64) void hd64_decode_kernel(const uint64_t* __restr
 }
 
 // out[bh, c] = fp16( sum_s w_s o_s[c] / sum_s w_s l_s ),  w_s = exp(m_s - max m) (0 for an empty slab).  One workgroup per row, four waves
-// over the slabs (lane = channel), folded through LDS.
+// over the slabs (lane = channel), folded through LDS.  LSE: lse[bh] = max m + log(sum_s w_s l_s), the log-sum-exp of the row's scores as the
+// softmax saw them, from the (max, sum) pairs reduced here anyway (-inf for a row whose slabs are all empty).
+template <bool LSE>
 __global__ __launch_bounds__(256) void hd64_finish_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, int S, int BH,
-                                                          h16* __restrict__ out)
+                                                          h16* __restrict__ out, typename LseOf<LSE>::type lse)
 {
     __shared__ float part[4][kD];
     const int bh = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -767,7 +774,9 @@ __global__ __launch_bounds__(256) void hd64_finish_kernel(const float* __restric
     __syncthreads();
     if (wave == 0) {
         const float o = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-        out[(int64_t)bh * kD + lane] = (h16)(o / (dens[0] + dens[1] + dens[2] + dens[3]));
+        const float d = dens[0] + dens[1] + dens[2] + dens[3];
+        out[(int64_t)bh * kD + lane] = (h16)(o / d);
+        if constexpr (LSE) { if (lane == 0) lse.ptr[bh] = d > 0.f ? Mx + __logf(d) : -INFINITY; }
     }
 }
 
@@ -847,14 +856,19 @@ int launch_decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const
                   const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
                   void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
                   void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-                  const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, const ExtArgs* ext)
+                  const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, const ExtArgs* ext,
+                  float* lse, bool lse_entry)
 {
     if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
-    if (T < 0 || (T & 63) || groups < 1 || groups > 8 || Batch_Size < 1 || Batch_Size % groups || window_len < 1 ||
+    // A window-less call (the entry points with an LSE only): no window argument at all and at least one compressed token.  Its launch
+    // has no window workgroups and no window slabs; any other mixture of zero and non-zero window arguments is refused.
+    const bool no_window = lse_entry && window_len == 0 && window_capacity == 0 && !k_window && !v_window && !k_new && !v_new &&
+                           !window_len_extra && T > 0;
+    if (T < 0 || (T & 63) || groups < 1 || groups > 8 || Batch_Size < 1 || Batch_Size % groups || (window_len < 1 && !no_window) ||
         window_len > window_capacity || window_capacity > kMaxWindow ||
         ld_scores < T + (window_len_extra ? window_capacity : window_len) || (ld_scores & 7) || Split_K < 1 || !(sqrt_d > 0.f))
         return MUSTAFAR_EINVAL;
-    if (!q || !k_window || !v_window || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    if (!q || ((!k_window || !v_window) && !no_window) || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
     // window rows (and the new rows) are read as 16-byte pieces
     if (!aligned16(k_window) || !aligned16(v_window) || (k_new && !aligned16(k_new))) return MUSTAFAR_EINVAL;
     if (T > 0 && (!k_bmp || !k_nz || !k_idx || !v_bmp || !v_nz || !v_idx)) return MUSTAFAR_EINVAL;
@@ -897,8 +911,12 @@ int launch_decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const
     }
 #undef MUSTAFAR_HD64
 #undef MUSTAFAR_HD64_L
-    hipExtLaunchKernelGGL(hd64_finish_kernel, dim3(Batch_Size), dim3(256), 0, st, e2, e3, 0, ws_o, ws_ml, S1 + nchunks, Batch_Size,
-                          static_cast<h16*>(out));
+    if (lse)
+        hipExtLaunchKernelGGL(hd64_finish_kernel<true>, dim3(Batch_Size), dim3(256), 0, st, e2, e3, 0, ws_o, ws_ml, S1 + nchunks, Batch_Size,
+                              static_cast<h16*>(out), LseArg{lse});
+    else
+        hipExtLaunchKernelGGL(hd64_finish_kernel<false>, dim3(Batch_Size), dim3(256), 0, st, e2, e3, 0, ws_o, ws_ml, S1 + nchunks, Batch_Size,
+                              static_cast<h16*>(out), NoLse{});
     return (int)hipGetLastError();
 }
 
@@ -916,11 +934,11 @@ int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32
            const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
            void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
            void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev)
+           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, float* lse, bool lse_entry)
 {
     return launch_decode(st, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new, window_len,
                          window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra,
-                         attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr);
+                         attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr, lse, lse_entry);
 }
 
 int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
@@ -928,7 +946,7 @@ int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const must
                    const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
                    void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
                    const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, const int32_t* T_device, hipEvent_t* ev,
-                   bool* ran_extents)
+                   bool* ran_extents, float* lse, bool lse_entry)
 {
     *ran_extents = false;
     if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255) || (T - T_base) / 256 > kMaxExtents)
@@ -940,7 +958,8 @@ int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const must
             return MUSTAFAR_EINVAL;
         return launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx, v_base->nz_offset,
                              q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T,
-                             Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr);
+                             Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr, lse,
+                             lse_entry);
     }
     if (!k_extents || !v_extents) return MUSTAFAR_EINVAL;
     const mustafar_cache_view* b[2] = {k_base, v_base};
@@ -955,7 +974,7 @@ int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const must
     const int err = launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx,
                                   v_base->nz_offset, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
                                   workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                  heads_per_mask_row, ev, &e);
+                                  heads_per_mask_row, ev, &e, lse, lse_entry);
     *ran_extents = err == 0;
     return err;
 }

@@ -1698,9 +1698,19 @@ constexpr int kMaxSlabs = 512;
 // Every wave works out the row's maximum, the slab weights and the denominator for ITSELF (lane = slab, DPP reductions, its own
 // LDS copy of the weights): no barrier before the weighted sum, one behind it to fold the two slab parities.  (Round 2 reduced
 // across the workgroup: five barriers in a kernel that is all latency; 5.4 -> 4.x us per layer at c3.)
-template <int KPER = kMaxSlabs / 64>   // slabs per lane of the weight pass: 64 * KPER >= S (round 5: c3's 36 slabs run the KPER = 1 text)
+// LSE (both row kernels): the row's log-sum-exp, max_s m_s + log(sum_s w_s l_s), from the maximum and denominator the kernel has anyway --
+// lse[bh] is the log of the softmax denominator of the scores as the softmax saw them (fp16(fp16(score) / sqrt d), masked), so that the
+// output can be merged with attention over other tokens (mustafar_merge_attention_states).  The slab sums arrive unscaled: the dot2
+// engine's 2^15 leaves them where a workgroup writes its slab (kOut / scale_l in the three one-pass kernels).  The instantiation
+// without an LSE takes an empty struct in the pointer's place and is the kernel it was.
+struct LseArg { float* ptr; };
+struct NoLse {};
+template <bool LSE> struct LseOf { typedef NoLse type; };
+template <> struct LseOf<true> { typedef LseArg type; };
+
+template <int KPER = kMaxSlabs / 64, bool LSE = false>   // slabs per lane of the weight pass: 64 * KPER >= S (round 5: c3's 36 slabs run the KPER = 1 text)
 __global__ __launch_bounds__(256) void onepass_finish_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                                             int S, h16* __restrict__ out, int BH)
+                                                             int S, h16* __restrict__ out, int BH, typename LseOf<LSE>::type lse)
 {
     __shared__ float wgt_all[4][64 * KPER];
     __shared__ float part[kD];
@@ -1781,13 +1791,15 @@ __global__ __launch_bounds__(256) void onepass_finish_kernel(const float* __rest
     if (par) part[c] = s;
     __syncthreads();
     if (!par) out[(int64_t)bh * kD + c] = (h16)((s + part[c]) / denom);
+    if constexpr (LSE) { if (tid == 0) lse.ptr[bh] = M + __logf(denom); }
 }
 
 // The row kernel for rows of at most 64 slabs (round 5; every BASELINE shape up to 8k x batch 8): ONE thread per channel walks all the slabs of
 // the row -- no parity halves, no LDS, no barrier -- with the first kEarly1 slabs' outputs requested before the weights are known and each
 // weight taken from the lane that computed it (v_readlane; a slab per lane).  Two waves per row, each working the weights out for itself.
+template <bool LSE = false>
 __global__ __launch_bounds__(128) void onepass_finish1_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, int S,
-                                                              h16* __restrict__ out, int BH)
+                                                              h16* __restrict__ out, int BH, typename LseOf<LSE>::type lse)
 {
     constexpr int kEarly1 = 40;   // slab loads in flight per thread before the weights are known: covers c3's 36-slab rows whole (profiles/r05_probes.txt; other depths were not measured)
     static_assert(kEarly1 <= 64 && kEarly1 % 4 == 0, "a slab per lane");
@@ -1817,6 +1829,52 @@ __global__ __launch_bounds__(128) void onepass_finish1_kernel(const float* __res
     }
     for (int k = kEarly1; k < S; k++) s0 += wk(k) * src[(int64_t)k * total];   // (S <= 64; wave-uniform k)
     out[(int64_t)bh * kD + c] = (h16)(((s0 + s1) + (s2 + s3)) / denom);
+    if constexpr (LSE) { if (c == 0) lse.ptr[bh] = M + __logf(denom); }
+}
+
+// ------------------------------------------------------------------------------------------------ merge of partial attention states
+// mustafar_merge_attention_states: n <= 64 parts, each the normalised fp16 output and the fp32 LSE of attention over its own tokens, into the
+// attention over all of them.  Per row: M = max_i lse_i, w_i = exp(lse_i - M) (0 for an empty part, lse = -inf),
+// out = fp16(sum_i w_i out_i / sum_i w_i) in fp32, lse = M + log(sum_i w_i).  A wave per row, kMergeRows rows per workgroup: the launch is all
+// latency (256 rows at the bench shape), so the first kMergeEarly parts' rows are requested before the LSEs are loaded and reduced
+// (lane = part, DPP reductions, as onepass_finish1_kernel with lane = slab) and every weight is read from the lane that computed it.
+// Lane = channel (D = 128: channels lane and lane + 64).  No LDS, no barrier.
+constexpr int kMergeRows = 4, kMergeEarly = 4, kMaxMergeParts = 64;
+template <int D>
+__global__ __launch_bounds__(64 * kMergeRows) void merge_states_kernel(const h16* __restrict__ outs, int64_t out_stride,
+                                                                        const float* __restrict__ lses, int64_t lse_stride, int n, int BH,
+                                                                        h16* __restrict__ out, float* __restrict__ lse_out)
+{
+    constexpr int NC = D / 64;
+    const int lane = threadIdx.x & 63;
+    const int bh = blockIdx.x * kMergeRows + (int)(threadIdx.x >> 6);
+    if (bh >= BH) return;   // (whole waves; nothing below crosses waves)
+    const h16* src = outs + (int64_t)bh * D + lane;
+    float v[kMergeEarly][NC];
+#pragma unroll
+    for (int i = 0; i < kMergeEarly; i++)
+#pragma unroll
+        for (int c = 0; c < NC; c++) v[i][c] = (i < n) ? (float)src[(int64_t)i * out_stride + 64 * c] : 0.f;
+    const float l = (lane < n) ? lses[(int64_t)lane * lse_stride + bh] : -INFINITY;
+    const float M = wave_max(l);
+    const float w = (l == -INFINITY) ? 0.f : __expf(l - M);   // (lanes >= n, empty parts: zero)
+    const float wsum = wave_sum(w);
+    auto wk = [&](int k) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, w), k)); };
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0.f;
+#pragma unroll
+    for (int i = 0; i < kMergeEarly; i++)
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] += wk(i) * v[i][c];
+    for (int i = kMergeEarly; i < n; i++) {   // (wave-uniform i)
+        const float wi = wk(i);
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] += wi * (float)src[(int64_t)i * out_stride + 64 * c];
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) out[(int64_t)bh * D + lane + 64 * c] = (h16)(wsum > 0.f ? acc[c] / wsum : 0.f);
+    if (lse_out && lane == 0) lse_out[bh] = wsum > 0.f ? M + __logf(wsum) : -INFINITY;
 }
 
 // ------------------------------------------------------------------------------------------------ one-pass decode, lean form (G = 4)
@@ -3659,7 +3717,7 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
 
 extern "C" {
 
-int mustafar_abi_version(void) { return 109; }   // 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
+int mustafar_abi_version(void) { return 110; }   // 110: mustafar_decode_attention_lse_hd, mustafar_decode_attention_extents_lse_hd, mustafar_merge_attention_states (the LSE of a fused decode, window-less calls, the merge of partial attention states); 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
 
 int Key_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const void* NZ, const uint32_t* idx,
                    const uint32_t* NZ_offset, const void* B, void* C, int M_Global, int N_Global, int K_Global,
@@ -3760,7 +3818,8 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
                      int ld_scores, void* out, void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups,
                      float sqrt_d, const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                      int heads_per_mask_row, uint32_t flags, const mustafar_cache_view* k_ext = nullptr,
-                     const mustafar_cache_view* v_ext = nullptr, int T_base = 0, const int32_t* T_device = nullptr)
+                     const mustafar_cache_view* v_ext = nullptr, int T_base = 0, const int32_t* T_device = nullptr, float* lse = nullptr,
+                     bool lse_entry = false)
 {
     const int groups = num_key_value_groups;
     const bool extents = k_ext != nullptr;   // (validated by mustafar_decode_attention_extents)
@@ -3773,11 +3832,18 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
     } override_(f_eng == 1 ? 0 : f_eng == 2 ? 1 : f_eng == 3 ? 2 : -1, f_str == 1 ? 0 : f_str == 2 ? 1 : -1);
     if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
     const MaskArg mask{static_cast<const h16*>(attention_mask), mask_row_stride, heads_per_mask_row > 0 ? heads_per_mask_row : 1};
-    if (T < 0 || (T & 63) || groups < 1 || Batch_Size < 1 || Batch_Size % groups || window_len < 1 ||
+    // A window-less call (the entry points with an LSE only): no window argument at all and at least one compressed token.  The one-pass
+    // launch then has no window workgroups (win_rows = 0) and no window slabs; any other mixture of zero and non-zero window arguments
+    // is refused, and so is the two-launch form, whose row kernels read the window themselves.
+    const bool no_window = lse_entry && window_len == 0 && window_capacity == 0 && !k_window && !v_window && !k_new && !v_new &&
+                           !window_len_extra && T > 0;
+    if (T < 0 || (T & 63) || groups < 1 || Batch_Size < 1 || Batch_Size % groups || (window_len < 1 && !no_window) ||
         window_len > window_capacity || window_capacity > kMaxWindow ||
         ld_scores < T + (window_len_extra ? window_capacity : window_len) || (ld_scores & 7) || Split_K < 1 || !(sqrt_d > 0.f))
         return MUSTAFAR_EINVAL;
-    if (!q || !k_window || !v_window || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    if (!q || ((!k_window || !v_window) && !no_window) || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    // an LSE comes from the one-pass forms' row kernels: a call that would run two launches is refused before anything is launched
+    if ((lse || no_window) && !(T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0)) return MUSTAFAR_EINVAL;
     if (T > 0 && (!kc.bmp || !kc.nz || !kc.idx || !kc.nz_offset || !vc.bmp || !vc.nz || !vc.idx || !vc.nz_offset)) return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? T_base : T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
     if (T > 0 && ((kc.bmp_head_stride && kc.bmp_head_stride < tiles) || (kc.idx_head_stride && kc.idx_head_stride < tiles + 1) ||
@@ -3890,18 +3956,25 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
 #undef MUSTAFAR_LP
 #undef MUSTAFAR_LL
         // (the row kernel's own start / stop timestamps go into the record's second event pair: mustafar_profile_end2)
-        if (NS + nchunks <= 64 && finish1())
-            hipExtLaunchKernelGGL(onepass_finish1_kernel, dim3(Batch_Size), dim3(128), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-        else if (NS + nchunks <= 64)
-            hipExtLaunchKernelGGL(onepass_finish_kernel<1>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-        else if (NS + nchunks <= 128)
-            hipExtLaunchKernelGGL(onepass_finish_kernel<2>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
-        else
-            hipExtLaunchKernelGGL(onepass_finish_kernel<>, dim3(Batch_Size), dim3(256), 0, st, prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr,
-                                  prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, 0, ws_o, ws_ml, NS + nchunks, static_cast<h16*>(out), Batch_Size);
+        {
+            hipEvent_t f0 = prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr, f1 = prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr;
+            const int NSL = NS + nchunks;
+            auto oh = static_cast<h16*>(out);
+#define MUSTAFAR_FIN(KERNEL, THREADS, TAIL) \
+    hipExtLaunchKernelGGL((KERNEL), dim3(Batch_Size), dim3(THREADS), 0, st, f0, f1, 0, ws_o, ws_ml, NSL, oh, Batch_Size, TAIL)
+            if (lse) {   // the same four variants, each with the LSE store
+                if (NSL <= 64 && finish1()) MUSTAFAR_FIN(onepass_finish1_kernel<true>, 128, LseArg{lse});
+                else if (NSL <= 64)         MUSTAFAR_FIN((onepass_finish_kernel<1, true>), 256, LseArg{lse});
+                else if (NSL <= 128)        MUSTAFAR_FIN((onepass_finish_kernel<2, true>), 256, LseArg{lse});
+                else                        MUSTAFAR_FIN((onepass_finish_kernel<kMaxSlabs / 64, true>), 256, LseArg{lse});
+            } else {
+                if (NSL <= 64 && finish1()) MUSTAFAR_FIN(onepass_finish1_kernel<false>, 128, NoLse{});
+                else if (NSL <= 64)         MUSTAFAR_FIN((onepass_finish_kernel<1, false>), 256, NoLse{});
+                else if (NSL <= 128)        MUSTAFAR_FIN((onepass_finish_kernel<2, false>), 256, NoLse{});
+                else                        MUSTAFAR_FIN((onepass_finish_kernel<kMaxSlabs / 64, false>), 256, NoLse{});
+            }
+#undef MUSTAFAR_FIN
+        }
         if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
         t_last_choice = eng | (1 << 4) | ((small_form ? 4 : sb_form() && per_wg <= 4 ? 3 : 2) << 8);
         return (int)hipGetLastError();
@@ -3969,18 +4042,31 @@ int mustafar_decode_attention(void* stream, const uint64_t* k_bmp, const void* k
                             mask_row_stride, heads_per_mask_row, flags);
 }
 
-int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
-                                 const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
-                                 const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
-                                 const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
-                                 void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
-                                 const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
-                                 int heads_per_mask_row, uint32_t flags, int head_dim)
+}  // extern "C"
+
+namespace {
+// mustafar_decode_attention_hd (lse_entry false) and mustafar_decode_attention_lse_hd (true; lse may still be nullptr)
+int decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                        const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                        const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                        const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                        void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                        const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                        int heads_per_mask_row, uint32_t flags, int head_dim, float* lse, bool lse_entry)
 {
-    if (head_dim == kD)
-        return mustafar_decode_attention(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new,
-                                         v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
-                                         num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
+    if (head_dim == kD) {
+        if (!lse_entry)
+            return mustafar_decode_attention(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new,
+                                             v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
+                                             num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
+        const mustafar_cache_view kc{const_cast<uint64_t*>(k_bmp), const_cast<void*>(k_nz), const_cast<uint32_t*>(k_idx),
+                                     const_cast<uint32_t*>(k_nz_offset), 0, 0, 0};
+        const mustafar_cache_view vc{const_cast<uint64_t*>(v_bmp), const_cast<void*>(v_nz), const_cast<uint32_t*>(v_idx),
+                                     const_cast<uint32_t*>(v_nz_offset), 0, 0, 0};
+        return decode_attention(stream, kc, vc, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
+                                workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
+                                mask_row_stride, heads_per_mask_row, flags, nullptr, nullptr, 0, nullptr, lse, true);
+    }
     if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
     // every engine flag runs the one exact engine (v_fma_mix arithmetic); the two-launch structure has no D = 64 form
     const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
@@ -3989,11 +4075,40 @@ int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void
     const int err = mustafar_hd64::decode(static_cast<hipStream_t>(stream), k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q,
                                           k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace,
                                           Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                                          mask_row_stride, heads_per_mask_row, prof ? g_prof.ev + 4 * g_prof.n : nullptr);
+                                          mask_row_stride, heads_per_mask_row, prof ? g_prof.ev + 4 * g_prof.n : nullptr, lse, lse_entry);
     if (err) return err;
     if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }   // (the one-pass launch in the "key" pair, the row merge in the second)
     t_last_choice = 0 | (1 << 4) | (5 << 8);
     return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                                 const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                                 const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                                 const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                                 void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                 const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                 int heads_per_mask_row, uint32_t flags, int head_dim)
+{
+    return decode_attention_hd(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new,
+                               window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups,
+                               sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, head_dim, nullptr, false);
+}
+
+int mustafar_decode_attention_lse_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
+                                     const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
+                                     const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
+                                     const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
+                                     void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                     const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                     int heads_per_mask_row, uint32_t flags, int head_dim, float* lse)
+{
+    return decode_attention_hd(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new,
+                               window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups,
+                               sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, head_dim, lse, true);
 }
 
 int64_t mustafar_decode_workspace_bytes_hd(int T, int Batch_Size, int num_key_value_groups, int Split_K, int head_dim)
@@ -4017,6 +4132,63 @@ int mustafar_decode_attention_view(void* stream, const mustafar_cache_view* k_ca
                             num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
 }
 
+}  // extern "C"
+
+namespace {
+// mustafar_decode_attention_extents (lse_entry false) and the D = 128 half of mustafar_decode_attention_extents_lse_hd (true)
+int decode_attention_extents(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                             const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                             const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                             int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                             int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                             const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                             int heads_per_mask_row, uint32_t flags, const int32_t* T_device, float* lse, bool lse_entry)
+{
+    if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255)) return MUSTAFAR_EINVAL;
+    if (T_device && T == T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
+    if (T == T_base)   // no appended extent: the plain call
+        return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
+                                out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
+                                mask_row_stride, heads_per_mask_row, flags, nullptr, nullptr, 0, nullptr, lse, lse_entry);
+    if (!k_extents || !v_extents || k_base->nz_head_stride == 0 || v_base->nz_head_stride == 0) return MUSTAFAR_EINVAL;
+    return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
+                            out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
+                            mask_row_stride, heads_per_mask_row, flags, k_extents, v_extents, T_base, T_device, lse, lse_entry);
+}
+
+// mustafar_decode_attention_extents_hd (lse_entry false) and mustafar_decode_attention_extents_lse_hd (true)
+int decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                                int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim, float* lse, bool lse_entry)
+{
+    if (head_dim == kD)
+        return decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new,
+                                        window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
+                                        num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
+                                        heads_per_mask_row, flags, T_device, lse, lse_entry);
+    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
+    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;   // as mustafar_decode_attention_hd
+    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
+    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
+    bool ran_extents = false;
+    const int err = mustafar_hd64::decode_extents(static_cast<hipStream_t>(stream), k_base, v_base, T_base, k_extents, v_extents, q, k_window,
+                                                  v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K,
+                                                  T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
+                                                  heads_per_mask_row, T_device, prof ? g_prof.ev + 4 * g_prof.n : nullptr, &ran_extents, lse,
+                                                  lse_entry);
+    if (err) return err;
+    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
+    t_last_choice = 0 | (1 << 4) | ((ran_extents ? 6 : 5) << 8);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
 int mustafar_decode_attention_extents(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
                                       const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
                                       const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
@@ -4025,16 +4197,9 @@ int mustafar_decode_attention_extents(void* stream, const mustafar_cache_view* k
                                       const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                       int heads_per_mask_row, uint32_t flags, const int32_t* T_device)
 {
-    if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255)) return MUSTAFAR_EINVAL;
-    if (T_device && T == T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
-    if (T == T_base)   // no appended extent: the plain call
-        return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
-                                out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                                mask_row_stride, heads_per_mask_row, flags);
-    if (!k_extents || !v_extents || k_base->nz_head_stride == 0 || v_base->nz_head_stride == 0) return MUSTAFAR_EINVAL;
-    return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
-                            out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                            mask_row_stride, heads_per_mask_row, flags, k_extents, v_extents, T_base, T_device);
+    return decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
+                                    window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
+                                    window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, nullptr, false);
 }
 
 int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
@@ -4045,24 +4210,51 @@ int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view
                                          const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                          int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim)
 {
-    if (head_dim == kD)
-        return mustafar_decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new,
-                                                 window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
-                                                 num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                                 heads_per_mask_row, flags, T_device);
-    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
-    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;   // as mustafar_decode_attention_hd
-    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
-    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
-    bool ran_extents = false;
-    const int err = mustafar_hd64::decode_extents(static_cast<hipStream_t>(stream), k_base, v_base, T_base, k_extents, v_extents, q, k_window,
-                                                  v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K,
-                                                  T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                                  heads_per_mask_row, T_device, prof ? g_prof.ev + 4 * g_prof.n : nullptr, &ran_extents);
-    if (err) return err;
-    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
-    t_last_choice = 0 | (1 << 4) | ((ran_extents ? 6 : 5) << 8);
-    return 0;
+    return decode_attention_extents_hd(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
+                                       window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
+                                       window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, head_dim, nullptr,
+                                       false);
+}
+
+int mustafar_decode_attention_extents_lse_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                             const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                             const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                             int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
+                                             int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
+                                             const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
+                                             int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim, float* lse)
+{
+    return decode_attention_extents_hd(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
+                                       window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
+                                       window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, head_dim, lse,
+                                       true);
+}
+
+int mustafar_merge_attention_states(void* stream, const void* outs, int64_t out_part_stride, const float* lses, int64_t lse_part_stride,
+                                    int n_parts, int Batch_Size, int head_dim, void* out, float* lse_out)
+{
+    if (n_parts < 1 || n_parts > kMaxMergeParts || Batch_Size < 1 || (head_dim != 64 && head_dim != kD) || !outs || !lses || !out)
+        return MUSTAFAR_EINVAL;
+    const int64_t row_halfs = (int64_t)Batch_Size * head_dim;
+    if (n_parts > 1 && (out_part_stride < row_halfs || lse_part_stride < Batch_Size)) return MUSTAFAR_EINVAL;
+    // the result must not lie inside the parts: a wave would overwrite rows that another one still reads
+    const uintptr_t p0 = (uintptr_t)outs, p1 = p0 + (size_t)(((int64_t)(n_parts - 1) * out_part_stride + row_halfs) * 2);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)(row_halfs * 2);
+    if (o0 < p1 && p0 < o1) return MUSTAFAR_EINVAL;
+    if (lse_out) {
+        const uintptr_t l0 = (uintptr_t)lses, l1 = l0 + (size_t)(((int64_t)(n_parts - 1) * lse_part_stride + Batch_Size) * 4);
+        const uintptr_t q0 = (uintptr_t)lse_out, q1 = q0 + (size_t)Batch_Size * 4;
+        if (q0 < l1 && l0 < q1) return MUSTAFAR_EINVAL;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((Batch_Size + kMergeRows - 1) / kMergeRows), block(64 * kMergeRows);
+    if (head_dim == 64)
+        merge_states_kernel<64><<<grid, block, 0, st>>>(static_cast<const h16*>(outs), out_part_stride, lses, lse_part_stride, n_parts, Batch_Size,
+                                                        static_cast<h16*>(out), lse_out);
+    else
+        merge_states_kernel<kD><<<grid, block, 0, st>>>(static_cast<const h16*>(outs), out_part_stride, lses, lse_part_stride, n_parts, Batch_Size,
+                                                        static_cast<h16*>(out), lse_out);
+    return (int)hipGetLastError();
 }
 
 int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint32_t flags)

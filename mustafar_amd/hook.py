@@ -339,8 +339,13 @@ class MustafarAttention:
 
     def decode_fused(self, query_states, key_states, value_states, past, step_counter: Optional[torch.Tensor] = None,
                      attention_mask: Optional[torch.Tensor] = None, t_device: Optional[torch.Tensor] = None,
-                     t_capacity: Optional[int] = None, defer_trigger: bool = False):
+                     t_capacity: Optional[int] = None, defer_trigger: bool = False, return_lse: bool = False):
         """Same contract as decode() with api="native"; windows are `Window` objects appended in place.
+
+        `return_lse`: return `(out, lse, past)`, `lse` fp32 [bsz, num_heads] = the log-sum-exp of each row's scores as the softmax saw
+        them (scaled, masked), written by the row kernel of the same call: what `partial.merge_states` needs to combine this output
+        with attention over tokens this call did not read.  Every cache kind, eagerly and under capture.  At
+        head_dim 128 the LSE comes from the one-pass forms: a call that would run two launches raises ValueError.
 
         `attention_mask` is the hook's additive mask [bsz, 1, 1, kv_seq_len] (model :293-301), applied inside the softmax
         kernel exactly as the model does (fp16 add, clamp at finfo.min).  Under graph replay (`step_counter`) the rows must
@@ -360,10 +365,31 @@ class MustafarAttention:
         tokens IN USE as a device quantity and the capacity the launch is sized for (a cache that grows by extents only).  ONE captured graph of the call then serves every compressed
         length up to `t_capacity`: after a trigger (run eagerly, outside the graph) the caller adds 256 to `t_device` and takes
         256 off `step_counter` (tests/test_gpu_extents.py)."""
+        lse = None
+        if return_lse:
+            self._lse_served(past[4] if t_capacity is None else t_capacity)
+            lse = torch.empty((query_states.shape[0], self.num_heads), dtype=torch.float32, device=query_states.device)
+        inner = self._decode_fused_ext64 if self.cfg.hd64_extents else self._decode_fused
+        out, new = inner(query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity, defer_trigger, lse)
+        return (out, lse, new) if return_lse else (out, new)
+
+    def _lse_served(self, C: int) -> None:
+        """The calls whose LSE the library refuses (mustafar_hip.h: the head_dim 128 forms that run two launches), named."""
+        if self.head_dim != 128:
+            return
+        if C == 0:
+            raise ValueError("decode_fused(return_lse=True): no compressed tokens yet -- a window-only call at head_dim 128 runs the "
+                             "two-launch form, which has no LSE")
+        if self.cfg.structure == "two_launch":
+            raise ValueError("decode_fused(return_lse=True): MustafarConfig(structure='two_launch') has no LSE; the one-pass forms do")
+        if self.cfg.structure is None and _lib.load().mustafar_get_onepass() == 0:
+            raise ValueError("decode_fused(return_lse=True): the process default is the two-launch form (MUSTAFAR_ONEPASS=0 / "
+                             "mustafar_set_onepass(0)), which has no LSE")
+
+    def _decode_fused(self, query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
+                      defer_trigger, lse):
+        """decode_fused over tuple caches and arenas.  lse: None (the plain entry points), or the tensor the row kernel fills."""
         cfg = self.cfg
-        if cfg.hd64_extents:
-            return self._decode_fused_ext64(query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
-                                            defer_trigger)
         bsz, _, q_len, D = query_states.shape
         assert q_len == 1 and (D == 128 or (D == 64 and self.head_dim == 64))
         BH, Bkv, groups = bsz * self.num_heads, bsz * self.num_key_value_heads, self.num_key_value_groups
@@ -427,7 +453,24 @@ class MustafarAttention:
         flags = tail[-1]
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            if use_arena and C > k_c.tokens:
+            if lse is not None:
+                # the two entry points with an LSE: the tuple cache through its eight arrays, an arena through its base views (T == T_base:
+                # the views alone) or base views + device tables
+                if use_arena:
+                    if C > k_c.tokens and not L.mustafar_decode_reads_extents(groups, ld, flags):
+                        raise RuntimeError("decode_fused: this launch form cannot read a cache that grows by extents "
+                                           "(MustafarConfig(extents=False), or consolidate() the arenas first)")
+                    grown = C > k_c.tokens
+                    err = L.mustafar_decode_attention_extents_lse_hd(
+                        st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.ext_table.data_ptr() if grown else None,
+                        v_c.ext_table.data_ptr() if grown else None, *tail, t_device.data_ptr() if t_device is not None else None, D,
+                        lse.data_ptr())
+                else:
+                    err = L.mustafar_decode_attention_lse_hd(
+                        st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,
+                        p(v_c[0]) if C else None, p(v_c[2].flat) if C else None, p(v_c[1]) if C else None, p(v_c[3]) if C else None, *tail, D,
+                        lse.data_ptr())
+            elif use_arena and C > k_c.tokens:
                 # the cache has grown by extents (or, under a capture ahead of a trigger, is about to): base views + device tables
                 if not L.mustafar_decode_reads_extents(groups, ld, flags):
                     # an engine / structure switch after the cache grew: this form reads ONE view -- one copy of the cache.  (Not
@@ -485,9 +528,35 @@ class MustafarAttention:
             C += 256
         return out, (k_c, k_w, v_c, v_w, C, kv_seq_len)
 
+    def decode_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None):
+        """One decode step over frozen compressed segments + the live cache: `frozen` is a list of `(k_cache, v_cache, tokens)` that
+        precede the live cache in sequence order (partial.decode_segment says what a segment may be).  One window-less call per
+        segment, one decode_fused(return_lse=True) call on `past`, one merge (partial.merge_states).  `attention_mask`: additive fp16
+        [bsz, 1, 1, frozen tokens + kv_seq_len]; every call reads its own columns (the pointer moves, rows need no alignment).
+        Returns (out, past) with the contract of decode(); the 256-token trigger runs on the live cache only."""
+        from . import partial
+        if self.cfg.api != "fused":
+            raise ValueError("decode_split needs MustafarConfig(api='fused')")
+        outs, lses, col = [], [], 0
+        total = sum(int(t) for _, _, t in frozen) + past[-1] + 1
+        if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[3] != total):
+            raise ValueError(f"Attention mask should be of size {(query_states.shape[0], 1, 1, total)}, but is {tuple(attention_mask.size())}")
+        for k_cache, v_cache, tokens in frozen:
+            m = attention_mask[..., col:col + tokens] if attention_mask is not None else None
+            o, l = partial.decode_segment(self, query_states, k_cache, v_cache, tokens, m)
+            outs.append(o)
+            lses.append(l)
+            col += tokens
+        m = attention_mask[..., col:] if attention_mask is not None else None
+        o, l, new = self.decode_fused(query_states, key_states, value_states, past, attention_mask=m, return_lse=True)
+        outs.append(o)
+        lses.append(l)
+        out, _ = partial.merge_states(outs, lses)
+        return out, new
+
     # ---- head_dim 64 over a cache that grows by extents (MustafarConfig(hd64_extents=True); cache64.py) ---------------------------------
     def _decode_fused_ext64(self, query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
-                            defer_trigger):
+                            defer_trigger, lse=None):
         """decode_fused for ExtentCache64 caches: the plain D = 64 launch while the cache is its base alone, the extents launch once
         extents exist or whenever `t_device` is passed; the trigger through run_triggers' batched form."""
         cfg = self.cfg
@@ -538,7 +607,13 @@ class MustafarAttention:
                 _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure])
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            if isinstance(k_c, ExtentCache64) and (k_c.extents or t_device is not None):
+            if lse is not None and isinstance(k_c, ExtentCache64):   # (T == T_base: the base alone, as the plain launch below)
+                err = L.mustafar_decode_attention_extents_lse_hd(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.table.data_ptr(),
+                                                                 v_c.table.data_ptr(), *tail,
+                                                                 t_device.data_ptr() if t_device is not None else None, D, lse.data_ptr())
+            elif lse is not None:
+                err = L.mustafar_decode_attention_lse_hd(st, *([None] * 8), *tail, D, lse.data_ptr())
+            elif isinstance(k_c, ExtentCache64) and (k_c.extents or t_device is not None):
                 err = L.mustafar_decode_attention_extents_hd(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.table.data_ptr(),
                                                              v_c.table.data_ptr(), *tail,
                                                              t_device.data_ptr() if t_device is not None else None, D)
