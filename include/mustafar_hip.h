@@ -442,6 +442,32 @@ int mustafar_merge_attention_states(void* stream, const void* outs, int64_t out_
                                     int n_parts, int Batch_Size, int head_dim, void* out, float* lse_out);
 
 /*
+ * Shared-prefix segments (ABI 111): ONE compressed copy of a frozen segment decoded for every sequence of a batch (shared_segment.hip).
+ *
+ * mustafar_decode_shared_segment: attention of n_seqs query tokens over one cache of `kv_heads` heads and T tokens, and nothing else.
+ *   Row (s, h) of q attends to kv head h / num_key_value_groups of the one cache.  Two launches: a workgroup of the first serves one kv
+ *   head and a run of consecutive 64-token blocks for all R = n_seqs * num_key_value_groups rows of it -- each block expanded once into a
+ *   dense fp16 image in LDS, scores and outputs on the matrix pipe (fp16 x fp16 products, fp32 sums), the online softmax of
+ *   mustafar_decode_attention_hd -- and leaves one (max, sum, output) slab per row; the row kernel merges a row's slabs.  The stream,
+ *   bitmaps and offsets of a block are requested from memory once per launch, whatever n_seqs is.
+ *   k_cache / v_cache   HOST views of a cache in the reference format, head_dim 64 or 128 (tiles = T * head_dim / 64 per head):
+ *                       bmp / idx strides 0 (exactly tiles / tiles + 1) or larger; nz_head_stride 0: nz_offset is loaded; nz 16-byte aligned
+ *   q, out              fp16 [n_seqs, kv_heads * num_key_value_groups, head_dim], contiguous, 16-byte aligned
+ *   lse                 fp32 [n_seqs, kv_heads * num_key_value_groups] out, REQUIRED: M + log(sum_t exp(x_t - M)) as the _lse_hd entry points
+ *   workspace           mustafar_shared_segment_workspace_bytes() bytes, 16-byte aligned
+ *   No window, no new row, no mask, no extents, no device-side T: a frozen segment has none.  MUSTAFAR_EINVAL before any launch for
+ *   T <= 0 or T % 64 != 0, n_seqs * num_key_value_groups outside 1..64, num_key_value_groups outside 1..8, head_dim not 64 or 128, null or
+ *   misaligned pointers.  Nothing is read back and nothing is allocated: the call can be captured in a hipGraph.
+ * mustafar_shared_segment_workspace_bytes: slabs * kv_heads * R * (head_dim + 2) * 4, slabs = ceil(T / 64 / blocks per run); a run holds
+ *   ceil(8 R (head_dim + 2) / (88 head_dim)) blocks, so that the slab bytes written and read stay below the stream bytes of the launch
+ *   (DESIGN.md 4.10).  0 for the shapes the call refuses.
+ */
+int64_t mustafar_shared_segment_workspace_bytes(int T, int kv_heads, int num_key_value_groups, int n_seqs, int head_dim);
+int mustafar_decode_shared_segment(void* stream, const mustafar_cache_view* k_cache, const mustafar_cache_view* v_cache,
+                                   int T, int kv_heads, int num_key_value_groups, int n_seqs,
+                                   const void* q, void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
+
+/*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
  * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
  *

@@ -530,7 +530,8 @@ class MustafarAttention:
 
     def decode_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None):
         """One decode step over frozen compressed segments + the live cache: `frozen` is a list of `(k_cache, v_cache, tokens)` that
-        precede the live cache in sequence order (partial.decode_segment says what a segment may be).  One window-less call per
+        precede the live cache in sequence order (partial.decode_segment says what a segment may be), and / or of
+        `partial.SharedSegment`s -- one copy of kv_heads heads that every sequence of the batch reads (no mask then).  One window-less call per
         segment, one decode_fused(return_lse=True) call on `past`, one merge (partial.merge_states).  `attention_mask`: additive fp16
         [bsz, 1, 1, frozen tokens + kv_seq_len]; every call reads its own columns (the pointer moves, rows need no alignment).
         Returns (out, past) with the contract of decode(); the 256-token trigger runs on the live cache only."""
@@ -538,10 +539,20 @@ class MustafarAttention:
         if self.cfg.api != "fused":
             raise ValueError("decode_split needs MustafarConfig(api='fused')")
         outs, lses, col = [], [], 0
-        total = sum(int(t) for _, _, t in frozen) + past[-1] + 1
+        shared = [isinstance(f, partial.SharedSegment) for f in frozen]
+        if any(shared) and attention_mask is not None:
+            raise ValueError("decode_split: a SharedSegment in `frozen` takes no attention mask (left padding and a shared prefix do not "
+                             "coexist); pass attention_mask=None")
+        total = sum(f.tokens if sh else int(f[2]) for f, sh in zip(frozen, shared)) + past[-1] + 1
         if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[3] != total):
             raise ValueError(f"Attention mask should be of size {(query_states.shape[0], 1, 1, total)}, but is {tuple(attention_mask.size())}")
-        for k_cache, v_cache, tokens in frozen:
+        for f, sh in zip(frozen, shared):
+            if sh:   # one copy for the whole batch: mustafar_decode_shared_segment
+                o, l = partial.decode_segment(self, query_states, f)
+                outs.append(o)
+                lses.append(l)
+                continue
+            k_cache, v_cache, tokens = f
             m = attention_mask[..., col:col + tokens] if attention_mask is not None else None
             o, l = partial.decode_segment(self, query_states, k_cache, v_cache, tokens, m)
             outs.append(o)
