@@ -31,6 +31,12 @@ class TriggerItem(ctypes.Structure):
 
 _item_p = ctypes.POINTER(TriggerItem)
 
+# The seven fused decode entry points share one run of arguments (q ... flags: what hook.py builds as one tuple); each adds its own
+# head (the stream and how the cache arrives) and tail (T_device, head_dim, lse).
+_DECODE_TAIL = [_vp] * 5 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i32, ctypes.c_uint32]
+_ARRAYS = [_vp] * 9                                     # stream + the eight arrays of the two caches
+_EXTENTS = [_vp, _view_p, _view_p, _i32, _vp, _vp]      # stream, base views, T_base, device tables
+
 # name -> (restype, argtypes); must list every symbol of include/mustafar_hip.h
 SIGNATURES = {
     "mustafar_abi_version": (_i32, []),
@@ -38,24 +44,14 @@ SIGNATURES = {
     "Value_SplitK_API": (_i32, [_vp] * 8 + [_i32] * 3 + [_vp] + [_i32] * 3),
     "mustafar_value_pick_split_k": (_i32, [_i32] * 5),
     "mustafar_value_workspace_bytes": (_i64, [_i32] * 6),
-    "mustafar_decode_attention": (_i32, [_vp] * 14 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp,
-                                         _vp, _i64, _i32, ctypes.c_uint32]),
-    "mustafar_decode_attention_hd": (_i32, [_vp] * 14 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp,
-                                            _vp, _i64, _i32, ctypes.c_uint32, _i32]),
+    "mustafar_decode_attention": (_i32, _ARRAYS + _DECODE_TAIL),
+    "mustafar_decode_attention_hd": (_i32, _ARRAYS + _DECODE_TAIL + [_i32]),
     "mustafar_decode_workspace_bytes_hd": (_i64, [_i32] * 5),
-    "mustafar_decode_attention_view": (_i32, [_vp, _view_p, _view_p] + [_vp] * 5 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
-                                              ctypes.c_float, _vp, _vp, _i64, _i32, ctypes.c_uint32]),
-    "mustafar_decode_attention_extents": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp] + [_vp] * 5 +
-                                          [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i32,
-                                           ctypes.c_uint32, _vp]),
-    "mustafar_decode_attention_extents_hd": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp] + [_vp] * 5 +
-                                             [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i32,
-                                              ctypes.c_uint32, _vp, _i32]),
-    "mustafar_decode_attention_lse_hd": (_i32, [_vp] * 14 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp,
-                                                _vp, _i64, _i32, ctypes.c_uint32, _i32, _vp]),
-    "mustafar_decode_attention_extents_lse_hd": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp] + [_vp] * 5 +
-                                                 [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i32,
-                                                  ctypes.c_uint32, _vp, _i32, _vp]),
+    "mustafar_decode_attention_view": (_i32, [_vp, _view_p, _view_p] + _DECODE_TAIL),
+    "mustafar_decode_attention_extents": (_i32, _EXTENTS + _DECODE_TAIL + [_vp]),
+    "mustafar_decode_attention_extents_hd": (_i32, _EXTENTS + _DECODE_TAIL + [_vp, _i32]),
+    "mustafar_decode_attention_lse_hd": (_i32, _ARRAYS + _DECODE_TAIL + [_i32, _vp]),
+    "mustafar_decode_attention_extents_lse_hd": (_i32, _EXTENTS + _DECODE_TAIL + [_vp, _i32, _vp]),
     "mustafar_merge_attention_states": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "mustafar_shared_segment_workspace_bytes": (_i64, [_i32] * 5),
     "mustafar_decode_shared_segment": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_float, _i32]),

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/mustafar_hip.h"
+#include "decode_call.h"
 
 namespace mustafar_hd64 {
 
@@ -19,24 +20,11 @@ int bitmap(bool key, hipStream_t st, const void* x, int Bp, int t, int64_t* bmp,
 int pack(bool key, hipStream_t st, const void* x, int Bp, int t, const int64_t* bmp, const int32_t* accum, const int64_t* head_off,
          void* nz_flat);
 
-// fused decode (the arguments of mustafar_decode_attention; flags already checked by the caller).  ev: 4 events (decode launch start /
-// stop, row-merge start / stop) or nullptr.  lse: fp32 [Batch_Size] written by the row merge, or nullptr; lse_entry: the call came through
-// an entry point with an LSE argument, which also accepts a window-less call (mustafar_hip.h).
-int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
-           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
-           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
-           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, float* lse = nullptr,
-           bool lse_entry = false);
+// fused decode of one DecodeCall (decode_call.h; flags already checked by the caller): the plain launch over c.k / c.v, or, with
+// c.k_ext set, the one over base views + device tables of 256-token extents.  ev: 4 events (decode launch start / stop, row-merge
+// start / stop) or nullptr.  *ran_extents: the EXT instantiation was launched.
+int decode(const DecodeCall& c, hipEvent_t* ev, bool* ran_extents);
 int64_t workspace_bytes(int T, int Batch_Size, int groups);
-// the same over base views + device tables of 256-token extents (mustafar_decode_attention_extents_hd); *ran_extents: the EXT
-// instantiation was launched (false: T == T_base, the plain one over the base)
-int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
-                   const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, const void* q, void* k_window, void* v_window,
-                   const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
-                   void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-                   const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, const int32_t* T_device, hipEvent_t* ev,
-                   bool* ran_extents, float* lse = nullptr, bool lse_entry = false);
 // the 256-token trigger: n launches, raw window rows -> one extent per layer and side; the finish lists the views and slides the windows
 int trigger_compress_batch(hipStream_t st, int n, const mustafar_trigger_item* items, int64_t head_stride, int Bp, int t, int kth_k, int kth_v,
                            int64_t k_region_halfs, int64_t v_region_halfs);

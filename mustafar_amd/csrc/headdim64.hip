@@ -851,24 +851,23 @@ int64_t workspace_bytes(int T, int Batch_Size, int groups)
 
 namespace {
 
-// Validation and launches shared by the two decode entry points.  ext == nullptr: the plain instantiation over one set of arrays.
-int launch_decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
-                  const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
-                  void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
-                  void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-                  const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, const ExtArgs* ext,
-                  float* lse, bool lse_entry)
+// Validation and launches of one call.  ext == nullptr: the plain instantiation over one set of arrays.
+int launch_decode(const DecodeCall& c, hipEvent_t* ev, const ExtArgs* ext)
 {
-    if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
-    // A window-less call (the entry points with an LSE only): no window argument at all and at least one compressed token.  Its launch
-    // has no window workgroups and no window slabs; any other mixture of zero and non-zero window arguments is refused.
-    const bool no_window = lse_entry && window_len == 0 && window_capacity == 0 && !k_window && !v_window && !k_new && !v_new &&
-                           !window_len_extra && T > 0;
-    if (T < 0 || (T & 63) || groups < 1 || groups > 8 || Batch_Size < 1 || Batch_Size % groups || (window_len < 1 && !no_window) ||
-        window_len > window_capacity || window_capacity > kMaxWindow ||
-        ld_scores < T + (window_len_extra ? window_capacity : window_len) || (ld_scores & 7) || Split_K < 1 || !(sqrt_d > 0.f))
-        return MUSTAFAR_EINVAL;
-    if (!q || ((!k_window || !v_window) && !no_window) || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    bool no_window = false;
+    if (!decode_call_ok(c, kMaxWindow, &no_window) || c.groups > 8) return MUSTAFAR_EINVAL;
+    const hipStream_t st = c.stream;
+    const uint64_t *k_bmp = c.k.bmp, *v_bmp = c.v.bmp;
+    const void *k_nz = c.k.nz, *v_nz = c.v.nz;
+    const uint32_t *k_idx = c.k.idx, *k_nz_offset = c.k.nz_offset, *v_idx = c.v.idx, *v_nz_offset = c.v.nz_offset;
+    const void *q = c.q, *k_new = c.k_new, *v_new = c.v_new, *attention_mask = c.attention_mask;
+    void *k_window = c.k_window, *v_window = c.v_window, *out = c.out, *workspace = c.workspace;
+    const int window_len = c.window_len, window_capacity = c.window_capacity, T = c.T, Batch_Size = c.Batch_Size, groups = c.groups;
+    const int32_t* window_len_extra = c.window_len_extra;
+    const int64_t mask_row_stride = c.mask_row_stride;
+    const int heads_per_mask_row = c.heads_per_mask_row;
+    const float sqrt_d = c.sqrt_d;
+    float* lse = c.lse;
     // window rows (and the new rows) are read as 16-byte pieces
     if (!aligned16(k_window) || !aligned16(v_window) || (k_new && !aligned16(k_new))) return MUSTAFAR_EINVAL;
     if (T > 0 && (!k_bmp || !k_nz || !k_idx || !v_bmp || !v_nz || !v_idx)) return MUSTAFAR_EINVAL;
@@ -930,51 +929,27 @@ bool extent_view_ok(const mustafar_cache_view& v, int Bp, int64_t region_halfs)
 
 }  // namespace
 
-int decode(hipStream_t st, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx, const uint32_t* k_nz_offset,
-           const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx, const uint32_t* v_nz_offset, const void* q, void* k_window,
-           void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores,
-           void* out, void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-           const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, hipEvent_t* ev, float* lse, bool lse_entry)
-{
-    return launch_decode(st, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new, window_len,
-                         window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra,
-                         attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr, lse, lse_entry);
-}
-
-int decode_extents(hipStream_t st, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
-                   const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, const void* q, void* k_window, void* v_window,
-                   const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
-                   void* workspace, int Split_K, int T, int Batch_Size, int groups, float sqrt_d, const int32_t* window_len_extra,
-                   const void* attention_mask, int64_t mask_row_stride, int heads_per_mask_row, const int32_t* T_device, hipEvent_t* ev,
-                   bool* ran_extents, float* lse, bool lse_entry)
+int decode(const DecodeCall& c, hipEvent_t* ev, bool* ran_extents)
 {
     *ran_extents = false;
-    if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255) || (T - T_base) / 256 > kMaxExtents)
-        return MUSTAFAR_EINVAL;
-    if (T_device && T == T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
-    if (T == T_base) {   // no appended extent: the plain launch over the base (whose rows must then be exactly T long)
-        if ((k_base->bmp_head_stride && k_base->bmp_head_stride != T) || (k_base->idx_head_stride && k_base->idx_head_stride != T + 1) ||
-            (v_base->bmp_head_stride && v_base->bmp_head_stride != T) || (v_base->idx_head_stride && v_base->idx_head_stride != T + 1))
-            return MUSTAFAR_EINVAL;
-        return launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx, v_base->nz_offset,
-                             q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T,
-                             Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, ev, nullptr, lse,
-                             lse_entry);
+    const mustafar_cache_view* b[2] = {&c.k, &c.v};
+    if (!c.k_ext) {   // the plain launch; base views that carry row strides (T == T_base at an extents entry point) must have rows exactly T long
+        for (int i = 0; i < 2; i++)
+            if ((b[i]->bmp_head_stride && b[i]->bmp_head_stride != c.T) || (b[i]->idx_head_stride && b[i]->idx_head_stride != c.T + 1))
+                return MUSTAFAR_EINVAL;
+        return launch_decode(c, ev, nullptr);
     }
-    if (!k_extents || !v_extents) return MUSTAFAR_EINVAL;
-    const mustafar_cache_view* b[2] = {k_base, v_base};
+    const int T_base = c.T_base;   // (T_base > 0, T > T_base and both in whole extents: checked by the dispatcher)
+    if ((c.T - T_base) / 256 > kMaxExtents) return MUSTAFAR_EINVAL;
     for (int i = 0; i < 2; i++)
         if ((b[i]->bmp_head_stride && b[i]->bmp_head_stride < T_base) || (b[i]->idx_head_stride && b[i]->idx_head_stride < T_base + 1) ||
             b[i]->nz_head_stride < 0 || b[i]->nz_head_stride > 0xffffffffll)
             return MUSTAFAR_EINVAL;
-    const ExtArgs e{k_extents, v_extents, T_device,
-                    k_base->bmp_head_stride ? k_base->bmp_head_stride : T_base, k_base->idx_head_stride ? k_base->idx_head_stride : T_base + 1,
-                    v_base->bmp_head_stride ? v_base->bmp_head_stride : T_base, v_base->idx_head_stride ? v_base->idx_head_stride : T_base + 1,
-                    (uint32_t)k_base->nz_head_stride, (uint32_t)v_base->nz_head_stride, T_base};
-    const int err = launch_decode(st, k_base->bmp, k_base->nz, k_base->idx, k_base->nz_offset, v_base->bmp, v_base->nz, v_base->idx,
-                                  v_base->nz_offset, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
-                                  workspace, Split_K, T, Batch_Size, groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                  heads_per_mask_row, ev, &e, lse, lse_entry);
+    const ExtArgs e{c.k_ext, c.v_ext, c.T_device,
+                    c.k.bmp_head_stride ? c.k.bmp_head_stride : T_base, c.k.idx_head_stride ? c.k.idx_head_stride : T_base + 1,
+                    c.v.bmp_head_stride ? c.v.bmp_head_stride : T_base, c.v.idx_head_stride ? c.v.idx_head_stride : T_base + 1,
+                    (uint32_t)c.k.nz_head_stride, (uint32_t)c.v.nz_head_stride, T_base};
+    const int err = launch_decode(c, ev, &e);
     *ran_extents = err == 0;
     return err;
 }

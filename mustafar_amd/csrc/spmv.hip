@@ -3509,7 +3509,7 @@ inline bool window_rows_last(int side)
 // c3 5200 vs 4590, c4 1676 vs 1543, c5 3672 vs 3391), so `by size` means one-pass wherever the launch can run: T > 0 and
 // ld_scores % 32 == 0.  (Round 2's kernel lost to two launches at c4 / c5 on the VALU engine; it is gone, DESIGN.md.)
 // Process DEFAULTS live in the g_* variables (environment, mustafar_set_fma_engine / mustafar_set_onepass); a fused call may carry
-// its own choice in its `flags` argument, in force for that call only (t_engine / t_onepass: set and cleared by decode_attention
+// its own choice in its `flags` argument, in force for that call only (t_engine / t_onepass: set and cleared by decode_dispatch
 // on the calling thread).
 thread_local int t_engine = -1, t_onepass = -1;
 thread_local int t_last_choice = -1;   // what the last fused call on this thread launched: engine | structure << 4 | one-pass form << 8
@@ -3813,35 +3813,34 @@ int64_t mustafar_decode_workspace_bytes(int T, int Batch_Size, int num_key_value
 }  // extern "C"
 
 namespace {
-int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar_cache_view& vc, const void* q, void* k_window,
-                     void* v_window, const void* k_new, const void* v_new, int window_len, int window_capacity, void* scores,
-                     int ld_scores, void* out, void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups,
-                     float sqrt_d, const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
-                     int heads_per_mask_row, uint32_t flags, const mustafar_cache_view* k_ext = nullptr,
-                     const mustafar_cache_view* v_ext = nullptr, int T_base = 0, const int32_t* T_device = nullptr, float* lse = nullptr,
-                     bool lse_entry = false)
+// `flags` of a fused call (mustafar_hip.h: MUSTAFAR_FLAG_*) taken apart; false: a value outside the defined ones
+bool parse_flags(uint32_t flags, uint32_t* f_eng, uint32_t* f_str)
 {
-    const int groups = num_key_value_groups;
-    const bool extents = k_ext != nullptr;   // (validated by mustafar_decode_attention_extents)
-    // the call's own engine / structure (mustafar_hip.h: MUSTAFAR_FLAG_*), in force until this function returns
-    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
-    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u)) return MUSTAFAR_EINVAL;
-    struct Override {
-        Override(int e, int o) { t_engine = e; t_onepass = o; }
-        ~Override() { t_engine = -1; t_onepass = -1; }
-    } override_(f_eng == 1 ? 0 : f_eng == 2 ? 1 : f_eng == 3 ? 2 : -1, f_str == 1 ? 0 : f_str == 2 ? 1 : -1);
-    if (attention_mask && (heads_per_mask_row < 1 || Batch_Size % heads_per_mask_row || mask_row_stride < 0)) return MUSTAFAR_EINVAL;
-    const MaskArg mask{static_cast<const h16*>(attention_mask), mask_row_stride, heads_per_mask_row > 0 ? heads_per_mask_row : 1};
-    // A window-less call (the entry points with an LSE only): no window argument at all and at least one compressed token.  The one-pass
-    // launch then has no window workgroups (win_rows = 0) and no window slabs; any other mixture of zero and non-zero window arguments
-    // is refused, and so is the two-launch form, whose row kernels read the window themselves.
-    const bool no_window = lse_entry && window_len == 0 && window_capacity == 0 && !k_window && !v_window && !k_new && !v_new &&
-                           !window_len_extra && T > 0;
-    if (T < 0 || (T & 63) || groups < 1 || Batch_Size < 1 || Batch_Size % groups || (window_len < 1 && !no_window) ||
-        window_len > window_capacity || window_capacity > kMaxWindow ||
-        ld_scores < T + (window_len_extra ? window_capacity : window_len) || (ld_scores & 7) || Split_K < 1 || !(sqrt_d > 0.f))
-        return MUSTAFAR_EINVAL;
-    if (!q || ((!k_window || !v_window) && !no_window) || !scores || !out || !workspace) return MUSTAFAR_EINVAL;
+    *f_eng = flags & 7u;
+    *f_str = (flags >> 4) & 3u;
+    return !(*f_eng > 3u || *f_str > 2u || (flags & ~0x37u));
+}
+
+// head_dim 128.  ev: the 4 events of a profile record or nullptr.  *choice: what was launched (mustafar_last_decode_choice), left
+// alone by a call that is refused.  The call's own engine / structure are in force (decode_dispatch).
+int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
+{
+    const mustafar_cache_view &kc = c.k, &vc = c.v;
+    const mustafar_cache_view *k_ext = c.k_ext, *v_ext = c.v_ext;
+    const int T_base = c.T_base, T = c.T, Batch_Size = c.Batch_Size, groups = c.groups, Split_K = c.Split_K, ld_scores = c.ld_scores;
+    const int window_len = c.window_len, window_capacity = c.window_capacity;
+    const int32_t *T_device = c.T_device, *window_len_extra = c.window_len_extra;
+    void *k_window = c.k_window, *v_window = c.v_window, *scores = c.scores, *out = c.out, *workspace = c.workspace;
+    const void *q = c.q, *k_new = c.k_new, *v_new = c.v_new;
+    const float sqrt_d = c.sqrt_d;
+    float* lse = c.lse;
+    const bool extents = k_ext != nullptr;   // (T > T_base and both tables: checked by decode_dispatch)
+    if (extents && (kc.nz_head_stride == 0 || vc.nz_head_stride == 0)) return MUSTAFAR_EINVAL;
+    // A window-less call has no window workgroups (win_rows = 0) and no window slabs in the one-pass launch; the two-launch form,
+    // whose row kernels read the window themselves, is refused for it.
+    bool no_window = false;
+    if (!decode_call_ok(c, kMaxWindow, &no_window)) return MUSTAFAR_EINVAL;
+    const MaskArg mask{static_cast<const h16*>(c.attention_mask), c.mask_row_stride, c.heads_per_mask_row > 0 ? c.heads_per_mask_row : 1};
     // an LSE comes from the one-pass forms' row kernels: a call that would run two launches is refused before anything is launched
     if ((lse || no_window) && !(T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0)) return MUSTAFAR_EINVAL;
     if (T > 0 && (!kc.bmp || !kc.nz || !kc.idx || !kc.nz_offset || !vc.bmp || !vc.nz || !vc.idx || !vc.nz_offset)) return MUSTAFAR_EINVAL;
@@ -3849,13 +3848,12 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
     if (T > 0 && ((kc.bmp_head_stride && kc.bmp_head_stride < tiles) || (kc.idx_head_stride && kc.idx_head_stride < tiles + 1) ||
                   (vc.bmp_head_stride && vc.bmp_head_stride < tiles) || (vc.idx_head_stride && vc.idx_head_stride < tiles + 1)))
         return MUSTAFAR_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = c.stream;
     auto qh = static_cast<const h16*>(q);
     auto sc = static_cast<h16*>(scores);
     const int G = pick_g(groups);
     const int gy = (Batch_Size / groups) * (groups / G);
     int S = 0, nwin_slabs = 0;
-    const bool prof = g_prof.on && g_prof.n < g_prof.cap && T > 0;
     auto kwin = static_cast<h16*>(k_window);
     auto vwin = static_cast<h16*>(v_window);
     auto knew = static_cast<const h16*>(k_new);
@@ -3905,7 +3903,7 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
             const int64_t W = (int64_t)S1 * gy, full = W / slots * slots;
             if (g_late_prio && full > 0 && W - full > 0 && (W - full) * 4 <= slots && !(a.win_rows > 0)) a.hi_prio_from = (int)full;
         }
-        hipEvent_t e0 = prof ? g_prof.ev[4 * g_prof.n] : nullptr, e1 = prof ? g_prof.ev[4 * g_prof.n + 1] : nullptr;
+        hipEvent_t e0 = ev ? ev[0] : nullptr, e1 = ev ? ev[1] : nullptr;
         auto kz = static_cast<const unsigned char*>(kc.nz), vz = static_cast<const unsigned char*>(vc.nz);
         bool small_form = false;
 #define MUSTAFAR_LL(KERNEL)                                                                                                           \
@@ -3957,7 +3955,7 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
 #undef MUSTAFAR_LL
         // (the row kernel's own start / stop timestamps go into the record's second event pair: mustafar_profile_end2)
         {
-            hipEvent_t f0 = prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr, f1 = prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr;
+            hipEvent_t f0 = ev ? ev[2] : nullptr, f1 = ev ? ev[3] : nullptr;
             const int NSL = NS + nchunks;
             auto oh = static_cast<h16*>(out);
 #define MUSTAFAR_FIN(KERNEL, THREADS, TAIL) \
@@ -3975,8 +3973,7 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
             }
 #undef MUSTAFAR_FIN
         }
-        if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
-        t_last_choice = eng | (1 << 4) | ((small_form ? 4 : sb_form() && per_wg <= 4 ? 3 : 2) << 8);
+        *choice = eng | (1 << 4) | ((small_form ? 4 : sb_form() && per_wg <= 4 ? 3 : 2) << 8);
         return (int)hipGetLastError();
     }
     // ---- two-launch form.  With a compressed part the dense-window work rides in the two SpMV launches (window workgroups);
@@ -3986,7 +3983,7 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
     if (T > 0) {
         const WinArgs kw = ride_k ? WinArgs{kwin, knew, window_len_extra, window_len, window_capacity, 0, 0} : WinArgs{};
         launch_key(st, kc.bmp, static_cast<const unsigned char*>(kc.nz), kc.idx, kc.nz_offset, qh, sc, T, 1, groups, Batch_Size, ld_scores, kw,
-                   prof ? g_prof.ev[4 * g_prof.n] : nullptr, prof ? g_prof.ev[4 * g_prof.n + 1] : nullptr, kc.bmp_head_stride,
+                   ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, kc.bmp_head_stride,
                    kc.idx_head_stride, (uint32_t)kc.nz_head_stride);
     }
     const float inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
@@ -4011,15 +4008,90 @@ int decode_attention(void* stream, const mustafar_cache_view& kc, const mustafar
         const WinArgs vw = ride_v ? WinArgs{vwin, vnew, window_len_extra, window_len, window_capacity, 0, 0} : WinArgs{};
         if (ride_v) nwin_slabs = (window_capacity + kValueWinChunk - 1) / kValueWinChunk;
         launch_value(st, gv, vc.bmp, nz, vc.idx, vc.nz_offset, sc, no_out, ws, no_flags, T, 1, groups, Batch_Size, tb_per_wg, 0, ld_scores, vw,
-                     prof ? g_prof.ev[4 * g_prof.n + 2] : nullptr, prof ? g_prof.ev[4 * g_prof.n + 3] : nullptr, vc.bmp_head_stride,
+                     ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, vc.bmp_head_stride,
                      vc.idx_head_stride, (uint32_t)vc.nz_head_stride);
-        if (prof) g_prof.n++;
     }
     value_finish_kernel<<<Batch_Size, 256, 0, st>>>(ws, S + nwin_slabs, sc, ld_scores, T, ride_v ? nullptr : vwin, ride_v ? nullptr : vnew,
                                                     window_len, window_capacity, static_cast<h16*>(out), Batch_Size, groups,
                                                     window_len_extra);
-    t_last_choice = (fma_engine() == 1 && G == 4 ? 1 : 0);
+    *choice = (fma_engine() == 1 && G == 4 ? 1 : 0);
     return (int)hipGetLastError();
+}
+
+// Every fused entry point ends here.  One place for: the flags, the preconditions of the extents entry points, the call's own
+// engine / structure, the route by head_dim, the profile record and mustafar_last_decode_choice().
+int decode_dispatch(DecodeCall c)
+{
+    uint32_t f_eng, f_str;
+    if (!parse_flags(c.flags, &f_eng, &f_str)) return MUSTAFAR_EINVAL;
+    const bool hd64 = c.head_dim == mustafar_hd64::kD;
+    if (!hd64 && c.head_dim != kD) return MUSTAFAR_EINVAL;
+    // head_dim 64: every engine flag runs the one exact engine (v_fma_mix arithmetic); the two-launch structure has no D = 64 form
+    if (hd64 && f_str == 1u) return MUSTAFAR_EINVAL;
+    if (c.extents_entry) {
+        if (c.T_base <= 0 || (c.T_base & 255) || c.T < c.T_base || ((c.T - c.T_base) & 255)) return MUSTAFAR_EINVAL;
+        if (c.T_device && c.T == c.T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
+        if (c.T == c.T_base) {   // no appended extent: the plain call over the base, which needs no tables
+            c.k_ext = c.v_ext = nullptr;
+            c.T_base = 0;
+        } else if (!c.k_ext || !c.v_ext) return MUSTAFAR_EINVAL;
+    }
+    // the call's own engine / structure, in force on this thread until this function returns (fma_engine(), onepass_mode())
+    struct Override {
+        Override(int e, int o) { t_engine = e; t_onepass = o; }
+        ~Override() { t_engine = -1; t_onepass = -1; }
+    } override_(f_eng == 1 ? 0 : f_eng == 2 ? 1 : f_eng == 3 ? 2 : -1, f_str == 1 ? 0 : f_str == 2 ? 1 : -1);
+    // a profile record: head_dim 128 takes one only with a compressed part (T == 0 runs the two row kernels alone)
+    const bool prof = g_prof.on && g_prof.n < g_prof.cap && (hd64 || c.T > 0);
+    hipEvent_t* ev = prof ? g_prof.ev + 4 * g_prof.n : nullptr;
+    int choice = -1, err;
+    if (hd64) {
+        bool ran_extents = false;
+        err = mustafar_hd64::decode(c, ev, &ran_extents);
+        if (!err) choice = 0 | (1 << 4) | ((ran_extents ? 6 : 5) << 8);
+    } else {
+        err = decode_attention(c, ev, &choice);   // (sets `choice` once it has launched, whatever the launch returned)
+    }
+    if (choice < 0) return err;
+    if (prof) {
+        // a one-pass launch: its events in the "key" pair, the row merge in the second; two launches: key and value SpMV
+        if (choice & (1 << 4)) { g_prof.onepass++; g_prof.finish++; }
+        g_prof.n++;
+    }
+    t_last_choice = choice;
+    return err;
+}
+
+// The arguments that every entry point spells the same way (q ... flags), copied by name.
+#define MUSTAFAR_FILL_COMMON(c)                                                                                                   \
+    do {                                                                                                                          \
+        c.stream = static_cast<hipStream_t>(stream);                                                                              \
+        c.q = q; c.k_window = k_window; c.v_window = v_window; c.k_new = k_new; c.v_new = v_new;                                  \
+        c.window_len = window_len; c.window_capacity = window_capacity; c.scores = scores; c.ld_scores = ld_scores;              \
+        c.out = out; c.workspace = workspace; c.Split_K = Split_K; c.T = T; c.Batch_Size = Batch_Size;                            \
+        c.groups = num_key_value_groups; c.sqrt_d = sqrt_d; c.window_len_extra = window_len_extra;                                \
+        c.attention_mask = attention_mask; c.mask_row_stride = mask_row_stride; c.heads_per_mask_row = heads_per_mask_row;       \
+        c.flags = flags;                                                                                                          \
+    } while (0)
+
+mustafar_cache_view view_of(const uint64_t* bmp, const void* nz, const uint32_t* idx, const uint32_t* nz_offset)
+{
+    return mustafar_cache_view{const_cast<uint64_t*>(bmp), const_cast<void*>(nz), const_cast<uint32_t*>(idx), const_cast<uint32_t*>(nz_offset),
+                               0, 0, 0};
+}
+// (a null view is a view of null arrays: refused wherever T > 0, accepted by mustafar_decode_attention_view at T == 0)
+mustafar_cache_view view_of(const mustafar_cache_view* v) { return v ? *v : view_of(nullptr, nullptr, nullptr, nullptr); }
+// the cache arguments of the three extents entry points
+void fill_extents(DecodeCall& c, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                  const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, const int32_t* T_device)
+{
+    c.k = view_of(k_base);
+    c.v = view_of(v_base);
+    c.extents_entry = true;
+    c.k_ext = k_extents;
+    c.v_ext = v_extents;
+    c.T_base = T_base;
+    c.T_device = T_device;
 }
 }  // namespace
 
@@ -4033,57 +4105,12 @@ int mustafar_decode_attention(void* stream, const uint64_t* k_bmp, const void* k
                               const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                               int heads_per_mask_row, uint32_t flags)
 {
-    const mustafar_cache_view kc{const_cast<uint64_t*>(k_bmp), const_cast<void*>(k_nz), const_cast<uint32_t*>(k_idx),
-                                 const_cast<uint32_t*>(k_nz_offset), 0, 0, 0};
-    const mustafar_cache_view vc{const_cast<uint64_t*>(v_bmp), const_cast<void*>(v_nz), const_cast<uint32_t*>(v_idx),
-                                 const_cast<uint32_t*>(v_nz_offset), 0, 0, 0};
-    return decode_attention(stream, kc, vc, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
-                            workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                            mask_row_stride, heads_per_mask_row, flags);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    c.k = view_of(k_bmp, k_nz, k_idx, k_nz_offset);
+    c.v = view_of(v_bmp, v_nz, v_idx, v_nz_offset);
+    return decode_dispatch(c);
 }
-
-}  // extern "C"
-
-namespace {
-// mustafar_decode_attention_hd (lse_entry false) and mustafar_decode_attention_lse_hd (true; lse may still be nullptr)
-int decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
-                        const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
-                        const uint32_t* v_nz_offset, const void* q, void* k_window, void* v_window, const void* k_new,
-                        const void* v_new, int window_len, int window_capacity, void* scores, int ld_scores, void* out,
-                        void* workspace, int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
-                        const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
-                        int heads_per_mask_row, uint32_t flags, int head_dim, float* lse, bool lse_entry)
-{
-    if (head_dim == kD) {
-        if (!lse_entry)
-            return mustafar_decode_attention(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new,
-                                             v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
-                                             num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
-        const mustafar_cache_view kc{const_cast<uint64_t*>(k_bmp), const_cast<void*>(k_nz), const_cast<uint32_t*>(k_idx),
-                                     const_cast<uint32_t*>(k_nz_offset), 0, 0, 0};
-        const mustafar_cache_view vc{const_cast<uint64_t*>(v_bmp), const_cast<void*>(v_nz), const_cast<uint32_t*>(v_idx),
-                                     const_cast<uint32_t*>(v_nz_offset), 0, 0, 0};
-        return decode_attention(stream, kc, vc, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out,
-                                workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                                mask_row_stride, heads_per_mask_row, flags, nullptr, nullptr, 0, nullptr, lse, true);
-    }
-    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
-    // every engine flag runs the one exact engine (v_fma_mix arithmetic); the two-launch structure has no D = 64 form
-    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
-    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
-    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
-    const int err = mustafar_hd64::decode(static_cast<hipStream_t>(stream), k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q,
-                                          k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace,
-                                          Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                                          mask_row_stride, heads_per_mask_row, prof ? g_prof.ev + 4 * g_prof.n : nullptr, lse, lse_entry);
-    if (err) return err;
-    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }   // (the one-pass launch in the "key" pair, the row merge in the second)
-    t_last_choice = 0 | (1 << 4) | (5 << 8);
-    return 0;
-}
-}  // namespace
-
-extern "C" {
 
 int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
                                  const uint32_t* k_nz_offset, const uint64_t* v_bmp, const void* v_nz, const uint32_t* v_idx,
@@ -4093,9 +4120,12 @@ int mustafar_decode_attention_hd(void* stream, const uint64_t* k_bmp, const void
                                  const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                  int heads_per_mask_row, uint32_t flags, int head_dim)
 {
-    return decode_attention_hd(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new,
-                               window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups,
-                               sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, head_dim, nullptr, false);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    c.k = view_of(k_bmp, k_nz, k_idx, k_nz_offset);
+    c.v = view_of(v_bmp, v_nz, v_idx, v_nz_offset);
+    c.head_dim = head_dim;
+    return decode_dispatch(c);
 }
 
 int mustafar_decode_attention_lse_hd(void* stream, const uint64_t* k_bmp, const void* k_nz, const uint32_t* k_idx,
@@ -4106,9 +4136,14 @@ int mustafar_decode_attention_lse_hd(void* stream, const uint64_t* k_bmp, const 
                                      const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                      int heads_per_mask_row, uint32_t flags, int head_dim, float* lse)
 {
-    return decode_attention_hd(stream, k_bmp, k_nz, k_idx, k_nz_offset, v_bmp, v_nz, v_idx, v_nz_offset, q, k_window, v_window, k_new, v_new,
-                               window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups,
-                               sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, head_dim, lse, true);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    c.k = view_of(k_bmp, k_nz, k_idx, k_nz_offset);
+    c.v = view_of(v_bmp, v_nz, v_idx, v_nz_offset);
+    c.head_dim = head_dim;
+    c.lse = lse;
+    c.lse_entry = true;
+    return decode_dispatch(c);
 }
 
 int64_t mustafar_decode_workspace_bytes_hd(int T, int Batch_Size, int num_key_value_groups, int Split_K, int head_dim)
@@ -4125,69 +4160,12 @@ int mustafar_decode_attention_view(void* stream, const mustafar_cache_view* k_ca
                                    const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                    int heads_per_mask_row, uint32_t flags)
 {
-    const mustafar_cache_view none{nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
-    if (T > 0 && (!k_cache || !v_cache)) return MUSTAFAR_EINVAL;
-    return decode_attention(stream, k_cache ? *k_cache : none, v_cache ? *v_cache : none, q, k_window, v_window, k_new, v_new,
-                            window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
-                            num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    c.k = view_of(k_cache);
+    c.v = view_of(v_cache);
+    return decode_dispatch(c);
 }
-
-}  // extern "C"
-
-namespace {
-// mustafar_decode_attention_extents (lse_entry false) and the D = 128 half of mustafar_decode_attention_extents_lse_hd (true)
-int decode_attention_extents(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
-                             const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
-                             const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
-                             int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
-                             int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
-                             const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
-                             int heads_per_mask_row, uint32_t flags, const int32_t* T_device, float* lse, bool lse_entry)
-{
-    if (!k_base || !v_base || T_base <= 0 || (T_base & 255) || T < T_base || ((T - T_base) & 255)) return MUSTAFAR_EINVAL;
-    if (T_device && T == T_base) return MUSTAFAR_EINVAL;   // (a capacity of exactly the base tokens: nothing to grow into)
-    if (T == T_base)   // no appended extent: the plain call
-        return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
-                                out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                                mask_row_stride, heads_per_mask_row, flags, nullptr, nullptr, 0, nullptr, lse, lse_entry);
-    if (!k_extents || !v_extents || k_base->nz_head_stride == 0 || v_base->nz_head_stride == 0) return MUSTAFAR_EINVAL;
-    return decode_attention(stream, *k_base, *v_base, q, k_window, v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores,
-                            out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask,
-                            mask_row_stride, heads_per_mask_row, flags, k_extents, v_extents, T_base, T_device, lse, lse_entry);
-}
-
-// mustafar_decode_attention_extents_hd (lse_entry false) and mustafar_decode_attention_extents_lse_hd (true)
-int decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
-                                const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
-                                const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
-                                int window_len, int window_capacity, void* scores, int ld_scores, void* out, void* workspace,
-                                int Split_K, int T, int Batch_Size, int num_key_value_groups, float sqrt_d,
-                                const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
-                                int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim, float* lse, bool lse_entry)
-{
-    if (head_dim == kD)
-        return decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new,
-                                        window_len, window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size,
-                                        num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                        heads_per_mask_row, flags, T_device, lse, lse_entry);
-    if (head_dim != mustafar_hd64::kD) return MUSTAFAR_EINVAL;
-    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;   // as mustafar_decode_attention_hd
-    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u) || f_str == 1u) return MUSTAFAR_EINVAL;
-    const bool prof = g_prof.on && g_prof.n < g_prof.cap;
-    bool ran_extents = false;
-    const int err = mustafar_hd64::decode_extents(static_cast<hipStream_t>(stream), k_base, v_base, T_base, k_extents, v_extents, q, k_window,
-                                                  v_window, k_new, v_new, window_len, window_capacity, scores, ld_scores, out, workspace, Split_K,
-                                                  T, Batch_Size, num_key_value_groups, sqrt_d, window_len_extra, attention_mask, mask_row_stride,
-                                                  heads_per_mask_row, T_device, prof ? g_prof.ev + 4 * g_prof.n : nullptr, &ran_extents, lse,
-                                                  lse_entry);
-    if (err) return err;
-    if (prof) { g_prof.onepass++; g_prof.finish++; g_prof.n++; }
-    t_last_choice = 0 | (1 << 4) | ((ran_extents ? 6 : 5) << 8);
-    return 0;
-}
-}  // namespace
-
-extern "C" {
 
 int mustafar_decode_attention_extents(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
                                       const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
@@ -4197,9 +4175,10 @@ int mustafar_decode_attention_extents(void* stream, const mustafar_cache_view* k
                                       const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                       int heads_per_mask_row, uint32_t flags, const int32_t* T_device)
 {
-    return decode_attention_extents(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
-                                    window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
-                                    window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, nullptr, false);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    fill_extents(c, k_base, v_base, T_base, k_extents, v_extents, T_device);
+    return decode_dispatch(c);
 }
 
 int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
@@ -4210,10 +4189,11 @@ int mustafar_decode_attention_extents_hd(void* stream, const mustafar_cache_view
                                          const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                          int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim)
 {
-    return decode_attention_extents_hd(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
-                                       window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
-                                       window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, head_dim, nullptr,
-                                       false);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    fill_extents(c, k_base, v_base, T_base, k_extents, v_extents, T_device);
+    c.head_dim = head_dim;
+    return decode_dispatch(c);
 }
 
 int mustafar_decode_attention_extents_lse_hd(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
@@ -4224,11 +4204,16 @@ int mustafar_decode_attention_extents_lse_hd(void* stream, const mustafar_cache_
                                              const int32_t* window_len_extra, const void* attention_mask, int64_t mask_row_stride,
                                              int heads_per_mask_row, uint32_t flags, const int32_t* T_device, int head_dim, float* lse)
 {
-    return decode_attention_extents_hd(stream, k_base, v_base, T_base, k_extents, v_extents, q, k_window, v_window, k_new, v_new, window_len,
-                                       window_capacity, scores, ld_scores, out, workspace, Split_K, T, Batch_Size, num_key_value_groups, sqrt_d,
-                                       window_len_extra, attention_mask, mask_row_stride, heads_per_mask_row, flags, T_device, head_dim, lse,
-                                       true);
+    DecodeCall c;
+    MUSTAFAR_FILL_COMMON(c);
+    fill_extents(c, k_base, v_base, T_base, k_extents, v_extents, T_device);
+    c.head_dim = head_dim;
+    c.lse = lse;
+    c.lse_entry = true;
+    return decode_dispatch(c);
 }
+
+#undef MUSTAFAR_FILL_COMMON
 
 int mustafar_merge_attention_states(void* stream, const void* outs, int64_t out_part_stride, const float* lses, int64_t lse_part_stride,
                                     int n_parts, int Batch_Size, int head_dim, void* out, float* lse_out)
@@ -4259,8 +4244,8 @@ int mustafar_merge_attention_states(void* stream, const void* outs, int64_t out_
 
 int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint32_t flags)
 {
-    const uint32_t f_eng = flags & 7u, f_str = (flags >> 4) & 3u;
-    if (f_eng > 3u || f_str > 2u || (flags & ~0x37u)) return 0;
+    uint32_t f_eng, f_str;
+    if (!parse_flags(flags, &f_eng, &f_str)) return 0;
     if (f_str == 1u || (f_str == 0u && onepass_mode() == 0)) return 0;   // two launches asked for (by the call or by the process default)
     // rows so long that four blocks per workgroup leave more slabs than the row kernel folds (T > ~127 k tokens; ld_scores >= T
     // stands in for T): decode_attention then gives a workgroup more blocks, which may straddle extents -> not served

@@ -146,6 +146,26 @@ def append_compressed(old: list, new: list, heads: int, old_tokens: int, new_tok
     return [bmp, idx, FlatStreams(per_head), off]
 
 
+def mask_args(attention_mask: Optional[torch.Tensor], bsz: int, columns: int, dev, row_len: Optional[int] = None, exact: bool = False):
+    """The additive fp16 mask of a fused call, checked: `(mask, row stride)` with `mask` the tensor whose address the call takes (the
+    caller holds it until the call is issued), or `(None, 0)`.  The mask is [bsz, 1, 1, >= columns], `columns` being what the kernels
+    read; a column slice of a wider mask keeps its rows the full row apart (rows need no alignment).  `row_len`: the row length the
+    error names (the hook's kv_seq_len; default `columns`), which the rows must have exactly when `exact` -- an eager step.  A replayed
+    graph reads more columns as its window grows, so there only the lower bound holds."""
+    if attention_mask is None:
+        return None, 0
+    if row_len is None:
+        row_len = columns
+    if attention_mask.dim() != 4 or attention_mask.shape[:3] != (bsz, 1, 1) or attention_mask.shape[3] < columns or \
+            (exact and attention_mask.shape[3] != row_len):
+        raise ValueError(f"Attention mask should be of size {(bsz, 1, 1, row_len)}, but is {tuple(attention_mask.size())}")   # :294-297
+    if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
+        raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
+    if attention_mask.stride(3) != 1:
+        attention_mask = attention_mask.contiguous()
+    return attention_mask, (attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3])
+
+
 class Window:
     """Dense local window with spare capacity: `buf` [B, Hkv, cap, D], the first `len` rows are valid (api="fused")."""
 
@@ -337,6 +357,46 @@ class MustafarAttention:
         pool[key] = (sc, ws)
         return sc, ws
 
+    def _decode_operands(self, query_states, T, window=None, step_counter=None, mask=(None, 0)):
+        """What every fused entry point takes behind its cache arguments (`_lib._DECODE_TAIL`: q ... flags) for a launch sized for `T`
+        compressed tokens, with the scratch and the output it names.  window: `(k_window, v_window, k_new, v_new, window_len,
+        window_capacity)`, or None for a window-less call: null pointers and zero lengths.  mask: what `mask_args` returned.
+        Returns `(out, operands, keep)`; `keep` holds the tensors whose addresses the operands carry until the call is issued."""
+        bsz, D = query_states.shape[0], query_states.shape[3]
+        BH, groups = bsz * self.num_heads, self.num_key_value_groups
+        dev = query_states.device
+        L = _lib.load()
+        # (the head_dim-64 kernel picks its own split; at head_dim 128 the _hd form is mustafar_decode_workspace_bytes)
+        split = 1 if D == 64 or not T else L.mustafar_value_pick_split_k(128, 1, T, BH, groups)
+        ws_bytes = L.mustafar_decode_workspace_bytes_hd(T, BH, groups, split, D)
+        k_win, v_win, kn, vn, w_len, cap = window if window is not None else (None, None, None, None, 0, 0)
+        ld = (T + cap + 31) // 32 * 32   # rows on 64-byte lines of their own (one-pass form: mustafar_hip.h)
+        scores, ws = self._scratch(dev, BH, ld, ws_bytes)
+        out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
+        q = query_states if query_states.is_contiguous() else query_states.contiguous()
+        p = lambda t: t.data_ptr() if t is not None else None
+        operands = (q.data_ptr(), p(k_win), p(v_win), p(kn), p(vn), w_len, cap, scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(),
+                    split, T, BH, groups, math.sqrt(D), p(step_counter), p(mask[0]), mask[1], self.num_heads,
+                    _lib.ENGINE_FLAGS[self.cfg.engine] | _lib.STRUCTURE_FLAGS[self.cfg.structure])
+        return out, operands, (q, kn, vn, mask[0])
+
+    def _step_operands(self, query_states, key_states, value_states, k_w, v_w, T, kv_seq_len, step_counter, attention_mask):
+        """`_decode_operands` of a decode step: reserves the step's row in both windows and checks the mask.  T: the compressed tokens
+        the launch is sized for.  Returns `(out, operands, keep, w_len)`."""
+        w_len = k_w.len + 1
+        k_w.reserve(w_len)
+        v_w.reserve(w_len)
+        if k_w.cap != v_w.cap:
+            raise RuntimeError("key/value windows must have the same capacity")
+        kn = key_states if key_states.is_contiguous() else key_states.contiguous()
+        vn = value_states if value_states.is_contiguous() else value_states.contiguous()
+        if query_states.shape[3] == 64 and kn.data_ptr() % 16:   # (the head_dim-64 kernel reads the new key row as 16-byte pieces)
+            kn = kn.clone()
+        # a replayed graph reads more columns as the window grows: up to the window capacity (the bound ld_scores gets too)
+        mask = mask_args(attention_mask, query_states.shape[0], T + (w_len if step_counter is None else k_w.cap), query_states.device,
+                         kv_seq_len, exact=step_counter is None)
+        return self._decode_operands(query_states, T, (k_w.buf, v_w.buf, kn, vn, w_len, k_w.cap), step_counter, mask) + (w_len,)
+
     def decode_fused(self, query_states, key_states, value_states, past, step_counter: Optional[torch.Tensor] = None,
                      attention_mask: Optional[torch.Tensor] = None, t_device: Optional[torch.Tensor] = None,
                      t_capacity: Optional[int] = None, defer_trigger: bool = False, return_lse: bool = False):
@@ -392,7 +452,7 @@ class MustafarAttention:
         cfg = self.cfg
         bsz, _, q_len, D = query_states.shape
         assert q_len == 1 and (D == 128 or (D == 64 and self.head_dim == 64))
-        BH, Bkv, groups = bsz * self.num_heads, bsz * self.num_key_value_heads, self.num_key_value_groups
+        Bkv, groups = bsz * self.num_key_value_heads, self.num_key_value_groups
         k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
         C_used = C
         if t_device is not None:   # the launch is sized for the capacity; the kernels read the tokens in use from `t_device`
@@ -402,39 +462,12 @@ class MustafarAttention:
                 raise ValueError("decode_fused: t_device needs an arena cache and t_capacity = compressed length + a multiple of 256, beyond the base tokens")
             C = t_capacity
         kv_seq_len = past[-1] + 1
-        w_len = k_w.len + 1
-        k_w.reserve(w_len)
-        v_w.reserve(w_len)
+        # (keep: the tensors behind the addresses in `tail`, alive until the call below is issued)
+        out, tail, keep, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, C, kv_seq_len, step_counter,
+                                                     attention_mask)
+        ld, flags = tail[8], tail[-1]
         dev = query_states.device
         L = _lib.load()
-        if D == 64:   # the head_dim-64 kernel picks its own split (mustafar_decode_attention_hd)
-            split = 1
-            ws_bytes = L.mustafar_decode_workspace_bytes_hd(C, BH, groups, split, D)
-        else:
-            split = L.mustafar_value_pick_split_k(128, 1, C, BH, groups) if C else 1
-            ws_bytes = L.mustafar_decode_workspace_bytes(C, BH, groups, split)
-        ld = (C + max(k_w.cap, v_w.cap) + 31) // 32 * 32   # rows on 64-byte lines of their own (one-pass form: mustafar_hip.h)
-        scores, ws = self._scratch(dev, BH, ld, ws_bytes)
-        out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
-        q = query_states if query_states.is_contiguous() else query_states.contiguous()
-        kn = key_states if key_states.is_contiguous() else key_states.contiguous()
-        vn = value_states if value_states.is_contiguous() else value_states.contiguous()
-        if D == 64 and kn.data_ptr() % 16:   # (the head_dim-64 kernel reads the new key row as 16-byte pieces)
-            kn = kn.clone()
-        if k_w.cap != v_w.cap:
-            raise RuntimeError("key/value windows must have the same capacity")
-        mask_ptr, mask_stride = None, 0
-        if attention_mask is not None:
-            # a replayed graph reads more columns as the window grows: up to the window capacity (the bound ld_scores gets too)
-            need = C + w_len if step_counter is None else C + k_w.cap
-            if attention_mask.dim() != 4 or attention_mask.shape[:3] != (bsz, 1, q_len) or attention_mask.shape[3] < need or \
-                    (step_counter is None and attention_mask.shape[3] != kv_seq_len):
-                raise ValueError(f"Attention mask should be of size {(bsz, 1, q_len, kv_seq_len)}, but is {tuple(attention_mask.size())}")   # :294-297
-            if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
-                raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
-            if attention_mask.stride(3) != 1:
-                attention_mask = attention_mask.contiguous()
-            mask_ptr, mask_stride = attention_mask.data_ptr(), attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3]
         p = lambda t: t.data_ptr() if t is not None else None
         use_arena = isinstance(k_c, CompressedArena)
         if use_arena:            # a failed asynchronous append is reported before the cache is read again (no host stall)
@@ -446,11 +479,6 @@ class MustafarAttention:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("decode_fused: extent tables missing under graph capture (to_fused() creates them)")
                 k_c.ext_table, v_c.ext_table
-        tail = (q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(), w_len, k_w.cap,
-                scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(), split, C, BH, groups, math.sqrt(D),
-                step_counter.data_ptr() if step_counter is not None else None, mask_ptr, mask_stride, self.num_heads,
-                _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure])
-        flags = tail[-1]
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             if lse is not None:
@@ -570,10 +598,8 @@ class MustafarAttention:
                             defer_trigger, lse=None):
         """decode_fused for ExtentCache64 caches: the plain D = 64 launch while the cache is its base alone, the extents launch once
         extents exist or whenever `t_device` is passed; the trigger through run_triggers' batched form."""
-        cfg = self.cfg
-        bsz, _, q_len, D = query_states.shape
+        _, _, q_len, D = query_states.shape
         assert q_len == 1 and D == 64
-        BH, groups = bsz * self.num_heads, self.num_key_value_groups
         k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
         cap_T = C
         if t_device is not None:
@@ -585,37 +611,10 @@ class MustafarAttention:
                                  "table's entries), not below the compressed length")
             cap_T = t_capacity
         kv_seq_len = past[-1] + 1
-        w_len = k_w.len + 1
-        k_w.reserve(w_len)
-        v_w.reserve(w_len)
-        if k_w.cap != v_w.cap:
-            raise RuntimeError("key/value windows must have the same capacity")
+        out, tail, keep, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, cap_T, kv_seq_len, step_counter,
+                                                     attention_mask)
         dev = query_states.device
         L = _lib.load()
-        ws_bytes = L.mustafar_decode_workspace_bytes_hd(cap_T, BH, groups, 1, D)
-        ld = (cap_T + k_w.cap + 31) // 32 * 32
-        scores, ws = self._scratch(dev, BH, ld, ws_bytes)
-        out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
-        q = query_states if query_states.is_contiguous() else query_states.contiguous()
-        kn = key_states if key_states.is_contiguous() else key_states.contiguous()
-        vn = value_states if value_states.is_contiguous() else value_states.contiguous()
-        if kn.data_ptr() % 16:
-            kn = kn.clone()
-        mask_ptr, mask_stride = None, 0
-        if attention_mask is not None:
-            need = cap_T + w_len if step_counter is None else cap_T + k_w.cap
-            if attention_mask.dim() != 4 or attention_mask.shape[:3] != (bsz, 1, q_len) or attention_mask.shape[3] < need or \
-                    (step_counter is None and attention_mask.shape[3] != kv_seq_len):
-                raise ValueError(f"Attention mask should be of size {(bsz, 1, q_len, kv_seq_len)}, but is {tuple(attention_mask.size())}")
-            if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
-                raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
-            if attention_mask.stride(3) != 1:
-                attention_mask = attention_mask.contiguous()
-            mask_ptr, mask_stride = attention_mask.data_ptr(), attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3]
-        tail = (q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(), w_len, k_w.cap,
-                scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(), 1, cap_T, BH, groups, math.sqrt(D),
-                step_counter.data_ptr() if step_counter is not None else None, mask_ptr, mask_stride, self.num_heads,
-                _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure])
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             if lse is not None and isinstance(k_c, ExtentCache64):   # (T == T_base: the base alone, as the plain launch below)

@@ -16,27 +16,13 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence
 
 import torch
 
 from . import _lib
 from .cache import CompressedArena
 from .cache64 import ExtentCache64
-
-
-def _mask_args(attention_mask: Optional[torch.Tensor], bsz: int, columns: int, dev) -> Tuple[Optional[int], int]:
-    """Pointer and row stride of an additive fp16 mask [bsz, 1, 1, >= columns] -- usually a column slice of the step's mask, whose
-    rows stay the full row apart (mask rows need no alignment: the pointer simply moves to the segment's first column)."""
-    if attention_mask is None:
-        return None, 0
-    if attention_mask.dim() != 4 or attention_mask.shape[:3] != (bsz, 1, 1) or attention_mask.shape[3] < columns:
-        raise ValueError(f"Attention mask should be of size {(bsz, 1, 1, columns)}, but is {tuple(attention_mask.size())}")
-    if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
-        raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
-    if attention_mask.stride(3) != 1:
-        attention_mask = attention_mask.contiguous()
-    return attention_mask.data_ptr(), (attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3])
 
 
 def _flat_stream(c):
@@ -175,23 +161,14 @@ def decode_segment(attn, query_states: torch.Tensor, k_cache, v_cache=None, toke
         raise ValueError("decode_segment: a per-sequence segment is (k_cache, v_cache, tokens)")
     if tokens <= 0 or tokens % 64:
         raise ValueError(f"decode_segment: a segment holds a positive multiple of 64 tokens (got {tokens})")
-    cfg = attn.cfg
     if D == 128:   # the LSE comes from the one-pass forms (mustafar_hip.h)
         attn._lse_served(tokens)
-    BH, groups = bsz * H, attn.num_key_value_groups
+    from .hook import mask_args
     dev = query_states.device
     L = _lib.load()
-    split = 1 if D == 64 else L.mustafar_value_pick_split_k(128, 1, tokens, BH, groups)
-    ws_bytes = L.mustafar_decode_workspace_bytes_hd(tokens, BH, groups, split, D)
-    ld = (tokens + 31) // 32 * 32
-    scores, ws = attn._scratch(dev, BH, ld, ws_bytes)
-    out = torch.empty((bsz, H, 1, D), dtype=torch.float16, device=dev)
+    # no window argument at all: the window-less form of the two entry points with an LSE (keep: the tensors `tail` points into)
+    out, tail, keep = attn._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
     lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-    q = query_states if query_states.is_contiguous() else query_states.contiguous()
-    mask_ptr, mask_stride = _mask_args(attention_mask, bsz, tokens, dev)
-    # no window argument at all: the window-less form of the two entry points with an LSE
-    tail = (q.data_ptr(), None, None, None, None, 0, 0, scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(), split, tokens, BH, groups,
-            math.sqrt(D), None, mask_ptr, mask_stride, H, _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure])
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         if isinstance(k_cache, (CompressedArena, ExtentCache64)):
