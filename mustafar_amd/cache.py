@@ -29,7 +29,7 @@ trigger paid one copy of the cache, a round of driver allocations and -- because
 graph (c3: 16 + 11 ms per trigger against 1.4 ms per step).  `append_extent_pair` instead compresses the 256 tokens of a trigger into
 a small arena of their own, an EXTENT, and lists its view in a device table next to the base arena (`ext_table`).  Nothing that is
 already compressed is read, written or moved; the pair form of the one-pass decode launch takes the blocks behind the base tokens
-from the table (mustafar_decode_attention_extents), so the base pointers, the table pointer and therefore a graph captured ahead
+from the table (the extents form of the fused decode call: hook._call_decode), so the base pointers, the table pointer and therefore a graph captured ahead
 stay valid across the trigger.  `tokens` / the four arrays keep describing the BASE; `total_tokens` counts the extents too,
 `to_reference()` concatenates, and after `MAX_EXTENTS` triggers (512: 128 k generated tokens) or when a launch form that cannot read extents is asked for
 `consolidate()` re-houses everything into one base again.
@@ -228,6 +228,15 @@ class CompressedArena:
 
     def view_ptr(self):
         return ctypes.byref(self._view)
+
+    def decode_args(self, v_arena: "CompressedArena", tables: bool):
+        """How this K arena and its V arena arrive at a fused decode call (hook._call_decode): `(k_view_ptr, v_view_ptr, T_base,
+        k_table, v_table)` -- the device tables of the extents when `tables`, else None -- and the tensors to keep until the call is
+        issued (none: the arenas own everything named)."""
+        self.poll()      # a failed asynchronous append is reported before the cache is read again (no host stall)
+        v_arena.poll()
+        kt, vt = (self.ext_table.data_ptr(), v_arena.ext_table.data_ptr()) if tables else (None, None)
+        return (self.view_ptr(), v_arena.view_ptr(), self.tokens, kt, vt), ()
 
     def bytes_in_use(self) -> int:
         t = self.tokens * self.TILES_PER_TOKEN

@@ -8,7 +8,7 @@ trigger.  `ExtentCache64` keeps one side (K or V) of one layer the way `Compress
     to it in place, so it needs no spare room and no strides;
   * a trigger compresses its 256 window rows into a small cache of their own, an EXTENT (mustafar_trigger_compress_batch_hd: one launch
     per layer from the raw rows), and lists the extent's view in a DEVICE table of `MAX_EXTENTS` mustafar_cache_view entries that
-    mustafar_decode_attention_extents_hd reads.  The table is created with the cache -- before any graph can name it (a table created
+    the extents form of the fused decode call reads (hook._call_decode).  The table is created with the cache -- before any graph can name it (a table created
     inside a capture would live in the graph's pool and be zero-filled again by every replay) -- and an entry is written once;
   * the extents of ONE trigger of ALL layers are carved from one pooled allocation (`ExtentPool64`) together with the layers' status
     words `[flag, K lengths, V lengths]`, which one copy brings to the host.  Regions are housed tight -- the base's measured halfs per
@@ -107,7 +107,7 @@ class ExtentPool64:
 
 
 class ExtentCache64:
-    MAX_EXTENTS = 512   # entries of the device table (mustafar_decode_attention_extents_hd takes at most 512)
+    MAX_EXTENTS = 512   # entries of the device table (the extents form of the fused decode call takes at most 512)
 
     def __init__(self, base: list, which: str, heads: int, tokens: int):
         """base: the reference-layout `[bitmaps, idxs, FlatStreams, nz_offset]` of `tokens` tokens (a multiple of 256)."""
@@ -129,6 +129,15 @@ class ExtentCache64:
 
     def view_ptr(self):
         return ctypes.byref(self.base_view)
+
+    def decode_args(self, v_cache: "ExtentCache64", tables: bool):
+        """How this K cache and its V cache arrive at a fused decode call (hook._call_decode): `(k_view_ptr, v_view_ptr, T_base,
+        k_table, v_table)` when `tables`, else the eight arrays of the two bases (the plain D = 64 launch: the base alone) -- and the
+        tensors to keep until the call is issued (none: the caches own everything named)."""
+        if tables:
+            return (self.view_ptr(), v_cache.view_ptr(), self.tokens, self.table.data_ptr(), v_cache.table.data_ptr()), ()
+        kb, vb = self.base_view, v_cache.base_view
+        return (kb.bmp, kb.nz, kb.idx, kb.nz_offset, vb.bmp, vb.nz, vb.idx, vb.nz_offset), ()
 
     def slot_ptr(self, i: int) -> int:
         return self.table.data_ptr() + i * VIEW_BYTES

@@ -15,7 +15,7 @@ compressed_length, kv_seq_len) (:445), k_compressed = [bitmaps, idxs, nzs(list p
 `torch.cat` of the per-head streams on every call :274/:314, 8-row outputs sliced to row 0 :275/:315).
 `api="native"` calls the same two entry points un-padded (N = 1) and keeps the packed stream of all heads in
 one flat tensor beside the list, so nothing is re-copied per step.
-`api="fused"` replaces the PyTorch glue between the two SpMVs by `mustafar_decode_attention` (C ABI extension):
+`api="fused"` replaces the PyTorch glue between the two SpMVs by the fused decode call of the C ABI (`_call_decode`):
 the local window lives in a preallocated buffer that is appended in place, and one call per layer launches
 key SpMV (+ window scores) -> softmax -> value SpMV (+ window p.V partials) -> sum.  All three produce the same output.
 """
@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -166,6 +166,85 @@ def mask_args(attention_mask: Optional[torch.Tensor], bsz: int, columns: int, de
     return attention_mask, (attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3])
 
 
+def _ld_scores(columns: int) -> int:
+    """Row pitch of the score scratch for `columns` = compressed tokens + window capacity: rows on 64-byte lines of their own
+    (one-pass form: mustafar_hip.h)."""
+    return (columns + 31) // 32 * 32
+
+
+class DecodeOperands(NamedTuple):
+    """What `MustafarAttention._decode_operands` builds for one fused call."""
+    out: torch.Tensor    # [bsz, num_heads, 1, D] fp16, written by the call
+    tail: tuple          # the arguments every entry point takes behind its cache arguments (`_lib._DECODE_TAIL`: q ... flags)
+    keep: tuple          # the tensors whose addresses `tail` carries, alive until the call is issued
+    ld: int              # `ld_scores` as in `tail`
+    flags: int           # `flags` as in `tail`
+
+
+def _flat_stream(c):
+    """The packed stream of all heads of a reference-layout cache as one tensor: a FlatStreams' `.flat`, a plain tensor, or a plain
+    list of per-head tensors, concatenated here."""
+    nz = c[2]
+    return nz.flat if hasattr(nz, "flat") else (nz if isinstance(nz, torch.Tensor) else torch.cat(list(nz)))
+
+
+def _list_decode_args(k_c, v_c):
+    """How two reference-layout caches `[bitmaps, idxs, nzs, nz_offset]` arrive at a fused decode call: the eight array addresses
+    (bitmaps, stream, idxs, nz_offset of K, then of V) and the tensors to keep until the call is issued.  None (nothing compressed
+    yet) and empty tensors become null addresses."""
+    if k_c is None:
+        return (None,) * 8, ()
+    kz, vz = _flat_stream(k_c), _flat_stream(v_c)
+    p = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    return (p(k_c[0]), p(kz), p(k_c[1]), p(k_c[3]), p(v_c[0]), p(vz), p(v_c[1]), p(v_c[3])), (kz, vz)
+
+
+def _call_decode(k_c, v_c, T: int, ops: DecodeOperands, D: int, t_device: Optional[torch.Tensor] = None,
+                 lse: Optional[torch.Tensor] = None) -> None:
+    """Issue ONE fused decode call: the only place that chooses among the seven entry points of the C ABI.  k_c / v_c: the two caches
+    (None: nothing compressed yet); T: the compressed tokens the launch is sized for (what `ops` was built with); t_device: the
+    tokens in use as a device int, or None; lse: the fp32 tensor the row kernel fills, or None.  Each cache kind says how it
+    arrives (`decode_args` of the two cache classes, `_list_decode_args`): eight arrays, or base views + T_base + device tables.
+
+        cache                            no LSE                                              LSE
+        list / None                      mustafar_decode_attention (D 128) / _hd (D 64)      _lse_hd
+        CompressedArena, T == its base   _view                                               _extents_lse_hd, null tables
+        CompressedArena, T > its base    _extents (tables, t_device)                         _extents_lse_hd (tables, t_device)
+        ExtentCache64, base alone        _hd over the eight arrays of the two bases          _extents_lse_hd (tables, t_device)
+        ExtentCache64, extents/t_device  _extents_hd (tables, t_device)                      _extents_lse_hd (tables, t_device)
+
+    Whether the launch form asked for can read a grown arena at all is the caller's business (`_decode_fused`)."""
+    L = _lib.load()
+    extent64 = isinstance(k_c, ExtentCache64)
+    if isinstance(k_c, CompressedArena):
+        cache, keep = k_c.decode_args(v_c, tables=T > k_c.tokens)
+    elif extent64:   # (with an LSE and T == T_base the extents form reads the base alone, as the plain launch does)
+        cache, keep = k_c.decode_args(v_c, tables=lse is not None or bool(k_c.extents) or t_device is not None)
+    else:
+        cache, keep = _list_decode_args(k_c, v_c)
+    arrays = len(cache) == 8
+    td = t_device.data_ptr() if t_device is not None else None
+    dev = ops.out.device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if arrays and lse is not None:
+            err = L.mustafar_decode_attention_lse_hd(st, *cache, *ops.tail, D, lse.data_ptr())
+        elif arrays and D == 64:
+            err = L.mustafar_decode_attention_hd(st, *cache, *ops.tail, D)
+        elif arrays:
+            err = L.mustafar_decode_attention(st, *cache, *ops.tail)
+        elif lse is not None:
+            err = L.mustafar_decode_attention_extents_lse_hd(st, *cache, *ops.tail, td, D, lse.data_ptr())
+        elif extent64:
+            err = L.mustafar_decode_attention_extents_hd(st, *cache, *ops.tail, td, D)
+        elif cache[3] is None:   # an arena that is its base alone: the two views
+            err = L.mustafar_decode_attention_view(st, cache[0], cache[1], *ops.tail)
+        else:
+            err = L.mustafar_decode_attention_extents(st, *cache, *ops.tail, td)
+    _lib.check(err, "mustafar_decode_attention")
+    del keep   # (alive until here: the call has been issued)
+
+
 class Window:
     """Dense local window with spare capacity: `buf` [B, Hkv, cap, D], the first `len` rows are valid (api="fused")."""
 
@@ -250,10 +329,30 @@ class MustafarAttention:
         """Margin an arena is housed with: none where the cache grows by extents (nothing is ever appended in place), the
         configured one where a trigger appends in place (other GQA shapes, two launches asked for)."""
         cfg = self.cfg
-        if cfg.extents and _lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, 32,
-                                                                     _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure]):
+        if cfg.extents and self._reads_extents(32):
             return 0.0
         return cfg.arena_slack
+
+    def _flags(self) -> int:
+        """`flags` of every fused call of this instance: its FMA engine and launch structure (MUSTAFAR_FLAG_* in include/mustafar_hip.h)."""
+        return _lib.ENGINE_FLAGS[self.cfg.engine] | _lib.STRUCTURE_FLAGS[self.cfg.structure]
+
+    def _reads_extents(self, columns: int) -> bool:
+        """Whether this instance's launch form reads a cache that grows by extents, for scores of `columns` columns (compressed tokens +
+        window capacity)."""
+        return bool(_lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, _ld_scores(columns), self._flags()))
+
+    def _kth(self, D: int) -> Tuple[int, int]:
+        """`(kth_k, kth_v)`: the prune rule's kth (model :97) for K and V rows of D channels at the configured sparsities."""
+        return compression.kth_from_sparsity(self.cfg.k_sparsity, D), compression.kth_from_sparsity(self.cfg.v_sparsity, D)
+
+    def _compress_front(self, k_rows: torch.Tensor, v_rows: torch.Tensor):
+        """The reference's trigger body on rows [0, 256) of a K and a V window [B, Hkv, >= 256, D]: prune (:325-326), compress
+        (:328-337) -> `(k_new, v_new)`, two reference-layout caches of 256 tokens."""
+        Bkv, D = k_rows.shape[0] * k_rows.shape[1], k_rows.shape[3]
+        k_blk = self.dh_prune_key(k_rows[:, :, :256, :]).reshape(Bkv, -1, D)                             # :325
+        v_blk = self.dh_prune_value(v_rows[:, :, :256, :]).reshape(Bkv, -1, D)                           # :326
+        return _compress(k_blk, "key"), _compress(v_blk, "value")                                       # :328-337
 
     def _ws(self, device):
         if self.Reduction_Workspace is None or self.Reduction_Workspace.device != device:
@@ -267,42 +366,28 @@ class MustafarAttention:
         total_batch_kv = bsz * self.num_key_value_heads
         # :416 computes ((L - R)//256)*256, which is -256 for L < R; clamp at 0.
         compressed_length = max(0, ((kv_seq_len - self.cfg.residual_length) // 256) * 256)
-        if compressed_length != 0 and self.cfg.arena and self.cfg.api == "fused":
-            # straight from the raw K / V into appendable storage: prune thresholds in registers, no pruned copy (:419-434).
+        if compressed_length == 0:
+            return (None, key_states, None, value_states, 0, kv_seq_len)
+        arena = self.cfg.arena and self.cfg.api == "fused"
+        if arena or self.cfg.hd64_raw_prefill:
             # In the model K and V arrive as transpose(1, 2) views of [B, L, H, D] projections (model :224-226; RoPE keeps the
-            # strides): the kernel reads rows of 128 contiguous halfs per head, so such views are made contiguous first.
+            # strides): the kernels read rows of D contiguous halfs per head, so such views are made contiguous first.
             ks = key_states if key_states.is_contiguous() else key_states.contiguous()
             vs = value_states if value_states.is_contiguous() else value_states.contiguous()
-            k_compressed, v_compressed = CompressedArena.from_raw_pair(
-                ks, vs, compressed_length, compression.kth_from_sparsity(self.cfg.k_sparsity, D),
-                compression.kth_from_sparsity(self.cfg.v_sparsity, D), None, self._slack())
+            if arena:
+                # straight from the raw K / V into appendable storage: prune thresholds in registers, no pruned copy (:419-434)
+                k_compressed, v_compressed = CompressedArena.from_raw_pair(ks, vs, compressed_length, *self._kth(D), None, self._slack())
+            else:
+                # head_dim 64 from the raw rows: one chunked compression launch, one host wait, one gather per side
+                k_compressed, v_compressed = compression.compress_raw_pair_hd64(ks, vs, compressed_length, *self._kth(D))
             del ks, vs
-            k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()             # :427
-            v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()           # :435
-        elif compressed_length != 0 and self.cfg.hd64_raw_prefill:
-            # head_dim 64 from the raw rows: one chunked compression launch, one host wait, one gather per side (transposed views are
-            # made contiguous first, as for the arena above)
-            ks = key_states if key_states.is_contiguous() else key_states.contiguous()
-            vs = value_states if value_states.is_contiguous() else value_states.contiguous()
-            k_compressed, v_compressed = compression.compress_raw_pair_hd64(
-                ks, vs, compressed_length, compression.kth_from_sparsity(self.cfg.k_sparsity, D),
-                compression.kth_from_sparsity(self.cfg.v_sparsity, D))
-            del ks, vs
-            k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()             # :427
-            v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()           # :435
-        elif compressed_length != 0:
+        else:
             k_pruned = self.dh_prune_key(key_states[:, :, :compressed_length, :])                     # :419
             v_pruned = self.dh_prune_value(value_states[:, :, :compressed_length, :])                 # :420
-            if self.cfg.arena and self.cfg.api == "fused":   # (unreachable since the branch above takes every arena prefill; kept for callers that set arena late)
-                k_compressed = CompressedArena.from_pruned(k_pruned.reshape(total_batch_kv, -1, D), "key", None, self._slack())
-                v_compressed = CompressedArena.from_pruned(v_pruned.reshape(total_batch_kv, -1, D), "value", None, self._slack())
-            else:
-                k_compressed = _compress(k_pruned.reshape(total_batch_kv, -1, D), "key")              # :422-426
-                v_compressed = _compress(v_pruned.reshape(total_batch_kv, -1, D), "value")            # :430-434
-            k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()             # :427
-            v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()           # :435
-        else:
-            k_compressed, k_local_window, v_compressed, v_local_window = None, key_states, None, value_states
+            k_compressed = _compress(k_pruned.reshape(total_batch_kv, -1, D), "key")                  # :422-426
+            v_compressed = _compress(v_pruned.reshape(total_batch_kv, -1, D), "value")                # :430-434
+        k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()                 # :427
+        v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()               # :435
         return (k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, kv_seq_len)   # :445
 
     def prefill(self, query_states, key_states, value_states):
@@ -361,7 +446,7 @@ class MustafarAttention:
         """What every fused entry point takes behind its cache arguments (`_lib._DECODE_TAIL`: q ... flags) for a launch sized for `T`
         compressed tokens, with the scratch and the output it names.  window: `(k_window, v_window, k_new, v_new, window_len,
         window_capacity)`, or None for a window-less call: null pointers and zero lengths.  mask: what `mask_args` returned.
-        Returns `(out, operands, keep)`; `keep` holds the tensors whose addresses the operands carry until the call is issued."""
+        Returns a `DecodeOperands`; its `keep` holds the tensors whose addresses the operands carry until the call is issued."""
         bsz, D = query_states.shape[0], query_states.shape[3]
         BH, groups = bsz * self.num_heads, self.num_key_value_groups
         dev = query_states.device
@@ -370,19 +455,18 @@ class MustafarAttention:
         split = 1 if D == 64 or not T else L.mustafar_value_pick_split_k(128, 1, T, BH, groups)
         ws_bytes = L.mustafar_decode_workspace_bytes_hd(T, BH, groups, split, D)
         k_win, v_win, kn, vn, w_len, cap = window if window is not None else (None, None, None, None, 0, 0)
-        ld = (T + cap + 31) // 32 * 32   # rows on 64-byte lines of their own (one-pass form: mustafar_hip.h)
+        ld, flags = _ld_scores(T + cap), self._flags()
         scores, ws = self._scratch(dev, BH, ld, ws_bytes)
         out = torch.empty((bsz, self.num_heads, 1, D), dtype=torch.float16, device=dev)
         q = query_states if query_states.is_contiguous() else query_states.contiguous()
         p = lambda t: t.data_ptr() if t is not None else None
-        operands = (q.data_ptr(), p(k_win), p(v_win), p(kn), p(vn), w_len, cap, scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(),
-                    split, T, BH, groups, math.sqrt(D), p(step_counter), p(mask[0]), mask[1], self.num_heads,
-                    _lib.ENGINE_FLAGS[self.cfg.engine] | _lib.STRUCTURE_FLAGS[self.cfg.structure])
-        return out, operands, (q, kn, vn, mask[0])
+        tail = (q.data_ptr(), p(k_win), p(v_win), p(kn), p(vn), w_len, cap, scores.data_ptr(), ld, out.data_ptr(), ws.data_ptr(),
+                split, T, BH, groups, math.sqrt(D), p(step_counter), p(mask[0]), mask[1], self.num_heads, flags)
+        return DecodeOperands(out, tail, (q, kn, vn, mask[0]), ld, flags)
 
     def _step_operands(self, query_states, key_states, value_states, k_w, v_w, T, kv_seq_len, step_counter, attention_mask):
         """`_decode_operands` of a decode step: reserves the step's row in both windows and checks the mask.  T: the compressed tokens
-        the launch is sized for.  Returns `(out, operands, keep, w_len)`."""
+        the launch is sized for.  Returns `(operands, w_len)`."""
         w_len = k_w.len + 1
         k_w.reserve(w_len)
         v_w.reserve(w_len)
@@ -395,7 +479,7 @@ class MustafarAttention:
         # a replayed graph reads more columns as the window grows: up to the window capacity (the bound ld_scores gets too)
         mask = mask_args(attention_mask, query_states.shape[0], T + (w_len if step_counter is None else k_w.cap), query_states.device,
                          kv_seq_len, exact=step_counter is None)
-        return self._decode_operands(query_states, T, (k_w.buf, v_w.buf, kn, vn, w_len, k_w.cap), step_counter, mask) + (w_len,)
+        return self._decode_operands(query_states, T, (k_w.buf, v_w.buf, kn, vn, w_len, k_w.cap), step_counter, mask), w_len
 
     def decode_fused(self, query_states, key_states, value_states, past, step_counter: Optional[torch.Tensor] = None,
                      attention_mask: Optional[torch.Tensor] = None, t_device: Optional[torch.Tensor] = None,
@@ -429,8 +513,8 @@ class MustafarAttention:
         if return_lse:
             self._lse_served(past[4] if t_capacity is None else t_capacity)
             lse = torch.empty((query_states.shape[0], self.num_heads), dtype=torch.float32, device=query_states.device)
-        inner = self._decode_fused_ext64 if self.cfg.hd64_extents else self._decode_fused
-        out, new = inner(query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity, defer_trigger, lse)
+        out, new = self._decode_fused(query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
+                                      defer_trigger, lse)
         return (out, lse, new) if return_lse else (out, new)
 
     def _lse_served(self, C: int) -> None:
@@ -448,113 +532,75 @@ class MustafarAttention:
 
     def _decode_fused(self, query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
                       defer_trigger, lse):
-        """decode_fused over tuple caches and arenas.  lse: None (the plain entry points), or the tensor the row kernel fills."""
+        """decode_fused over every cache kind (reference-layout lists, arenas, ExtentCache64).  lse: None (the plain entry points), or
+        the tensor the row kernel fills."""
         cfg = self.cfg
         bsz, _, q_len, D = query_states.shape
-        assert q_len == 1 and (D == 128 or (D == 64 and self.head_dim == 64))
-        Bkv, groups = bsz * self.num_key_value_heads, self.num_key_value_groups
+        assert q_len == 1 and ((D == 128 and not cfg.hd64_extents) or (D == 64 and self.head_dim == 64))
+        Bkv = bsz * self.num_key_value_heads
         k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
-        C_used = C
+        use_arena = isinstance(k_c, CompressedArena)
+        T = C   # the compressed tokens the launch is sized for
         if t_device is not None:   # the launch is sized for the capacity; the kernels read the tokens in use from `t_device`
             if step_counter is None:
                 raise ValueError("decode_fused: t_device is for captured graphs and needs step_counter (an eager call passes neither)")
-            if t_capacity is None or t_capacity < C or (t_capacity - C) % 256 or not isinstance(k_c, CompressedArena) or t_capacity <= k_c.tokens:
+            if cfg.hd64_extents:
+                if t_capacity is None or not isinstance(k_c, ExtentCache64) or t_capacity <= k_c.tokens or t_capacity < C or \
+                        (t_capacity - k_c.tokens) % 256 or (t_capacity - k_c.tokens) // 256 > k_c.MAX_EXTENTS:
+                    raise ValueError("decode_fused: t_device needs an extent cache and t_capacity = base tokens + a multiple of 256 (at most the "
+                                     "table's entries), not below the compressed length")
+            elif t_capacity is None or t_capacity < C or (t_capacity - C) % 256 or not use_arena or t_capacity <= k_c.tokens:
                 raise ValueError("decode_fused: t_device needs an arena cache and t_capacity = compressed length + a multiple of 256, beyond the base tokens")
-            C = t_capacity
+            T = t_capacity
         kv_seq_len = past[-1] + 1
-        # (keep: the tensors behind the addresses in `tail`, alive until the call below is issued)
-        out, tail, keep, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, C, kv_seq_len, step_counter,
-                                                     attention_mask)
-        ld, flags = tail[8], tail[-1]
-        dev = query_states.device
-        L = _lib.load()
-        p = lambda t: t.data_ptr() if t is not None else None
-        use_arena = isinstance(k_c, CompressedArena)
-        if use_arena:            # a failed asynchronous append is reported before the cache is read again (no host stall)
-            k_c.poll()
-            v_c.poll()
+        ops, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, T, kv_seq_len, step_counter, attention_mask)
+        if use_arena:
             if cfg.extents and (k_c._ext_table is None or v_c._ext_table is None):
                 # the extent tables must exist BEFORE a graph that names them is captured: created inside a capture they would
                 # live in the graph's pool and their zero-fill would be replayed over the entries with every step
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("decode_fused: extent tables missing under graph capture (to_fused() creates them)")
                 k_c.ext_table, v_c.ext_table
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            if lse is not None:
-                # the two entry points with an LSE: the tuple cache through its eight arrays, an arena through its base views (T == T_base:
-                # the views alone) or base views + device tables
-                if use_arena:
-                    if C > k_c.tokens and not L.mustafar_decode_reads_extents(groups, ld, flags):
-                        raise RuntimeError("decode_fused: this launch form cannot read a cache that grows by extents "
-                                           "(MustafarConfig(extents=False), or consolidate() the arenas first)")
-                    grown = C > k_c.tokens
-                    err = L.mustafar_decode_attention_extents_lse_hd(
-                        st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.ext_table.data_ptr() if grown else None,
-                        v_c.ext_table.data_ptr() if grown else None, *tail, t_device.data_ptr() if t_device is not None else None, D,
-                        lse.data_ptr())
-                else:
-                    err = L.mustafar_decode_attention_lse_hd(
-                        st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,
-                        p(v_c[0]) if C else None, p(v_c[2].flat) if C else None, p(v_c[1]) if C else None, p(v_c[3]) if C else None, *tail, D,
-                        lse.data_ptr())
-            elif use_arena and C > k_c.tokens:
-                # the cache has grown by extents (or, under a capture ahead of a trigger, is about to): base views + device tables
-                if not L.mustafar_decode_reads_extents(groups, ld, flags):
-                    # an engine / structure switch after the cache grew: this form reads ONE view -- one copy of the cache.  (Not
-                    # possible under a capture, nor for a graph captured ahead of a trigger, whose extent does not exist yet.)
-                    if torch.cuda.is_current_stream_capturing() or k_c.tokens + 256 * len(k_c.extents) < C or t_device is not None:
-                        raise RuntimeError("decode_fused: this launch form cannot read a cache that grows by extents "
-                                           "(MustafarConfig(extents=False), or consolidate() the arenas first)")
-                    k_c, v_c = k_c.consolidate(), v_c.consolidate()
-                    k_c.ext_table, v_c.ext_table
-                    err = L.mustafar_decode_attention_view(st, k_c.view_ptr(), v_c.view_ptr(), *tail)
-                else:
-                    err = L.mustafar_decode_attention_extents(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.ext_table.data_ptr(),
-                                                              v_c.ext_table.data_ptr(), *tail,
-                                                              t_device.data_ptr() if t_device is not None else None)
-            elif use_arena:
-                err = L.mustafar_decode_attention_view(st, k_c.view_ptr(), v_c.view_ptr(), *tail)
-            elif D == 64:
-                err = L.mustafar_decode_attention_hd(
-                    st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,
-                    p(v_c[0]) if C else None, p(v_c[2].flat) if C else None, p(v_c[1]) if C else None, p(v_c[3]) if C else None, *tail, D)
-            else:
-                err = L.mustafar_decode_attention(
-                    st, p(k_c[0]) if C else None, p(k_c[2].flat) if C else None, p(k_c[1]) if C else None, p(k_c[3]) if C else None,
-                    p(v_c[0]) if C else None, p(v_c[2].flat) if C else None, p(v_c[1]) if C else None, p(v_c[3]) if C else None, *tail)
-        _lib.check(err, "mustafar_decode_attention")
-        C = C_used   # (the compressed length in use: `C` above was the capacity when t_device sizes the launch)
+            # the cache has grown by extents (or, under a capture ahead of a trigger, is about to)
+            if T > k_c.tokens and not _lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, ops.ld, ops.flags):
+                # an engine / structure switch after the cache grew: this form reads ONE view -- one copy of the cache.  (Not
+                # possible under a capture, nor for a graph captured ahead of a trigger, whose extent does not exist yet; and the
+                # forms with an LSE read extents or nothing.)
+                if lse is not None or torch.cuda.is_current_stream_capturing() or k_c.tokens + 256 * len(k_c.extents) < T or \
+                        t_device is not None:
+                    raise RuntimeError("decode_fused: this launch form cannot read a cache that grows by extents "
+                                       "(MustafarConfig(extents=False), or consolidate() the arenas first)")
+                k_c, v_c = k_c.consolidate(), v_c.consolidate()   # (T == their base tokens now: the view form)
+                k_c.ext_table, v_c.ext_table
+        _call_decode(k_c, v_c, T, ops, D, t_device, lse)
+        out = ops.out
         if step_counter is not None:
             return out, (k_c, k_w, v_c, v_w, C, kv_seq_len - 1)   # lengths advance with the device counter
         k_w.len = v_w.len = w_len
+        new = (k_c, k_w, v_c, v_w, C, kv_seq_len)
         if defer_trigger:
-            # run_triggers() works on arena caches (a first trigger, C == 0, makes one when cfg.arena says so): anything else would
-            # come back with a cache of the wrong kind, or fail inside run_triggers -- refuse here
-            if not (use_arena or (cfg.arena and C == 0)):
+            # run_triggers() works on arena and extent caches (a first trigger, C == 0, makes an arena when cfg.arena says so): anything
+            # else would come back with a cache of the wrong kind, or fail inside run_triggers -- refuse here
+            if not (cfg.hd64_extents or use_arena or (cfg.arena and C == 0)):
                 raise RuntimeError("decode_fused(defer_trigger=True) needs an arena cache (MustafarConfig(arena=True)); "
                                    "tuple caches run their trigger inside the step")
-            return out, (k_c, k_w, v_c, v_w, C, kv_seq_len)
-        if (kv_seq_len - cfg.residual_length - C) % 256 == 0 and w_len >= 256:                          # :324
-            kth_k = compression.kth_from_sparsity(cfg.k_sparsity, D)
-            kth_v = compression.kth_from_sparsity(cfg.v_sparsity, D)
-            if use_arena or (cfg.arena and C == 0):
-                # prune (:325-326) + compress + append (:328-390) of the raw window rows in one launch
-                k_c, k_w, v_c, v_w, C, _ = self._trigger_one(k_c, k_w, v_c, v_w, C, kv_seq_len, kth_k, kth_v)
-                return out, (k_c, k_w, v_c, v_w, C, kv_seq_len)
-            else:
-                k_blk = self.dh_prune_key(k_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)                   # :325
-                v_blk = self.dh_prune_value(v_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)                 # :326
-                k_new, v_new = _compress(k_blk, "key"), _compress(v_blk, "value")                       # :328-337
-                if C == 0:
-                    k_c, v_c = k_new, v_new
-                else:
-                    k_c = append_compressed(k_c, k_new, Bkv, C, 256, D)
-                    v_c = append_compressed(v_c, v_new, Bkv, C, 256, D)
-                k_w.drop_front(256)                                                                     # :392-393
-                v_w.drop_front(256)
-            C += 256
-        return out, (k_c, k_w, v_c, v_w, C, kv_seq_len)
+            return out, new
+        if not self.trigger_due(new):                                                                   # :324
+            return out, new
+        if cfg.hd64_extents:
+            return out, self._run_triggers_ext64([new])[0]
+        if use_arena or (cfg.arena and C == 0):
+            # prune (:325-326) + compress + append (:328-390) of the raw window rows in one launch
+            return out, self._trigger_one(*new, *self._kth(D))
+        k_new, v_new = self._compress_front(k_w.buf, v_w.buf)
+        if C == 0:
+            k_c, v_c = k_new, v_new
+        else:
+            k_c = append_compressed(k_c, k_new, Bkv, C, 256, D)
+            v_c = append_compressed(v_c, v_new, Bkv, C, 256, D)
+        k_w.drop_front(256)                                                                             # :392-393
+        v_w.drop_front(256)
+        return out, (k_c, k_w, v_c, v_w, C + 256, kv_seq_len)
 
     def decode_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None):
         """One decode step over frozen compressed segments + the live cache: `frozen` is a list of `(k_cache, v_cache, tokens)` that
@@ -594,59 +640,11 @@ class MustafarAttention:
         return out, new
 
     # ---- head_dim 64 over a cache that grows by extents (MustafarConfig(hd64_extents=True); cache64.py) ---------------------------------
-    def _decode_fused_ext64(self, query_states, key_states, value_states, past, step_counter, attention_mask, t_device, t_capacity,
-                            defer_trigger, lse=None):
-        """decode_fused for ExtentCache64 caches: the plain D = 64 launch while the cache is its base alone, the extents launch once
-        extents exist or whenever `t_device` is passed; the trigger through run_triggers' batched form."""
-        _, _, q_len, D = query_states.shape
-        assert q_len == 1 and D == 64
-        k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
-        cap_T = C
-        if t_device is not None:
-            if step_counter is None:
-                raise ValueError("decode_fused: t_device is for captured graphs and needs step_counter (an eager call passes neither)")
-            if t_capacity is None or not isinstance(k_c, ExtentCache64) or t_capacity <= k_c.tokens or t_capacity < C or \
-                    (t_capacity - k_c.tokens) % 256 or (t_capacity - k_c.tokens) // 256 > k_c.MAX_EXTENTS:
-                raise ValueError("decode_fused: t_device needs an extent cache and t_capacity = base tokens + a multiple of 256 (at most the "
-                                 "table's entries), not below the compressed length")
-            cap_T = t_capacity
-        kv_seq_len = past[-1] + 1
-        out, tail, keep, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, cap_T, kv_seq_len, step_counter,
-                                                     attention_mask)
-        dev = query_states.device
-        L = _lib.load()
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            if lse is not None and isinstance(k_c, ExtentCache64):   # (T == T_base: the base alone, as the plain launch below)
-                err = L.mustafar_decode_attention_extents_lse_hd(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.table.data_ptr(),
-                                                                 v_c.table.data_ptr(), *tail,
-                                                                 t_device.data_ptr() if t_device is not None else None, D, lse.data_ptr())
-            elif lse is not None:
-                err = L.mustafar_decode_attention_lse_hd(st, *([None] * 8), *tail, D, lse.data_ptr())
-            elif isinstance(k_c, ExtentCache64) and (k_c.extents or t_device is not None):
-                err = L.mustafar_decode_attention_extents_hd(st, k_c.view_ptr(), v_c.view_ptr(), k_c.tokens, k_c.table.data_ptr(),
-                                                             v_c.table.data_ptr(), *tail,
-                                                             t_device.data_ptr() if t_device is not None else None, D)
-            elif isinstance(k_c, ExtentCache64):
-                kb, vb = k_c.base_view, v_c.base_view
-                err = L.mustafar_decode_attention_hd(st, kb.bmp, kb.nz, kb.idx, kb.nz_offset, vb.bmp, vb.nz, vb.idx, vb.nz_offset, *tail, D)
-            else:
-                err = L.mustafar_decode_attention_hd(st, *([None] * 8), *tail, D)
-        _lib.check(err, "mustafar_decode_attention_extents_hd")
-        if step_counter is not None:
-            return out, (k_c, k_w, v_c, v_w, C, kv_seq_len - 1)
-        k_w.len = v_w.len = w_len
-        new = (k_c, k_w, v_c, v_w, C, kv_seq_len)
-        if not defer_trigger and self.trigger_due(new):
-            new = self._run_triggers_ext64([new])[0]
-        return out, new
-
     def _run_triggers_ext64(self, pasts):
         """The trigger of every layer that is due.  A cache that is still empty (C = 0) gets its base from the window rows the
         reference's way (prune, two-pass conversion: the base is reference-layout arrays); every other layer's 256 rows become an
         extent, all layers in one batched call (ExtentCache64.append_extents).  A full table is consolidated first."""
-        cfg, D = self.cfg, self.head_dim
-        kth_k, kth_v = compression.kth_from_sparsity(cfg.k_sparsity, D), compression.kth_from_sparsity(cfg.v_sparsity, D)
+        kth_k, kth_v = self._kth(self.head_dim)
         out = list(pasts)
         groups = {}
         for i, p in enumerate(pasts):
@@ -655,10 +653,8 @@ class MustafarAttention:
             k_c, k_w, v_c, v_w, C, L = p
             Bkv = k_w.buf.shape[0] * k_w.buf.shape[1]
             if C == 0:
-                k_blk = self.dh_prune_key(k_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)
-                v_blk = self.dh_prune_value(v_w.buf[:, :, :256, :]).reshape(Bkv, -1, D)
-                k_c = self.EXTENT_CACHE_64(_compress(k_blk, "key"), "key", Bkv, 256)
-                v_c = self.EXTENT_CACHE_64(_compress(v_blk, "value"), "value", Bkv, 256)
+                k_new, v_new = self._compress_front(k_w.buf, v_w.buf)
+                k_c, v_c = self.EXTENT_CACHE_64(k_new, "key", Bkv, 256), self.EXTENT_CACHE_64(v_new, "value", Bkv, 256)
                 k_w.drop_front(256)
                 v_w.drop_front(256)
                 out[i] = (k_c, k_w, v_c, v_w, 256, L)
@@ -684,29 +680,25 @@ class MustafarAttention:
 
     def _batched_ok(self, past) -> bool:
         k_c, k_w, v_c, v_w, C, L = past
-        flags = _lib.ENGINE_FLAGS[self.cfg.engine] | _lib.STRUCTURE_FLAGS[self.cfg.structure]
-        ld = (C + 256 + k_w.cap + 31) // 32 * 32
         return self.cfg.extents and isinstance(k_c, CompressedArena) and C > 0 and k_c.tokens % 256 == 0 and \
-            len(k_c.extents) < k_c.MAX_EXTENTS and bool(_lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, ld, flags))
+            len(k_c.extents) < k_c.MAX_EXTENTS and self._reads_extents(C + 256 + k_w.cap)
 
     def prepare_triggers(self, pasts):
         """Allocate and initialise the storage of the coming trigger of every layer ahead of it (one allocation, three launches):
         run_triggers() then allocates nothing.  Returns the pool to hand to run_triggers (None where the batched form does not apply)."""
         if not pasts or not all(self._batched_ok(p) for p in pasts):
             return None
-        D = self.head_dim
-        return CompressedArena.prepare_extents([(p[0], p[2]) for p in pasts], compression.kth_from_sparsity(self.cfg.k_sparsity, D),
-                                               compression.kth_from_sparsity(self.cfg.v_sparsity, D))
+        return CompressedArena.prepare_extents([(p[0], p[2]) for p in pasts], *self._kth(self.head_dim))
 
     def run_triggers(self, pasts, pool=None):
         """The trigger (model :324-398) of every layer whose last step reached it (decode_fused(defer_trigger=True), or a replayed
         graph of the step accounted with advance()): prune + compress the 256 oldest window rows of K and V into an extent of the
         cache, slide the windows.  All layers in two library calls and one host read (cache.py: append_extent_pairs) where the cache
         grows by extents; layer by layer otherwise.  Returns the new list of pasts."""
-        cfg, D = self.cfg, self.head_dim
+        cfg = self.cfg
         if cfg.hd64_extents:
             return self._run_triggers_ext64(pasts)
-        kth_k, kth_v = compression.kth_from_sparsity(cfg.k_sparsity, D), compression.kth_from_sparsity(cfg.v_sparsity, D)
+        kth_k, kth_v = self._kth(self.head_dim)
         out = list(pasts)
         due = [i for i, p in enumerate(pasts) if self.trigger_due(p)]
         if not due:
@@ -735,15 +727,11 @@ class MustafarAttention:
     def _trigger_one(self, k_c, k_w, v_c, v_w, C, L, kth_k, kth_v):
         """One layer's trigger over an arena cache (the body decode_fused runs when it is not deferred)."""
         cfg = self.cfg
-        groups = self.num_key_value_groups
-        flags = _lib.ENGINE_FLAGS[cfg.engine] | _lib.STRUCTURE_FLAGS[cfg.structure]
-        ld = (C + max(k_w.cap, v_w.cap) + 31) // 32 * 32
-        Lb = _lib.load()
         if C == 0:
             k_c, v_c = CompressedArena.from_raw_pair(k_w.buf, v_w.buf, 256, kth_k, kth_v, None, self._slack())
             if cfg.extents:
                 k_c.ext_table, v_c.ext_table
-        elif cfg.extents and k_c.tokens % 256 == 0 and Lb.mustafar_decode_reads_extents(groups, ld, flags):
+        elif cfg.extents and k_c.tokens % 256 == 0 and self._reads_extents(C + max(k_w.cap, v_w.cap)):
             if len(k_c.extents) >= k_c.MAX_EXTENTS:          # table full: one copy of the cache, then extents again
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()
                 k_c.ext_table, v_c.ext_table
@@ -822,10 +810,7 @@ class MustafarAttention:
         # :324 (the reference would hand a <256-token window to the compressor when this fires with a short
         # window, which asserts there; guard instead)
         if (kv_seq_len - cfg.residual_length - compressed_length) % 256 == 0 and k_local_window.shape[2] >= 256:
-            k_blk = self.dh_prune_key(k_local_window[:, :, :256, :])                                   # :325
-            v_blk = self.dh_prune_value(v_local_window[:, :, :256, :])                                 # :326
-            k_new = _compress(k_blk.reshape(total_batch_kv, -1, D), "key")
-            v_new = _compress(v_blk.reshape(total_batch_kv, -1, D), "value")
+            k_new, v_new = self._compress_front(k_local_window, v_local_window)                        # :325-326
             if compressed_length == 0:                                                                 # :327-337
                 k_compressed, v_compressed = k_new, v_new
             else:                                                                                      # :339-390

@@ -23,11 +23,7 @@ import torch
 from . import _lib
 from .cache import CompressedArena
 from .cache64 import ExtentCache64
-
-
-def _flat_stream(c):
-    nz = c[2]
-    return nz.flat if hasattr(nz, "flat") else (nz if isinstance(nz, torch.Tensor) else torch.cat(list(nz)))
+from .hook import _call_decode, _compress, _flat_stream, mask_args
 
 
 class SharedSegment:
@@ -84,7 +80,6 @@ class SharedSegment:
     @classmethod
     def from_dense(cls, attn, key_states: torch.Tensor, value_states: torch.Tensor) -> "SharedSegment":
         """key_states / value_states [1, kv_heads, t, D] (t % 64 == 0): pruned at the hook's sparsities and converted."""
-        from .hook import _compress
         if key_states.dim() != 4 or key_states.shape[0] != 1 or key_states.shape != value_states.shape or \
                 key_states.shape[1] != attn.num_key_value_heads or key_states.shape[3] != attn.head_dim:
             raise ValueError(f"SharedSegment.from_dense: K / V of shape [1, {attn.num_key_value_heads}, t, {attn.head_dim}] "
@@ -163,34 +158,15 @@ def decode_segment(attn, query_states: torch.Tensor, k_cache, v_cache=None, toke
         raise ValueError(f"decode_segment: a segment holds a positive multiple of 64 tokens (got {tokens})")
     if D == 128:   # the LSE comes from the one-pass forms (mustafar_hip.h)
         attn._lse_served(tokens)
-    from .hook import mask_args
+    if isinstance(k_cache, (CompressedArena, ExtentCache64)) and \
+            (type(k_cache) is not type(v_cache) or k_cache.total_tokens != tokens or v_cache.total_tokens != tokens):
+        raise ValueError(f"decode_segment: the caches hold {k_cache.total_tokens} / {v_cache.total_tokens} tokens, not {tokens}")
     dev = query_states.device
-    L = _lib.load()
-    # no window argument at all: the window-less form of the two entry points with an LSE (keep: the tensors `tail` points into)
-    out, tail, keep = attn._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
+    # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
+    ops = attn._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
     lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        if isinstance(k_cache, (CompressedArena, ExtentCache64)):
-            if type(k_cache) is not type(v_cache) or k_cache.total_tokens != tokens or v_cache.total_tokens != tokens:
-                raise ValueError(f"decode_segment: the caches hold {k_cache.total_tokens} / {v_cache.total_tokens} tokens, not {tokens}")
-            if isinstance(k_cache, CompressedArena):
-                k_cache.poll()
-                v_cache.poll()
-                kt, vt = (k_cache.ext_table, v_cache.ext_table) if k_cache.extents else (None, None)
-            else:
-                kt, vt = k_cache.table, v_cache.table
-            err = L.mustafar_decode_attention_extents_lse_hd(st, k_cache.view_ptr(), v_cache.view_ptr(), k_cache.tokens,
-                                                             kt.data_ptr() if kt is not None else None,
-                                                             vt.data_ptr() if vt is not None else None, *tail, None, D, lse.data_ptr())
-        else:
-            flat = lambda c: c[2].flat if hasattr(c[2], "flat") else (c[2] if isinstance(c[2], torch.Tensor) else torch.cat(list(c[2])))
-            kz, vz = flat(k_cache), flat(v_cache)   # (kept alive until the call is issued)
-            p = lambda t: t.data_ptr() if t is not None and t.numel() else None
-            err = L.mustafar_decode_attention_lse_hd(st, p(k_cache[0]), p(kz), p(k_cache[1]), p(k_cache[3]), p(v_cache[0]), p(vz),
-                                                     p(v_cache[1]), p(v_cache[3]), *tail, D, lse.data_ptr())
-    _lib.check(err, "mustafar_decode_attention_lse_hd (window-less)")
-    return out, lse
+    _call_decode(k_cache, v_cache, tokens, ops, D, None, lse)
+    return ops.out, lse
 
 
 def merge_states(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor]):
