@@ -3527,10 +3527,9 @@ int g_finish1 = -1;   // round 5: the one-thread-per-channel row kernel for rows
 inline bool finish1() { return env_bool(g_finish1, "MUSTAFAR_FINISH1", 1) != 0; }
 int g_sb = -1;        // round 5: the super-block pair form (MUSTAFAR_SB=0, mustafar_tune(8, 0): round 4's pair kernel)
 inline bool sb_form() { return env_bool(g_sb, "MUSTAFAR_SB", 1) != 0; }
-int g_small = -1;     // round 6: decode_onepass_small_kernel: 1 = for launches of at most small_waves() waves (default), 2 = for every launch of two
+int g_small = -1;     // round 6: decode_onepass_small_kernel: 1 = for launches of at most one wave per SIMD (default; onepass_shape), 2 = for every launch of two
                       // blocks per workgroup, 0 = never (MUSTAFAR_SMALL, mustafar_tune(11, v))
 inline int small_mode() { return env_int(g_small, "MUSTAFAR_SMALL", 1); }
-inline int small_waves() { return cu_count() * 4; }   // one wave per SIMD
 int g_late_prio = 1;    // mustafar_tune(9, 0): no raised priority for a small last round of workgroups (experiments)
 int g_pair_slabs = 0;   // pair form, mustafar_tune(4, 1): a slab per pair instead of one per workgroup (kernel 1.1 us shorter at c3, row kernel 1.5 us longer)
 // g_lean_win_last: the pair form's window workgroups sit BEHIND the SpMV rows of the grid (mustafar_tune(3, 0): in front, round 3a).
@@ -3559,6 +3558,49 @@ struct Profile {
 } g_prof;
 
 
+// ------------------------------------------------------------------------------------------------ kernel selection
+// Every host launch below picks its instantiation from a table of kernel addresses and launches it in ONE statement.  A table
+// names each instantiation once; what a table does not name is not in the library.
+// Row of the key / value tables: GQA-4 on the vector engines, GQA-4 on the matrix pipe, GQA-2, MHA (G < 4 runs v_fma_mix).
+inline int group_row(int G) { return G == 4 ? (fma_engine() == 1 ? 1 : 0) : G == 2 ? 2 : 3; }
+
+// Window workgroups of a two-launch SpMV: whole grid rows of `chunk` window tokens per workgroup, added to the grid in front of
+// the SpMV rows or (wa.rows < 0) behind them.  side: 0 = key launch, 1 = value launch (window_rows_last).
+inline void add_window_rows(WinArgs& wa, dim3& grid, int chunk, int side)
+{
+    if (!wa.win) return;
+    wa.nchunks = (wa.w_cap + chunk - 1) / chunk;
+    wa.rows = ((int)grid.y * wa.nchunks + (int)grid.x - 1) / (int)grid.x;
+    grid.y += wa.rows;
+    if (window_rows_last(side)) wa.rows = -wa.rows;
+}
+
+using KeyLeanKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const h16*, h16*, int, int, int,
+                               WinArgs, int64_t, int64_t, uint32_t);
+inline KeyLeanKernel key_lean_select(int G, int N, bool win_rows)
+{
+    static constexpr KeyLeanKernel kTable[4][3] = {   // columns: N = 1, N = 1 with window workgroups, N = 8
+        {key_lean_kernel<4, 0, 1>, key_lean_kernel<4, 0, 1, true>, key_lean_kernel<4, 0, 8>},
+        {key_lean_kernel<4, 1, 1>, key_lean_kernel<4, 1, 1, true>, key_lean_kernel<4, 1, 8>},
+        {key_lean_kernel<2, 0, 1>, key_lean_kernel<2, 0, 1, true>, key_lean_kernel<2, 0, 8>},
+        {key_lean_kernel<1, 0, 1>, key_lean_kernel<1, 0, 1, true>, key_lean_kernel<1, 0, 8>},
+    };
+    return kTable[group_row(G)][N != 1 ? 2 : win_rows ? 1 : 0];
+}
+
+using KeySpmvKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const h16*, h16*, int, int, int, int,
+                               WinArgs, int64_t, int64_t, uint32_t);
+inline KeySpmvKernel key_spmv_select(int G, int split)
+{
+    static constexpr KeySpmvKernel kTable[4][2] = {   // columns: one wave per token block, two
+        {key_spmv_kernel<4, false, 1>, key_spmv_kernel<4, false, 2>},
+        {key_spmv_kernel<4, true, 1>, key_spmv_kernel<4, true, 2>},
+        {key_spmv_kernel<2, false, 1>, key_spmv_kernel<2, false, 2>},
+        {key_spmv_kernel<1, false, 1>, key_spmv_kernel<1, false, 2>},
+    };
+    return kTable[group_row(G)][split == 2 ? 1 : 0];
+}
+
 // One place that picks the key kernel instantiation: G heads per pass, FMA engine, waves per token block.
 void launch_key(hipStream_t st, const uint64_t* bmp, const unsigned char* nz, const uint32_t* idx, const uint32_t* nz_off,
                 const h16* q, h16* out, int T, int N, int groups, int Batch_Size, int ldc, WinArgs wa = WinArgs{},
@@ -3571,54 +3613,17 @@ void launch_key(hipStream_t st, const uint64_t* bmp, const unsigned char* nz, co
     if (key_lean() && (N == 1 || N == 8)) {
         // round 4: the lean pair form (key_lean_kernel); MUSTAFAR_KEY_LEAN=0 / mustafar_tune(6, 0) selects the round-1 kernel below
         dim3 grid((ntb + 1) / 2, gy);
-        if (wa.win) {
-            wa.nchunks = (wa.w_cap + kKeyWinChunk - 1) / kKeyWinChunk;
-            wa.rows = (gy * wa.nchunks + (int)grid.x - 1) / (int)grid.x;
-            grid.y += wa.rows;
-            if (window_rows_last(0)) wa.rows = -wa.rows;
-        }
-        const bool mf = G == 4 && fma_engine() == 1;
-#define MUSTAFAR_LKL(GG, EE)                                                                                                     \
-    do {                                                                                                                         \
-        if (N == 1 && wa.rows != 0)                                                                                              \
-            hipExtLaunchKernelGGL((key_lean_kernel<GG, EE, 1, true>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, q, out,     \
-                                  T, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);                                        \
-        else if (N == 1) hipExtLaunchKernelGGL((key_lean_kernel<GG, EE, 1>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, q, out,   \
-                                          T, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);                                \
-        else        hipExtLaunchKernelGGL((key_lean_kernel<GG, EE, 8>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, q, out,   \
-                                          T, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);                                \
-    } while (0)
-        if (G == 4) { if (mf) MUSTAFAR_LKL(4, 1); else MUSTAFAR_LKL(4, 0); }
-        else if (G == 2) MUSTAFAR_LKL(2, 0);
-        else MUSTAFAR_LKL(1, 0);
-#undef MUSTAFAR_LKL
+        add_window_rows(wa, grid, kKeyWinChunk, 0);
+        hipExtLaunchKernelGGL(key_lean_select(G, N, wa.rows != 0), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, q, out,
+                              T, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);
         return;
     }
     const int split = key_split(ntb, gy);
     const int per_wg = kWaves / split;
     dim3 grid((ntb + per_wg - 1) / per_wg, gy);
-    if (wa.win) {   // window workgroups first: whole grid rows in front of the SpMV rows
-        wa.nchunks = (wa.w_cap + kKeyWinChunk - 1) / kKeyWinChunk;
-        wa.rows = (gy * wa.nchunks + (int)grid.x - 1) / (int)grid.x;
-        grid.y += wa.rows;
-        if (window_rows_last(0)) wa.rows = -wa.rows;
-    }
-#define MUSTAFAR_LK(GG, MFF)                                                                                                   \
-    do {                                                                                                                       \
-        if (split == 2) hipExtLaunchKernelGGL((key_spmv_kernel<GG, MFF, 2>), grid, dim3(kThreads), 0, st, ev0, ev1, 0,         \
-                                              bmp, nz, idx, nz_off, q, out, T, N, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);   \
-        else            hipExtLaunchKernelGGL((key_spmv_kernel<GG, MFF, 1>), grid, dim3(kThreads), 0, st, ev0, ev1, 0,         \
-                                              bmp, nz, idx, nz_off, q, out, T, N, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);   \
-    } while (0)
-    switch (G) {
-        case 4:
-            if (fma_engine() == 1) MUSTAFAR_LK(4, true);
-            else              MUSTAFAR_LK(4, false);
-            break;
-        case 2: MUSTAFAR_LK(2, false); break;
-        default: MUSTAFAR_LK(1, false); break;
-    }
-#undef MUSTAFAR_LK
+    add_window_rows(wa, grid, kKeyWinChunk, 0);   // window workgroups first: whole grid rows in front of the SpMV rows
+    hipExtLaunchKernelGGL(key_spmv_select(G, split), grid, dim3(kThreads), 0, st, ev0, ev1, 0,
+                          bmp, nz, idx, nz_off, q, out, T, N, groups, ldc, wa, bmp_stride, idx_stride, nz_stride);
 }
 
 // The value kernel's form: 8 waves per workgroup, two per token block (one per 64-channel half) by default;
@@ -3655,6 +3660,31 @@ inline bool value_lean() { return value_lean_mode() != 0; }   // (the workgroup 
 inline bool value_lean_for(int N) { const int m = value_lean_mode(); return m == 1 || (m == 2 && (N == 1 || g_value_lean8)); }
 inline int value_tb_stride() { return value_lean() ? kWaves / 2 : value_split() == 2 ? kValueWaves / 2 : kWaves; }   // token blocks in flight per workgroup
 
+using ValueLeanKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const h16*, h16*, float*, uint32_t*,
+                                 int, int, int, int, int, int, WinArgs, int64_t, int64_t, uint32_t);
+inline ValueLeanKernel value_lean_select(int G, int N, bool win_rows)
+{
+    static constexpr ValueLeanKernel kTable[3][3] = {   // rows: GQA-4, GQA-2, MHA (v_fma_mix only); columns: N = 1, N = 1 with window workgroups, N = 8
+        {value_lean_kernel<4, 1>, value_lean_kernel<4, 1, true>, value_lean_kernel<4, 8>},
+        {value_lean_kernel<2, 1>, value_lean_kernel<2, 1, true>, value_lean_kernel<2, 8>},
+        {value_lean_kernel<1, 1>, value_lean_kernel<1, 1, true>, value_lean_kernel<1, 8>},
+    };
+    return kTable[G == 4 ? 0 : G == 2 ? 1 : 2][N != 1 ? 2 : win_rows ? 1 : 0];
+}
+
+using ValueSpmvKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const h16*, h16*, float*, uint32_t*,
+                                 int, int, int, int, int, int, int, WinArgs, int64_t, int64_t, uint32_t);
+inline ValueSpmvKernel value_spmv_select(int G, int split, bool win_rows)
+{
+    static constexpr ValueSpmvKernel kTable[4][4] = {   // columns: 8 waves, two per block: no window workgroups, with; 4 waves, one per block: no, with
+        {value_spmv_kernel<4, false, kValueWaves, 2, false>, value_spmv_kernel<4, false, kValueWaves, 2, true>, value_spmv_kernel<4, false, kWaves, 1, false>, value_spmv_kernel<4, false, kWaves, 1, true>},
+        {value_spmv_kernel<4, true, kValueWaves, 2, false>, value_spmv_kernel<4, true, kValueWaves, 2, true>, value_spmv_kernel<4, true, kWaves, 1, false>, value_spmv_kernel<4, true, kWaves, 1, true>},
+        {value_spmv_kernel<2, false, kValueWaves, 2, false>, value_spmv_kernel<2, false, kValueWaves, 2, true>, value_spmv_kernel<2, false, kWaves, 1, false>, value_spmv_kernel<2, false, kWaves, 1, true>},
+        {value_spmv_kernel<1, false, kValueWaves, 2, false>, value_spmv_kernel<1, false, kValueWaves, 2, true>, value_spmv_kernel<1, false, kWaves, 1, false>, value_spmv_kernel<1, false, kWaves, 1, true>},
+    };
+    return kTable[group_row(G)][(split == 2 ? 0 : 2) + (win_rows ? 1 : 0)];
+}
+
 // One place that picks the value kernel instantiation.
 void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned char* nz, const uint32_t* idx,
                   const uint32_t* nz_off, const h16* p, h16* out, float* ws, uint32_t* flags, int T, int N, int groups,
@@ -3662,55 +3692,134 @@ void launch_value(hipStream_t st, dim3 grid, const uint64_t* bmp, const unsigned
                   hipEvent_t ev1 = nullptr, int64_t bmp_stride = 0, int64_t idx_stride = 0, uint32_t nz_stride = 0)
 {
     const int G = pick_g(groups);
-    if (wa.win) {   // window workgroups first; their partial slabs follow the grid.x token-chunk slabs
-        wa.nchunks = (wa.w_cap + kValueWinChunk - 1) / kValueWinChunk;
-        wa.rows = ((int)grid.y * wa.nchunks + (int)grid.x - 1) / (int)grid.x;
-        grid.y += wa.rows;
-        if (window_rows_last(1)) wa.rows = -wa.rows;
-    }
+    add_window_rows(wa, grid, kValueWinChunk, 1);   // window workgroups first; their partial slabs follow the grid.x token-chunk slabs
     if ((N == 1 || N == 8) && value_lean_for(N)) {
         // (the pad workgroups behind the row-0 workgroups, one per head group and four chunks: value_lean_kernel)
         if (N > 1) grid.y += (grid.y * ((grid.x + kPadGroup - 1) / kPadGroup) + grid.x - 1) / grid.x;
-#define MUSTAFAR_LVL(GG)                                                                                                         \
-    do {                                                                                                                         \
-        if (N == 1 && wa.rows != 0)                                                                                                              \
-            hipExtLaunchKernelGGL((value_lean_kernel<GG, 1, true>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,    \
-                                  flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);                    \
-        else if (N == 1) hipExtLaunchKernelGGL((value_lean_kernel<GG, 1>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,  \
-                                          flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);            \
-        else        hipExtLaunchKernelGGL((value_lean_kernel<GG, 8>), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,  \
-                                          flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);            \
-    } while (0)
-        if (G == 4) MUSTAFAR_LVL(4);
-        else if (G == 2) MUSTAFAR_LVL(2);
-        else MUSTAFAR_LVL(1);
-#undef MUSTAFAR_LVL
+        hipExtLaunchKernelGGL(value_lean_select(G, N, wa.rows != 0), grid, dim3(kThreads), 0, st, ev0, ev1, 0, bmp, nz, idx, nz_off, p, out, ws,
+                              flags, T, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);
         return;
     }
-#define MUSTAFAR_LV(GG, MFF)                                                                                                   \
-    do {                                                                                                                       \
-        if (value_split() == 2 && wa.rows != 0)                                                                                \
-            hipExtLaunchKernelGGL((value_spmv_kernel<GG, MFF, kValueWaves, 2, true>), grid, dim3(kValueWaves * 64), 0, st, ev0, ev1, 0, \
-                                  bmp, nz, idx, nz_off, p, out, ws, flags, T, N, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride); \
-        else if (value_split() == 2)                                                                                           \
-            hipExtLaunchKernelGGL((value_spmv_kernel<GG, MFF, kValueWaves, 2, false>), grid, dim3(kValueWaves * 64), 0, st, ev0, ev1, 0, \
-                                  bmp, nz, idx, nz_off, p, out, ws, flags, T, N, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride); \
-        else if (wa.rows != 0)                                                                                                 \
-            hipExtLaunchKernelGGL((value_spmv_kernel<GG, MFF, kWaves, 1, true>), grid, dim3(kThreads), 0, st, ev0, ev1, 0,     \
-                                  bmp, nz, idx, nz_off, p, out, ws, flags, T, N, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride); \
-        else                                                                                                                   \
-            hipExtLaunchKernelGGL((value_spmv_kernel<GG, MFF, kWaves, 1, false>), grid, dim3(kThreads), 0, st, ev0, ev1, 0,    \
-                                  bmp, nz, idx, nz_off, p, out, ws, flags, T, N, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride); \
-    } while (0)
-    switch (G) {
-        case 4:
-            if (fma_engine() == 1) MUSTAFAR_LV(4, true);
-            else              MUSTAFAR_LV(4, false);
-            break;
-        case 2: MUSTAFAR_LV(2, false); break;
-        default: MUSTAFAR_LV(1, false); break;
+    const int split = value_split();
+    hipExtLaunchKernelGGL(value_spmv_select(G, split, wa.rows != 0), grid, dim3(split == 2 ? kValueWaves * 64 : kThreads), 0, st, ev0, ev1, 0,
+                          bmp, nz, idx, nz_off, p, out, ws, flags, T, N, groups, Batch_Size, tb_per_wg, direct, ldb, wa, bmp_stride, idx_stride, nz_stride);
+}
+
+// ------------------------------------------------------------------------------------------------ one-pass launch: shape and kernels
+// ONE shape rule.  decode_attention launches what onepass_shape() fills in, mustafar_decode_reads_extents() answers from
+// onepass_slabs_fit(), and mustafar_decode_workspace_bytes() is sized by the bound that follows from onepass_slabs().
+constexpr int onepass_slabs(int ntb, int per_wg, int spw) { return spw * ((ntb + per_wg - 1) / per_wg); }   // slabs the SpMV workgroups leave per row
+// ... and with the window chunks' slabs behind them: no more than a row kernel folds
+constexpr bool onepass_slabs_fit(int ntb, int per_wg, int spw, int nchunks) { return onepass_slabs(ntb, per_wg, spw) + nchunks <= kMaxSlabs; }
+// Every shape has per_wg >= 2 (an even count of blocks) and spw <= 2, so NS = onepass_slabs(ntb, per_wg, spw) <= 2 * ceil(ntb / 2) <= ntb + 1;
+// the worst case is a slab per pair of waves, two blocks per workgroup and an odd ntb:
+static_assert(onepass_slabs(7, 2, 2) == 7 + 1 && onepass_slabs(8, 2, 2) == 8, "mustafar_decode_workspace_bytes holds ntb + 1 slabs");
+
+struct OnePassKnobs {   // the process state the shape depends on (onepass_knobs() reads it for a call); onepass_shape() itself is pure
+    bool sb, pair_slabs, win_last, late_prio;   // sb_form(), g_pair_slabs, g_lean_win_last, g_late_prio
+    int wgs, lean_tbw, small;                   // onepass_wgs(), onepass_lean_tbw(), small_mode()
+    int cus;                                    // cu_count()
+};
+inline OnePassKnobs onepass_knobs()
+{
+    return OnePassKnobs{sb_form(), g_pair_slabs != 0, g_lean_win_last != 0, g_late_prio != 0, onepass_wgs(), onepass_lean_tbw(), small_mode(), cu_count()};
+}
+
+enum OnePassForm { kFormPair = 2, kFormSb = 3, kFormSmall = 4 };   // (as mustafar_last_decode_choice() reports them, bits 8 and up)
+struct OnePassShape {
+    int per_wg;         // 64-token blocks per workgroup
+    int spw;            // slabs per workgroup
+    int S1;             // workgroups per head group: grid.x
+    int NS;             // their slabs
+    int nchunks;        // window chunks of kOneWinChunk tokens: a workgroup and a slab each
+    int win_rows;       // grid rows of window workgroups; as OneArgs carries them: negative when they sit behind the SpMV rows
+    int form;           // OnePassForm
+    int hi_prio_from;   // OneArgs::hi_prio_from
+};
+
+// The shape of the one-pass launch over T tokens and gy head groups.  false: no shape serves the call (MUSTAFAR_EINVAL).
+inline bool onepass_shape(OnePassShape& s, int T, int gy, int window_capacity, bool extents, int eng, const OnePassKnobs& k)
+{
+    const int ntb = T / 64;
+    s.nchunks = (window_capacity + kOneWinChunk - 1) / kOneWinChunk;
+    // 64-token blocks per workgroup: two block pairs per workgroup (each pair of waves runs its block loop twice) unless that leaves fewer than 1024
+    // workgroups: start-up and merge code are paid once per two blocks and the row kernel folds half the slabs.  With the
+    // window workgroups BEHIND the SpMV rows (below) this is the better shape at c3 too -- round 3a, window rows first:
+    // 3968 workgroups of one pair each (tokens/s, four vs two blocks per workgroup, windows last: matrix pipe c3 6204 vs
+    // 6050, c4 1877 vs 1719, c5 4070 vs 3900; dot2 c3 5122 vs 4992).  MUSTAFAR_ONEPASS_WGS / MUSTAFAR_LEAN_TBW override
+    // (round 5, super-block form: from 768 workgroups -- three per CU -- on; Llama-3-8B 4k x batch 8 is 960 workgroups of four blocks:
+    // 23.5 vs 24.6 us; at 480 (c2) and 248 (8k x batch 1) two blocks per workgroup win, 13.3 vs 15.4 and 11.1 vs 14.6 us)
+    int per_wg = (int64_t)((ntb + 3) / 4) * gy >= (k.sb ? 768 : 1024) ? 4 : 2;
+    if (k.wgs > 0) {
+        const int want = (k.wgs + gy - 1) / gy;
+        per_wg = ((ntb + want - 1) / want + 1) / 2 * 2;
     }
-#undef MUSTAFAR_LV
+    if (k.lean_tbw > 0) per_wg = 2 * k.lean_tbw;
+    s.spw = k.pair_slabs && !(k.sb && per_wg <= 4) ? 2 : 1;   // (the super-block form always merges its pairs)
+    while (!onepass_slabs_fit(ntb, per_wg, s.spw, s.nchunks)) per_wg += 2;
+    if (extents && per_wg != 2 && per_wg != 4) return false;   // a workgroup's blocks stay inside one extent
+    s.per_wg = per_wg;
+    s.S1 = (ntb + per_wg - 1) / per_wg;
+    s.NS = onepass_slabs(ntb, per_wg, s.spw);
+    const int win_rows = (gy * s.nchunks + s.S1 - 1) / s.S1;
+    s.win_rows = k.win_last ? -win_rows : win_rows;
+    // the last round of SpMV workgroups, when it is a small fraction of a resident round (8 workgroups per CU): raised priority
+    const int slots = k.cus * 8;
+    const int64_t W = (int64_t)s.S1 * gy, full = W / slots * slots;
+    s.hi_prio_from = k.late_prio && full > 0 && W - full > 0 && (W - full) * 4 <= slots && !(s.win_rows > 0) ? (int)full : 0x7fffffff;
+    // round 6, the small form: the form without a memory wait inside the phases, for launches that do not even put one wave on every SIMD (c1;
+    // Llama-3-8B 4k x batch 1): there its shorter chain wins 10 %; from two waves per SIMD on (8k x batch 1, c2) its extra
+    // v_readlane per step cost more than the waits they replace (profiles/r06_probes.txt item 3).  mustafar_tune(11, 2): always.
+    // It has no matrix-pipe instantiation.
+    // round 5, the super-block pair form: same grid, slabs and window workgroups; a pair walks its <= 2 blocks once.
+    const bool small = k.sb && per_wg == 2 && eng != 1 && k.lean_tbw <= 0 &&
+                       (k.small == 2 || (k.small == 1 && (int64_t)s.S1 * gy * kWaves <= k.cus * 4));   // (cus * 4: one wave per SIMD)
+    s.form = small ? kFormSmall : k.sb && per_wg <= 4 ? kFormSb : kFormPair;
+    return true;
+}
+
+// The three one-pass kernels take the same arguments.  onepass_select names every instantiation the dispatcher can reach.
+using OnePassKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const uint64_t*, const unsigned char*,
+                               const uint32_t*, const uint32_t*, OneArgs, int64_t, int64_t, uint32_t, int64_t, int64_t, uint32_t);
+// eng: 0 for G < 4.  ext: the EXT instantiation.  mask: the MASK instantiation (the pair form has none: it reads a.mask at run time).
+// nullptr: no such kernel -- the MHA pair and super-block launches always run EXT (decode_attention), the matrix pipe has no small form.
+inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask)
+{
+    const int row = G == 4 ? eng : G == 2 ? 3 : 4;   // GQA-4: v_fma_mix, matrix pipe, v_dot2; GQA-2; MHA
+    const int col = (ext ? 2 : 0) + (mask ? 1 : 0);  // EXT = false: MASK false, true; EXT = true: MASK false, true
+    static constexpr OnePassKernel kPair[5][2] = {
+        {decode_onepass_leanpair_kernel<0, false>, decode_onepass_leanpair_kernel<0, true>},
+        {decode_onepass_leanpair_kernel<1, false>, decode_onepass_leanpair_kernel<1, true>},
+        {decode_onepass_leanpair_kernel<2, false>, decode_onepass_leanpair_kernel<2, true>},
+        {decode_onepass_leanpair_kernel<0, false, 2>, decode_onepass_leanpair_kernel<0, true, 2>},
+        {nullptr, decode_onepass_leanpair_kernel<0, true, 1>},
+    };
+    static constexpr OnePassKernel kSb[5][4] = {
+        {decode_onepass_sb_kernel<0, false, 4, false>, decode_onepass_sb_kernel<0, false, 4, true>, decode_onepass_sb_kernel<0, true, 4, false>, decode_onepass_sb_kernel<0, true, 4, true>},
+        {decode_onepass_sb_kernel<1, false, 4, false>, decode_onepass_sb_kernel<1, false, 4, true>, decode_onepass_sb_kernel<1, true, 4, false>, decode_onepass_sb_kernel<1, true, 4, true>},
+        {decode_onepass_sb_kernel<2, false, 4, false>, decode_onepass_sb_kernel<2, false, 4, true>, decode_onepass_sb_kernel<2, true, 4, false>, decode_onepass_sb_kernel<2, true, 4, true>},
+        {decode_onepass_sb_kernel<0, false, 2, false>, decode_onepass_sb_kernel<0, false, 2, true>, decode_onepass_sb_kernel<0, true, 2, false>, decode_onepass_sb_kernel<0, true, 2, true>},
+        {nullptr, nullptr, decode_onepass_sb_kernel<0, true, 1, false>, decode_onepass_sb_kernel<0, true, 1, true>},
+    };
+    static constexpr OnePassKernel kSmall[5][4] = {
+        {decode_onepass_small_kernel<0, false, 4, false>, decode_onepass_small_kernel<0, false, 4, true>, decode_onepass_small_kernel<0, true, 4, false>, decode_onepass_small_kernel<0, true, 4, true>},
+        {nullptr, nullptr, nullptr, nullptr},
+        {decode_onepass_small_kernel<2, false, 4, false>, decode_onepass_small_kernel<2, false, 4, true>, decode_onepass_small_kernel<2, true, 4, false>, decode_onepass_small_kernel<2, true, 4, true>},
+        {decode_onepass_small_kernel<0, false, 2, false>, decode_onepass_small_kernel<0, false, 2, true>, decode_onepass_small_kernel<0, true, 2, false>, decode_onepass_small_kernel<0, true, 2, true>},
+        {decode_onepass_small_kernel<0, false, 1, false>, decode_onepass_small_kernel<0, false, 1, true>, decode_onepass_small_kernel<0, true, 1, false>, decode_onepass_small_kernel<0, true, 1, true>},
+    };
+    return form == kFormSmall ? kSmall[row][col] : form == kFormSb ? kSb[row][col] : kPair[row][ext ? 1 : 0];
+}
+
+// The row kernel behind a one-pass launch: merges the NSL slabs of every row.  tail: LseArg{lse} or NoLse{}.
+template <bool LSE>
+void launch_finish(hipStream_t st, hipEvent_t f0, hipEvent_t f1, const float* ws_o, const float* ws_ml, int NSL, h16* out, int Batch_Size,
+                   typename LseOf<LSE>::type tail)
+{
+    const bool one = NSL <= 64 && finish1();   // one thread per channel
+    void (*const kernel)(const float*, const float*, int, h16*, int, typename LseOf<LSE>::type) =
+        one ? onepass_finish1_kernel<LSE> : NSL <= 64 ? onepass_finish_kernel<1, LSE> : NSL <= 128 ? onepass_finish_kernel<2, LSE> : onepass_finish_kernel<kMaxSlabs / 64, LSE>;
+    hipExtLaunchKernelGGL(kernel, dim3(Batch_Size), dim3(one ? 128 : 256), 0, st, f0, f1, 0, ws_o, ws_ml, NSL, out, Batch_Size, tail);
 }
 
 }  // namespace
@@ -3802,7 +3911,8 @@ int Value_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const
 int64_t mustafar_decode_workspace_bytes(int T, int Batch_Size, int num_key_value_groups, int Split_K)
 {
     (void)num_key_value_groups;   // token-chunk slabs + the window workgroups' slabs (one-pass forms: 64-token window chunks and a
-    // (max, sum) pair per slab and row); sized for a slab per 64-token block (the forms in use leave at most one per two)
+    // (max, sum) pair per slab and row); sized for the most slabs a shape of onepass_shape() leaves: onepass_slabs() <= ntb + 1 (derived and
+    // asserted there; the shapes in use leave at most one per two blocks) and, with the window slabs, <= kMaxSlabs (onepass_slabs_fit())
     const int ntb = T > 0 ? T / 64 : 1;
     const int sk = Split_K < 1 ? 1 : Split_K;
     const int per_block = ntb + 1 < kMaxSlabs ? ntb + 1 : kMaxSlabs;   // (pair form: two slabs per workgroup of two blocks, the last one may hold one)
@@ -3825,195 +3935,103 @@ bool parse_flags(uint32_t flags, uint32_t* f_eng, uint32_t* f_str)
 // alone by a call that is refused.  The call's own engine / structure are in force (decode_dispatch).
 int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
 {
-    const mustafar_cache_view &kc = c.k, &vc = c.v;
-    const mustafar_cache_view *k_ext = c.k_ext, *v_ext = c.v_ext;
-    const int T_base = c.T_base, T = c.T, Batch_Size = c.Batch_Size, groups = c.groups, Split_K = c.Split_K, ld_scores = c.ld_scores;
-    const int window_len = c.window_len, window_capacity = c.window_capacity;
-    const int32_t *T_device = c.T_device, *window_len_extra = c.window_len_extra;
-    void *k_window = c.k_window, *v_window = c.v_window, *scores = c.scores, *out = c.out, *workspace = c.workspace;
-    const void *q = c.q, *k_new = c.k_new, *v_new = c.v_new;
-    const float sqrt_d = c.sqrt_d;
-    float* lse = c.lse;
-    const bool extents = k_ext != nullptr;   // (T > T_base and both tables: checked by decode_dispatch)
-    if (extents && (kc.nz_head_stride == 0 || vc.nz_head_stride == 0)) return MUSTAFAR_EINVAL;
+    const bool extents = c.k_ext != nullptr;   // (T > T_base and both tables: checked by decode_dispatch)
+    if (extents && (c.k.nz_head_stride == 0 || c.v.nz_head_stride == 0)) return MUSTAFAR_EINVAL;
     // A window-less call has no window workgroups (win_rows = 0) and no window slabs in the one-pass launch; the two-launch form,
     // whose row kernels read the window themselves, is refused for it.
     bool no_window = false;
     if (!decode_call_ok(c, kMaxWindow, &no_window)) return MUSTAFAR_EINVAL;
     const MaskArg mask{static_cast<const h16*>(c.attention_mask), c.mask_row_stride, c.heads_per_mask_row > 0 ? c.heads_per_mask_row : 1};
-    // an LSE comes from the one-pass forms' row kernels: a call that would run two launches is refused before anything is launched
-    if ((lse || no_window) && !(T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0)) return MUSTAFAR_EINVAL;
-    if (T > 0 && (!kc.bmp || !kc.nz || !kc.idx || !kc.nz_offset || !vc.bmp || !vc.nz || !vc.idx || !vc.nz_offset)) return MUSTAFAR_EINVAL;
-    const int64_t tiles = (int64_t)(extents ? T_base : T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
-    if (T > 0 && ((kc.bmp_head_stride && kc.bmp_head_stride < tiles) || (kc.idx_head_stride && kc.idx_head_stride < tiles + 1) ||
-                  (vc.bmp_head_stride && vc.bmp_head_stride < tiles) || (vc.idx_head_stride && vc.idx_head_stride < tiles + 1)))
+    const bool onepass = c.T > 0 && onepass_mode() != 0 && (c.ld_scores & 31) == 0;   // where the one-pass launch can run, it does (onepass_mode())
+    // an LSE comes from the one-pass forms' row kernels, and appended extents are read by the one-pass launch only: a call that would
+    // run two launches is refused before anything is launched
+    if ((c.lse || no_window || extents) && !onepass) return MUSTAFAR_EINVAL;
+    if (c.T > 0 && (!c.k.bmp || !c.k.nz || !c.k.idx || !c.k.nz_offset || !c.v.bmp || !c.v.nz || !c.v.idx || !c.v.nz_offset)) return MUSTAFAR_EINVAL;
+    const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
+    if (c.T > 0 && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1) ||
+                    (c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))
         return MUSTAFAR_EINVAL;
     hipStream_t st = c.stream;
-    auto qh = static_cast<const h16*>(q);
-    auto sc = static_cast<h16*>(scores);
-    const int G = pick_g(groups);
-    const int gy = (Batch_Size / groups) * (groups / G);
-    int S = 0, nwin_slabs = 0;
-    auto kwin = static_cast<h16*>(k_window);
-    auto vwin = static_cast<h16*>(v_window);
-    auto knew = static_cast<const h16*>(k_new);
-    auto vnew = static_cast<const h16*>(v_new);
-    const float inv_sqrt_d0 = (float)(1.0 / (double)sqrt_d);
-    const int eng = G == 4 ? fma_engine() : 0;
-    // appended extents are read by the one-pass launch only
-    if (extents && !(T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0)) return MUSTAFAR_EINVAL;
-    if (T > 0 && onepass_mode() != 0 && (ld_scores & 31) == 0) {
+    auto qh = static_cast<const h16*>(c.q);
+    auto sc = static_cast<h16*>(c.scores);
+    auto oh = static_cast<h16*>(c.out);
+    auto ws = static_cast<float*>(c.workspace);
+    auto kwin = static_cast<h16*>(c.k_window);
+    auto vwin = static_cast<h16*>(c.v_window);
+    auto knew = static_cast<const h16*>(c.k_new);
+    auto vnew = static_cast<const h16*>(c.v_new);
+    auto kz = static_cast<const unsigned char*>(c.k.nz), vz = static_cast<const unsigned char*>(c.v.nz);
+    const int G = pick_g(c.groups);
+    const int gy = (c.Batch_Size / c.groups) * (c.groups / G);
+    const float inv_sqrt_d = (float)(1.0 / (double)c.sqrt_d);
+    if (onepass) {
         // ---- one-pass form: every wave runs key phase -> softmax step -> value phase on its token blocks; slabs merged per row.
         // Pair grain: two waves per block, two blocks per workgroup at a time, for every engine and group count (G < 4 -- MHA,
         // GQA-2 -- on the v_fma_mix engine).
-        const int ntb = T / 64;
-        const int nchunks = (window_capacity + kOneWinChunk - 1) / kOneWinChunk;
-        // 64-token blocks per workgroup: two block pairs per workgroup (each pair of waves runs its block loop twice) unless that leaves fewer than 1024
-        // workgroups: start-up and merge code are paid once per two blocks and the row kernel folds half the slabs.  With the
-        // window workgroups BEHIND the SpMV rows (below) this is the better shape at c3 too -- round 3a, window rows first:
-        // 3968 workgroups of one pair each (tokens/s, four vs two blocks per workgroup, windows last: matrix pipe c3 6204 vs
-        // 6050, c4 1877 vs 1719, c5 4070 vs 3900; dot2 c3 5122 vs 4992).  MUSTAFAR_ONEPASS_WGS / MUSTAFAR_LEAN_TBW override
-        // (round 5, super-block form: from 768 workgroups -- three per CU -- on; Llama-3-8B 4k x batch 8 is 960 workgroups of four blocks:
-        // 23.5 vs 24.6 us; at 480 (c2) and 248 (8k x batch 1) two blocks per workgroup win, 13.3 vs 15.4 and 11.1 vs 14.6 us)
-        int per_wg = (int64_t)((ntb + 3) / 4) * gy >= (sb_form() ? 768 : 1024) ? 4 : 2;
-        if (onepass_wgs() > 0) {
-            const int want = (onepass_wgs() + gy - 1) / gy;
-            per_wg = ((ntb + want - 1) / want + 1) / 2 * 2;
-        }
-        if (onepass_lean_tbw() > 0) per_wg = 2 * onepass_lean_tbw();
-        const int spw = g_pair_slabs && !(sb_form() && per_wg <= 4) ? 2 : 1;   // slabs per workgroup (the super-block form always merges its pairs)
-        while (spw * ((ntb + per_wg - 1) / per_wg) + nchunks > kMaxSlabs) per_wg += 2;
-        const int S1 = (ntb + per_wg - 1) / per_wg;   // workgroups per head group
-        const int NS = spw * S1;                      // their slabs
-        float* ws_o = static_cast<float*>(workspace);
-        float* ws_ml = ws_o + (int64_t)(NS + nchunks) * Batch_Size * kD;
-        const int win_rows = (gy * nchunks + S1 - 1) / S1;
-        if (extents && per_wg != 2 && per_wg != 4) return MUSTAFAR_EINVAL;   // a workgroup's blocks stay inside one extent
-        OneArgs a{qh, sc, ws_o, ws_ml, kwin, vwin, knew, vnew, window_len_extra, mask, T, groups, Batch_Size, per_wg,
-                  ld_scores, window_len, window_capacity, nchunks, g_lean_win_last ? -win_rows : win_rows, inv_sqrt_d0, spw == 2};
+        const int eng = G == 4 ? fma_engine() : 0;
+        OnePassShape s;
+        if (!onepass_shape(s, c.T, gy, c.window_capacity, extents, eng, onepass_knobs())) return MUSTAFAR_EINVAL;
+        float* ws_ml = ws + (int64_t)(s.NS + s.nchunks) * c.Batch_Size * kD;
+        OneArgs a{qh, sc, ws, ws_ml, kwin, vwin, knew, vnew, c.window_len_extra, mask, c.T, c.groups, c.Batch_Size, s.per_wg,
+                  c.ld_scores, c.window_len, c.window_capacity, s.nchunks, s.win_rows, inv_sqrt_d, s.spw == 2};
+        a.hi_prio_from = s.hi_prio_from;
         if (extents) {
-            a.k_ext = k_ext;
-            a.v_ext = v_ext;
-            a.nb0 = T_base / 64;
-            a.t_dev = T_device;
+            a.k_ext = c.k_ext;
+            a.v_ext = c.v_ext;
+            a.nb0 = c.T_base / 64;
+            a.t_dev = c.T_device;
         }
-        const dim3 grid(S1, gy + win_rows);
-        {   // the last round of SpMV workgroups, when it is a small fraction of a resident round (8 workgroups per CU): raised priority
-            const int slots = cu_count() * 8;
-            const int64_t W = (int64_t)S1 * gy, full = W / slots * slots;
-            if (g_late_prio && full > 0 && W - full > 0 && (W - full) * 4 <= slots && !(a.win_rows > 0)) a.hi_prio_from = (int)full;
-        }
-        hipEvent_t e0 = ev ? ev[0] : nullptr, e1 = ev ? ev[1] : nullptr;
-        auto kz = static_cast<const unsigned char*>(kc.nz), vz = static_cast<const unsigned char*>(vc.nz);
-        bool small_form = false;
-#define MUSTAFAR_LL(KERNEL)                                                                                                           \
-    hipExtLaunchKernelGGL(KERNEL, grid, dim3(kThreads), 0, st, e0, e1, 0, kc.bmp, kz, kc.idx, kc.nz_offset,                            \
-                          vc.bmp, vz, vc.idx, vc.nz_offset, a, kc.bmp_head_stride, kc.idx_head_stride, (uint32_t)kc.nz_head_stride,    \
-                          vc.bmp_head_stride, vc.idx_head_stride, (uint32_t)vc.nz_head_stride)
-#define MUSTAFAR_LP(EXTV)                                                                                   \
-    do {                                                                                                    \
-        if (G == 2)        MUSTAFAR_LL((decode_onepass_leanpair_kernel<0, EXTV, 2>));                       \
-        else if (G == 1)   MUSTAFAR_LL((decode_onepass_leanpair_kernel<0, EXTV, 1>));                       \
-        else if (eng == 2) MUSTAFAR_LL((decode_onepass_leanpair_kernel<2, EXTV>));                          \
-        else if (eng == 1) MUSTAFAR_LL((decode_onepass_leanpair_kernel<1, EXTV>));                          \
-        else               MUSTAFAR_LL((decode_onepass_leanpair_kernel<0, EXTV>));                          \
-    } while (0)
         // (G = 1 without extents: the plain instantiation comes out of the register allocator with a 68-byte private segment it
         // never touches, and a kernel with a private segment is launched with scratch (+1 % measured on the GQA-4 form); the
-        // extents instantiation has none and serves the same launch with every block in the base views)
-        if (!extents && G == 1) a.nb0 = ntb;
-        if (sb_form() && per_wg == 2 && eng != 1 && onepass_lean_tbw() <= 0 && (small_mode() == 2 || (small_mode() == 1 && (int64_t)S1 * gy * kWaves <= small_waves()))) {
-            // round 6: the form without a memory wait inside the phases, for launches that do not even put one wave on every SIMD (c1;
-            // Llama-3-8B 4k x batch 1): there its shorter chain wins 10 %; from two waves per SIMD on (8k x batch 1, c2) its extra
-            // v_readlane per step cost more than the waits they replace (profiles/r06_probes.txt item 3).  mustafar_tune(11, 2): always
-#define MUSTAFAR_SM(EXTV, MASKV)                                                                              \
-    do {                                                                                                      \
-        if (G == 2)        MUSTAFAR_LL((decode_onepass_small_kernel<0, EXTV, 2, MASKV>));                      \
-        else if (G == 1)   MUSTAFAR_LL((decode_onepass_small_kernel<0, EXTV, 1, MASKV>));                      \
-        else if (eng == 2) MUSTAFAR_LL((decode_onepass_small_kernel<2, EXTV, 4, MASKV>));                      \
-        else               MUSTAFAR_LL((decode_onepass_small_kernel<0, EXTV, 4, MASKV>));                      \
-    } while (0)
-            if (extents) { if (mask.ptr) MUSTAFAR_SM(true, true); else MUSTAFAR_SM(true, false); }
-            else         { if (mask.ptr) MUSTAFAR_SM(false, true); else MUSTAFAR_SM(false, false); }
-#undef MUSTAFAR_SM
-            small_form = true;
-        } else if (sb_form() && per_wg <= 4) {   // round 5: the super-block pair form (same grid, slabs and window workgroups; a pair walks its <= 2 blocks once)
-#define MUSTAFAR_SB(EXTV, MASKV)                                                                            \
-    do {                                                                                                    \
-        if (G == 2)        MUSTAFAR_LL((decode_onepass_sb_kernel<0, EXTV, 2, MASKV>));                       \
-        else if (G == 1)   MUSTAFAR_LL((decode_onepass_sb_kernel<0, EXTV, 1, MASKV>));                       \
-        else if (eng == 2) MUSTAFAR_LL((decode_onepass_sb_kernel<2, EXTV, 4, MASKV>));                       \
-        else if (eng == 1) MUSTAFAR_LL((decode_onepass_sb_kernel<1, EXTV, 4, MASKV>));                       \
-        else               MUSTAFAR_LL((decode_onepass_sb_kernel<0, EXTV, 4, MASKV>));                       \
-    } while (0)
-            if (extents || G == 1) { if (mask.ptr) MUSTAFAR_SB(true, true); else MUSTAFAR_SB(true, false); }
-            else                   { if (mask.ptr) MUSTAFAR_SB(false, true); else MUSTAFAR_SB(false, false); }
-#undef MUSTAFAR_SB
-        } else if (extents || G == 1) MUSTAFAR_LP(true);
-        else                          MUSTAFAR_LP(false);
-#undef MUSTAFAR_LP
-#undef MUSTAFAR_LL
+        // extents instantiation has none and serves the same launch with every block in the base views.  The small form
+        // launches its plain G = 1 instantiation.)
+        if (!extents && G == 1) a.nb0 = c.T / 64;
+        const bool ext = extents || (G == 1 && s.form != kFormSmall);
+        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr);
+        if (!kernel) return MUSTAFAR_EINVAL;   // (no shape selects a kernel the table leaves out)
+        hipExtLaunchKernelGGL(kernel, dim3(s.S1, gy + (s.win_rows < 0 ? -s.win_rows : s.win_rows)), dim3(kThreads), 0, st, ev ? ev[0] : nullptr,
+                              ev ? ev[1] : nullptr, 0, c.k.bmp, kz, c.k.idx, c.k.nz_offset, c.v.bmp, vz, c.v.idx, c.v.nz_offset, a,
+                              c.k.bmp_head_stride, c.k.idx_head_stride, (uint32_t)c.k.nz_head_stride,
+                              c.v.bmp_head_stride, c.v.idx_head_stride, (uint32_t)c.v.nz_head_stride);
         // (the row kernel's own start / stop timestamps go into the record's second event pair: mustafar_profile_end2)
-        {
-            hipEvent_t f0 = ev ? ev[2] : nullptr, f1 = ev ? ev[3] : nullptr;
-            const int NSL = NS + nchunks;
-            auto oh = static_cast<h16*>(out);
-#define MUSTAFAR_FIN(KERNEL, THREADS, TAIL) \
-    hipExtLaunchKernelGGL((KERNEL), dim3(Batch_Size), dim3(THREADS), 0, st, f0, f1, 0, ws_o, ws_ml, NSL, oh, Batch_Size, TAIL)
-            if (lse) {   // the same four variants, each with the LSE store
-                if (NSL <= 64 && finish1()) MUSTAFAR_FIN(onepass_finish1_kernel<true>, 128, LseArg{lse});
-                else if (NSL <= 64)         MUSTAFAR_FIN((onepass_finish_kernel<1, true>), 256, LseArg{lse});
-                else if (NSL <= 128)        MUSTAFAR_FIN((onepass_finish_kernel<2, true>), 256, LseArg{lse});
-                else                        MUSTAFAR_FIN((onepass_finish_kernel<kMaxSlabs / 64, true>), 256, LseArg{lse});
-            } else {
-                if (NSL <= 64 && finish1()) MUSTAFAR_FIN(onepass_finish1_kernel<false>, 128, NoLse{});
-                else if (NSL <= 64)         MUSTAFAR_FIN((onepass_finish_kernel<1, false>), 256, NoLse{});
-                else if (NSL <= 128)        MUSTAFAR_FIN((onepass_finish_kernel<2, false>), 256, NoLse{});
-                else                        MUSTAFAR_FIN((onepass_finish_kernel<kMaxSlabs / 64, false>), 256, NoLse{});
-            }
-#undef MUSTAFAR_FIN
-        }
-        *choice = eng | (1 << 4) | ((small_form ? 4 : sb_form() && per_wg <= 4 ? 3 : 2) << 8);
+        hipEvent_t f0 = ev ? ev[2] : nullptr, f1 = ev ? ev[3] : nullptr;
+        if (c.lse) launch_finish<true>(st, f0, f1, ws, ws_ml, s.NS + s.nchunks, oh, c.Batch_Size, LseArg{c.lse});
+        else       launch_finish<false>(st, f0, f1, ws, ws_ml, s.NS + s.nchunks, oh, c.Batch_Size, NoLse{});
+        *choice = eng | (1 << 4) | (s.form << 8);
         return (int)hipGetLastError();
     }
     // ---- two-launch form.  With a compressed part the dense-window work rides in the two SpMV launches (window workgroups);
     // without one (T == 0) the two row kernels do it themselves.
-    const bool long_rows = T > kMaxRowVecs * kGlueThreads * 8;   // beyond the register form of the softmax kernel
-    const bool ride_k = T > 0 && ((window_ride_mask() & 1) || long_rows), ride_v = T > 0 && (window_ride_mask() & 2);
-    if (T > 0) {
-        const WinArgs kw = ride_k ? WinArgs{kwin, knew, window_len_extra, window_len, window_capacity, 0, 0} : WinArgs{};
-        launch_key(st, kc.bmp, static_cast<const unsigned char*>(kc.nz), kc.idx, kc.nz_offset, qh, sc, T, 1, groups, Batch_Size, ld_scores, kw,
-                   ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, kc.bmp_head_stride,
-                   kc.idx_head_stride, (uint32_t)kc.nz_head_stride);
+    const bool long_rows = c.T > kMaxRowVecs * kGlueThreads * 8;   // beyond the register form of the softmax kernel
+    const bool ride_k = c.T > 0 && ((window_ride_mask() & 1) || long_rows), ride_v = c.T > 0 && (window_ride_mask() & 2);
+    if (c.T > 0) {
+        const WinArgs kw = ride_k ? WinArgs{kwin, knew, c.window_len_extra, c.window_len, c.window_capacity, 0, 0} : WinArgs{};
+        launch_key(st, c.k.bmp, kz, c.k.idx, c.k.nz_offset, qh, sc, c.T, 1, c.groups, c.Batch_Size, c.ld_scores, kw,
+                   ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, c.k.bmp_head_stride, c.k.idx_head_stride, (uint32_t)c.k.nz_head_stride);
     }
-    const float inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
     if (long_rows) {
-        if (mask.ptr) long_softmax_kernel<true><<<Batch_Size, kGlueThreads, 0, st>>>(sc, T, ld_scores, window_len, window_capacity, inv_sqrt_d, window_len_extra, mask);
-        else          long_softmax_kernel<false><<<Batch_Size, kGlueThreads, 0, st>>>(sc, T, ld_scores, window_len, window_capacity, inv_sqrt_d, window_len_extra, mask);
+        if (mask.ptr) long_softmax_kernel<true><<<c.Batch_Size, kGlueThreads, 0, st>>>(sc, c.T, c.ld_scores, c.window_len, c.window_capacity, inv_sqrt_d, c.window_len_extra, mask);
+        else          long_softmax_kernel<false><<<c.Batch_Size, kGlueThreads, 0, st>>>(sc, c.T, c.ld_scores, c.window_len, c.window_capacity, inv_sqrt_d, c.window_len_extra, mask);
     } else {
-        if (mask.ptr) window_softmax_kernel<true><<<Batch_Size, kGlueThreads, 0, st>>>(qh, ride_k ? nullptr : kwin, ride_k ? nullptr : knew, sc, T, ld_scores, window_len,
-                                                                                     window_capacity, groups, inv_sqrt_d, window_len_extra, mask);
-        else          window_softmax_kernel<false><<<Batch_Size, kGlueThreads, 0, st>>>(qh, ride_k ? nullptr : kwin, ride_k ? nullptr : knew, sc, T, ld_scores, window_len,
-                                                                                      window_capacity, groups, inv_sqrt_d, window_len_extra, mask);
+        if (mask.ptr) window_softmax_kernel<true><<<c.Batch_Size, kGlueThreads, 0, st>>>(qh, ride_k ? nullptr : kwin, ride_k ? nullptr : knew, sc, c.T, c.ld_scores, c.window_len,
+                                                                                       c.window_capacity, c.groups, inv_sqrt_d, c.window_len_extra, mask);
+        else          window_softmax_kernel<false><<<c.Batch_Size, kGlueThreads, 0, st>>>(qh, ride_k ? nullptr : kwin, ride_k ? nullptr : knew, sc, c.T, c.ld_scores, c.window_len,
+                                                                                        c.window_capacity, c.groups, inv_sqrt_d, c.window_len_extra, mask);
     }
-    float* ws = static_cast<float*>(workspace);
-    if (T > 0) {
-        const int ntb = T / 64;
-        const int tb_per_wg = (ntb + Split_K - 1) / Split_K;
+    int S = 0, nwin_slabs = 0;
+    if (c.T > 0) {
+        const int ntb = c.T / 64;
+        const int tb_per_wg = (ntb + c.Split_K - 1) / c.Split_K;
         S = (ntb + tb_per_wg - 1) / tb_per_wg;
-        const dim3 gv(S, gy);
-        auto nz = static_cast<const unsigned char*>(vc.nz);
         h16* no_out = nullptr;
         uint32_t* no_flags = nullptr;
-        const WinArgs vw = ride_v ? WinArgs{vwin, vnew, window_len_extra, window_len, window_capacity, 0, 0} : WinArgs{};
-        if (ride_v) nwin_slabs = (window_capacity + kValueWinChunk - 1) / kValueWinChunk;
-        launch_value(st, gv, vc.bmp, nz, vc.idx, vc.nz_offset, sc, no_out, ws, no_flags, T, 1, groups, Batch_Size, tb_per_wg, 0, ld_scores, vw,
-                     ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, vc.bmp_head_stride,
-                     vc.idx_head_stride, (uint32_t)vc.nz_head_stride);
+        const WinArgs vw = ride_v ? WinArgs{vwin, vnew, c.window_len_extra, c.window_len, c.window_capacity, 0, 0} : WinArgs{};
+        if (ride_v) nwin_slabs = (c.window_capacity + kValueWinChunk - 1) / kValueWinChunk;
+        launch_value(st, dim3(S, gy), c.v.bmp, vz, c.v.idx, c.v.nz_offset, sc, no_out, ws, no_flags, c.T, 1, c.groups, c.Batch_Size, tb_per_wg, 0, c.ld_scores, vw,
+                     ev ? ev[2] : nullptr, ev ? ev[3] : nullptr, c.v.bmp_head_stride, c.v.idx_head_stride, (uint32_t)c.v.nz_head_stride);
     }
-    value_finish_kernel<<<Batch_Size, 256, 0, st>>>(ws, S + nwin_slabs, sc, ld_scores, T, ride_v ? nullptr : vwin, ride_v ? nullptr : vnew,
-                                                    window_len, window_capacity, static_cast<h16*>(out), Batch_Size, groups,
-                                                    window_len_extra);
+    value_finish_kernel<<<c.Batch_Size, 256, 0, st>>>(ws, S + nwin_slabs, sc, c.ld_scores, c.T, ride_v ? nullptr : vwin, ride_v ? nullptr : vnew,
+                                                      c.window_len, c.window_capacity, oh, c.Batch_Size, c.groups, c.window_len_extra);
     *choice = (fma_engine() == 1 && G == 4 ? 1 : 0);
     return (int)hipGetLastError();
 }
@@ -4248,8 +4266,9 @@ int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint3
     if (!parse_flags(flags, &f_eng, &f_str)) return 0;
     if (f_str == 1u || (f_str == 0u && onepass_mode() == 0)) return 0;   // two launches asked for (by the call or by the process default)
     // rows so long that four blocks per workgroup leave more slabs than the row kernel folds (T > ~127 k tokens; ld_scores >= T
-    // stands in for T): decode_attention then gives a workgroup more blocks, which may straddle extents -> not served
-    if (((ld_scores / 64 + 3) / 4) + kMaxWindow / kOneWinChunk > kMaxSlabs) return 0;
+    // stands in for T and the largest window for the call's own): onepass_shape() then gives a workgroup more blocks, which may straddle
+    // extents -> not served
+    if (!onepass_slabs_fit(ld_scores / 64, 4, 1, kMaxWindow / kOneWinChunk)) return 0;
     return num_key_value_groups >= 1 && (ld_scores & 31) == 0 && onepass_wgs() <= 0 &&   // (MUSTAFAR_ONEPASS_WGS changes the shape rule)
            (onepass_lean_tbw() == 0 || onepass_lean_tbw() == 1 || onepass_lean_tbw() == 2);
 }

@@ -90,6 +90,42 @@ def test_extent_arguments_are_validated_without_a_gpu():
     assert L.mustafar_decode_reads_extents(4, 8256, 1 << 6) == 0                                                 # undefined flag bits
 
 
+# mustafar_decode_reads_extents over (block pairs per workgroup: mustafar_tune(1, .), workgroup target: mustafar_tune(2, .), flags): one
+# answer per (groups, ld_scores) of _EXTENTS_GROUPS x _EXTENTS_LD, groups-major.  Recorded from the library as it stood before the
+# one-pass launch shape moved into onepass_shape() / onepass_slabs_fit(); the answer derives from the same shape rule the launch uses
+# and must not move.  126976 is the longest row pitch served (four blocks per workgroup leave 496 slabs + 16 window slabs = 512).
+_EXTENTS_GROUPS = (0, 1, 2, 4, 8)
+_EXTENTS_LD = (0, 32, 64, 100, 4096, 126720, 126976, 127232, 127488)
+_SERVED = "000000000" + "111011100" * 4     # no groups: never; else: pitch % 32 == 0 and at most 126976
+_NEVER = "0" * 45
+_EXTENTS_ANSWERS = {
+    (0, 0, 0x0): _SERVED, (0, 0, 0x10): _NEVER, (0, 0, 0x20): _SERVED, (0, 0, 0x40): _NEVER,
+    (0, 64, 0x0): _NEVER, (0, 64, 0x10): _NEVER, (0, 64, 0x20): _NEVER, (0, 64, 0x40): _NEVER,
+    (1, 0, 0x0): _SERVED, (1, 0, 0x10): _NEVER, (1, 0, 0x20): _SERVED, (1, 0, 0x40): _NEVER,
+    (1, 64, 0x0): _NEVER, (1, 64, 0x10): _NEVER, (1, 64, 0x20): _NEVER, (1, 64, 0x40): _NEVER,
+    (2, 0, 0x0): _SERVED, (2, 0, 0x10): _NEVER, (2, 0, 0x20): _SERVED, (2, 0, 0x40): _NEVER,
+    (2, 64, 0x0): _NEVER, (2, 64, 0x10): _NEVER, (2, 64, 0x20): _NEVER, (2, 64, 0x40): _NEVER,
+    (3, 0, 0x0): _NEVER, (3, 0, 0x10): _NEVER, (3, 0, 0x20): _NEVER, (3, 0, 0x40): _NEVER,
+    (3, 64, 0x0): _NEVER, (3, 64, 0x10): _NEVER, (3, 64, 0x20): _NEVER, (3, 64, 0x40): _NEVER,
+}
+
+
+def test_reads_extents_answers_follow_the_recorded_shape_rule():
+    """mustafar_decode_reads_extents (host only) gives the recorded answer for every group count, row pitch on either side of the
+    slab limit, structure flag (none, two launches, one pass, an undefined bit) and shape knob."""
+    from mustafar_amd import _lib
+    L = _lib.load()
+    assert _SERVED == "000000000111011100111011100111011100111011100"
+    try:
+        for (tbw, wgs, flags), want in _EXTENTS_ANSWERS.items():
+            assert L.mustafar_tune(1, tbw) == 0 and L.mustafar_tune(2, wgs) == 0
+            got = "".join(str(L.mustafar_decode_reads_extents(g, ld, flags)) for g in _EXTENTS_GROUPS for ld in _EXTENTS_LD)
+            assert got == want, (tbw, wgs, flags)
+    finally:
+        L.mustafar_tune(1, 0)
+        L.mustafar_tune(2, 0)
+
+
 def test_batched_trigger_arguments_are_validated_without_a_gpu():
     """mustafar_trigger_compress_batch / mustafar_trigger_finish_batch (round 4): every item is checked on the host before anything is
     launched -- null windows, views without room for the 256 tokens, a missing flag, shapes."""
