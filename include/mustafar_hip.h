@@ -468,6 +468,45 @@ int mustafar_decode_shared_segment(void* stream, const mustafar_cache_view* k_ca
                                    const void* q, void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
 
 /*
+ * Several query tokens per call (ABI 112): n_q consecutive tokens of every sequence decoded by ONE call over the live cache (multi_query.hip).
+ *
+ * mustafar_decode_multi_query: query token j (0 .. n_q - 1) of sequence b attends to the compressed tokens [0, T) of its own cache and to
+ *   window rows [0, window_len - n_q + j] -- its own new row and everything older; the rows of the later tokens are masked (the causal
+ *   limit among the new tokens: the only mask).  window_len counts the rows AFTER the append, as in mustafar_decode_attention.  Three
+ *   launches (two with k_new == NULL): the n_q new rows are copied into the windows; then a workgroup serves one (sequence, kv head) and
+ *   either a run of consecutive 64-token blocks or 64 window rows for all R = n_q * num_key_value_groups rows of it -- each block expanded
+ *   once into a dense fp16 image in LDS, scores and outputs on the matrix pipe, the arithmetic of mustafar_decode_shared_segment -- and
+ *   leaves one (max, sum, output) slab per row; the row kernel merges a row's slabs.
+ *   k_base / v_base     HOST views of tokens [0, T_base) of B' = batch * kv_heads heads, any strides (nz_head_stride 0: nz_offset is
+ *                       loaded), as in mustafar_decode_shared_segment; may be NULL when T == 0 (nothing compressed yet: window only)
+ *   k_extents / v_extents   DEVICE tables as in mustafar_decode_attention_extents_hd: entry i holds tokens [T_base + 256 i, T_base + 256 (i + 1)),
+ *                       offsets relative to the extent, bmp / idx strides 0 = exactly 4 blocks' tiles / + 1, nz_head_stride != 0 or nz_offset
+ *                       loaded; resolved per block with scalar loads (a run may cross base -> extent and extent -> extent).  NULL when
+ *                       T == T_base.  T > T_base needs T_base % 256 == 0, (T - T_base) % 256 == 0 and at most 512 entries; T == T_base: any
+ *                       multiple of 64.  T > 0 needs T_base > 0
+ *   q, out              fp16 [B', num_key_value_groups, n_q, head_dim] -- the hook's [bsz, heads, n_q, head_dim] --, contiguous, 16-byte aligned
+ *   lse                 fp32 [B', num_key_value_groups, n_q] out, REQUIRED: M + log(sum_t exp(x_t - M)) over what the row saw, x as in the
+ *                       _lse_hd entry points
+ *   k_window / v_window [B', window_capacity, head_dim]; k_new / v_new [B', n_q, head_dim] are copied to rows [window_len - n_q, window_len)
+ *                       (both NULL: the rows are already stored); 16-byte aligned
+ *   workspace           mustafar_decode_multi_query_workspace_bytes() bytes, 16-byte aligned
+ *   MUSTAFAR_EINVAL before any launch for: n_q < 1, n_q * num_key_value_groups > 64, num_key_value_groups outside 1..8, head_dim not 64 or
+ *   128, Bp outside 1..65535, T < 0 or T % 64 != 0, the T_base / extent rules above, window_len < n_q, window_len > window_capacity,
+ *   window_capacity > 1024, exactly one of k_new / v_new NULL, NULL or misaligned q / out / windows / new rows / workspace / lse, a base
+ *   view mustafar_decode_shared_segment would refuse.  No mask, no device-side lengths (window_len_extra, T_device) in this version.
+ *   Nothing is allocated and nothing is read back: the call can be captured in a hipGraph at fixed lengths.
+ * mustafar_decode_multi_query_workspace_bytes: (ceil(T / 64 / bpw) + ceil(window_capacity / 64)) * Bp * R * (head_dim + 2) * 4, with
+ *   bpw = ceil(8 R (head_dim + 2) / (88 head_dim)) blocks per run, the rule of mustafar_shared_segment_workspace_bytes.  0 for the
+ *   shapes the call refuses.
+ */
+int64_t mustafar_decode_multi_query_workspace_bytes(int T, int window_capacity, int Bp, int num_key_value_groups, int n_q, int head_dim);
+int mustafar_decode_multi_query(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                int T, int Bp, int num_key_value_groups, int n_q,
+                                const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                int window_len, int window_capacity, void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
+
+/*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
  * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
  *

@@ -1,0 +1,463 @@
+// multi_query.hip -- several query tokens of every sequence per fused decode call, head_dim 64 and 128, for gfx950.  The C ABI entry points
+// mustafar_decode_multi_query and mustafar_decode_multi_query_workspace_bytes (include/mustafar_hip.h, ABI 112).
+//
+// A caller that verifies n_q drafted tokens, or feeds a short follow-up turn, would issue n_q decode steps, each re-reading the whole
+// compressed cache and paying the per-tile cost of the format -- bitmap, rank, address, select -- again.  The n_q tokens of one sequence are
+// R = n_q * G query rows over that sequence's own kv head: the arithmetic of shared_segment.hip, whose engine expands a 64-token block once
+// into a dense fp16 image in LDS and serves up to 64 rows with v_mfma_f32_16x16x32_f16.  This file adds what a step over the LIVE cache
+// needs beyond that: per-sequence caches, the 256-token extents, the dense window and a causal limit among the new tokens.
+//
+// q, out [B', G, n_q, D] (the hook's [bsz, H, n_q, D]), lse [B', G, n_q]: the R rows of one (sequence, kv head) are consecutive, local row
+// r = g * n_q + j for q head g and query token j, padded to row tiles of 16 with zero query rows.
+//
+// multi_query_append_kernel   copies the n_q new K / V rows of every head to rows [window_len - n_q, window_len) of its window, in a launch
+//                             of its own in front: stream order makes them visible to every workgroup of the decode launch
+// multi_query_decode_kernel   grid (compressed runs + window chunks, B'), 256 threads; a workgroup serves all R rows of one (sequence, kv head)
+//   compressed run   `bpw` consecutive 64-token blocks with the phases and barriers of shared_segment_decode_kernel: stage, K expand, scores,
+//                    softmax step, V expand, out.  EXT: block tb < T_base / 64 comes from the base view, block T_base / 64 + 4 i + j is block
+//                    j of entry i of a DEVICE table of mustafar_cache_view (offsets relative to the extent), resolved per block with
+//                    wave-uniform loads as headdim64.hip's extent_block does: a run may cross base -> extent and extent -> extent, and what
+//                    is requested ahead (the next block's metadata and key stream) follows the resolution of the NEXT block
+//   window chunk     64 rows of the dense window: the key image [token][channel] is filled straight from the rows of k_window as 16-byte
+//                    pieces, the value image [channel][token] is the transpose of the rows of v_window; scores, softmax step and out as for
+//                    a compressed block.  The causal limit is the only mask: window row w is visible to query token j iff
+//                    w <= window_len - n_q + j.  An invisible column counts as x = -inf, e = 0; a row that sees no column of its chunk
+//                    stays at M = -inf, L = 0 (a slab of weight zero).  Image rows at or beyond window_len are written as zeros
+//                    (0 x garbage through the matrix pipe is NaN where the garbage is Inf or NaN).  Chunks at or beyond
+//                    ceil(window_len / 64) leave slabs of weight zero
+// shared_merge_kernel         (expand_block.h) folds a row's slabs -- compressed runs first, then window chunks -- into out and lse
+// Products are fp16 x fp16, exact in fp32; sums are fp32.  No inline assembly.
+
+#include "expand_block.h"
+
+namespace mustafar_shared {
+namespace {
+
+typedef const __attribute__((address_space(4))) uint64_t* cu64_p;
+constexpr int kMaxExtents = 512;    // entries of the device tables
+constexpr int kMaxWindow = 1024;    // rows of a window buffer
+
+// ---- the phases of a block, as shared_segment_decode_kernel runs them.  s_img: halfs of max(64 (D + 8), D kRowPad); s_xe: 16 RT rows of kRowPad halfs; s_alpha: 16 RT floats.
+
+// K expand: lane = token, wave w takes the D / 4 channel tiles [w D / 4, (w + 1) D / 4) -> img[token][channel], rows of D + 8 halfs
+template <int D>
+__device__ __forceinline__ void expand_keys(const TileMeta& km, uint32_t k0, const uint16_t* sb, h16* s_img, int lane, int wave)
+{
+    constexpr int KROW = D + 8;
+    uint32_t pk[D / 8];   // D / 4 halfs
+#pragma unroll
+    for (int j = 0; j < D / 4; j += 2) {
+        const uint32_t lo = tile_element<D>(km, j, k0, sb, lane);
+        const uint32_t hi = tile_element<D>(km, j + 1, k0, sb, lane);
+        pk[j >> 1] = lo | (hi << 16);
+    }
+    uint4* dst = reinterpret_cast<uint4*>(s_img + lane * KROW + wave * (D / 4));
+#pragma unroll
+    for (int p = 0; p < D / 32; p++) dst[p] = make_uint4(pk[4 * p], pk[4 * p + 1], pk[4 * p + 2], pk[4 * p + 3]);
+}
+
+// scores: wave w = tokens [16 w, 16 w + 16) of the key image, every row tile: x -> xe[row][token]
+template <int D, int RT>
+__device__ __forceinline__ void score_tiles(const h16x8 (&qf)[RT][D / 32], const h16* s_img, h16* s_xe, float inv_sqrt_d, int wave, int l15,
+                                            int l4)
+{
+    constexpr int KS = D / 32, KROW = D + 8;
+    h16x8 bf[KS];
+#pragma unroll
+    for (int s = 0; s < KS; s++) bf[s] = *reinterpret_cast<const h16x8*>(s_img + (wave * 16 + l15) * KROW + 32 * s + 8 * l4);
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) {
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; s++) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[rt][s], bf[s], acc, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++)   // C: column = token l & 15, row = 4 (l >> 4) + i
+            s_xe[(rt * 16 + 4 * l4 + i) * kRowPad + wave * 16 + l15] = scaled(acc[i], inv_sqrt_d);
+    }
+}
+
+// V expand: lane = channel, wave w takes tokens [16 w, 16 w + 16) (both 64-channel halves at D = 128) -> img[channel][token], rows of kRowPad
+template <int D>
+__device__ __forceinline__ void expand_values(const TileMeta& vm, uint32_t v0, const uint16_t* sb, h16* s_img, int lane, int wave)
+{
+#pragma unroll
+    for (int hh = 0; hh < D / 64; hh++) {
+        uint32_t pk[8];
+#pragma unroll
+        for (int j = 0; j < 16; j += 2) {
+            const uint32_t lo = tile_element<D>(vm, hh * 16 + j, v0, sb, lane);
+            const uint32_t hi = tile_element<D>(vm, hh * 16 + j + 1, v0, sb, lane);
+            pk[j >> 1] = lo | (hi << 16);
+        }
+        uint4* dst = reinterpret_cast<uint4*>(s_img + (hh * 64 + lane) * kRowPad + wave * 16);
+        dst[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+        dst[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
+    }
+}
+
+// Online softmax step: thread = (row tid >> 2, 16 tokens), four lanes per row: the step of headdim64.hip's softmax_step, the row's max and
+// sum folded over the quad.  Rows of zero queries (at or beyond R) go through it like any other: x = 0, finite everywhere.
+// LIMIT: columns at or beyond `visible` (0..64, the row's own) count as x = -inf, e = 0; a row that sees no column at all, in this block and
+// before it, stays at M = -inf, L = 0 with alpha = 1 (exp(-inf - -inf) would be NaN).
+template <int RT, bool LIMIT>
+__device__ __forceinline__ void softmax_rows(h16* s_xe, float* s_alpha, float& M, float& L, int srow, int sq, int visible)
+{
+    if (srow < RT * 16) {
+        h16x8* px = reinterpret_cast<h16x8*>(s_xe + srow * kRowPad + sq * 16);
+        const h16x8 xa = px[0], xb = px[1];
+        float x[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { x[j] = (float)xa[j]; x[8 + j] = (float)xb[j]; }
+        if constexpr (LIMIT) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) x[j] = sq * 16 + j < visible ? x[j] : -INFINITY;
+        }
+        float mx = x[0];
+#pragma unroll
+        for (int j = 1; j < 16; j++) mx = fmaxf(mx, x[j]);
+        const float mn = fmaxf(M, quad_max(mx));
+        float alpha = __expf(M - mn);                 // (exp(-inf) = 0 before the first block)
+        float ms = mn;
+        if constexpr (LIMIT) {
+            if (mn == -INFINITY) { alpha = 1.f; ms = 0.f; }   // nothing seen yet: every e = exp(-inf - 0) = 0
+        }
+        h16x8 ea, eb;
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const h16 e = (h16)__expf(x[j] - ms);
+            sum += (float)e;
+            if (j < 8) ea[j] = e; else eb[j - 8] = e;
+        }
+        L = L * alpha + quad_sum(sum);
+        M = mn;
+        px[0] = ea;
+        px[1] = eb;
+        if (sq == 0) s_alpha[srow] = alpha;
+    }
+}
+
+// out: wave w = channel tiles [w D / 64, (w + 1) D / 64) of the value image, every row tile: o = o * alpha + e . V
+template <int D, int RT>
+__device__ __forceinline__ void accumulate_out(f32x4 (&o)[RT][D / 64], const h16* s_img, const h16* s_xe, const float* s_alpha, int wave,
+                                               int l15, int l4)
+{
+    constexpr int CT = D / 64;
+    h16x8 vf[CT][2];
+#pragma unroll
+    for (int c = 0; c < CT; c++)
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+            vf[c][s] = *reinterpret_cast<const h16x8*>(s_img + ((wave * CT + c) * 16 + l15) * kRowPad + 32 * s + 8 * l4);
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) {
+        const float4 al = *reinterpret_cast<const float4*>(s_alpha + rt * 16 + 4 * l4);
+        h16x8 ef[2];
+#pragma unroll
+        for (int s = 0; s < 2; s++) ef[s] = *reinterpret_cast<const h16x8*>(s_xe + (rt * 16 + l15) * kRowPad + 32 * s + 8 * l4);
+#pragma unroll
+        for (int c = 0; c < CT; c++) {
+            f32x4 acc = o[rt][c];
+            acc[0] *= al.x; acc[1] *= al.y; acc[2] *= al.z; acc[3] *= al.w;
+#pragma unroll
+            for (int s = 0; s < 2; s++) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ef[s], vf[c][s], acc, 0, 0, 0);
+            o[rt][c] = acc;
+        }
+    }
+}
+
+// The workgroup's slab of every row: slab = index of the workgroup's first row among all rows of the launch
+template <int D, int RT>
+__device__ __forceinline__ void write_slabs(const f32x4 (&o)[RT][D / 64], float M, float L, float* ws_o, float* ws_ml, int64_t slab, int R,
+                                            int wave, int l15, int l4, int srow, int sq)
+{
+    constexpr int CT = D / 64;
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int c = 0; c < CT; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int r = rt * 16 + 4 * l4 + i;
+                if (r < R) ws_o[(slab + r) * D + (wave * CT + c) * 16 + l15] = o[rt][c][i];
+            }
+    if (srow < R && sq == 0) { ws_ml[2 * (slab + srow)] = M; ws_ml[2 * (slab + srow) + 1] = L; }
+}
+
+// One side of a 64-token block as the phases read it: bitmaps and offsets of its tiles, the head's stream.
+struct BlockRef {
+    const uint64_t* bmp;
+    const uint32_t* idx;
+    const uint4* nz;
+};
+static_assert(sizeof(mustafar_cache_view) == 56, "a table entry is read as seven 8-byte words");
+// Block j (0..3) of a table entry, head kvh: every field a scalar load (the entry is wave-uniform), offsets relative to the extent.
+template <int TILES>
+__device__ __forceinline__ BlockRef extent_block(const mustafar_cache_view* entry, int kvh, int j)
+{
+    const cu64_p f = (cu64_p)reinterpret_cast<const uint64_t*>(entry);   // bmp, nz, idx, nz_offset, bmp stride, idx stride, nz stride
+    const int64_t bs = f[4] ? (int64_t)f[4] : 4 * TILES, is = f[5] ? (int64_t)f[5] : 4 * TILES + 1;
+    BlockRef r;
+    r.bmp = reinterpret_cast<const uint64_t*>(f[0]) + kvh * bs + j * TILES;
+    r.idx = reinterpret_cast<const uint32_t*>(f[2]) + kvh * is + j * TILES;
+    const int64_t start = f[6] ? (int64_t)kvh * (int64_t)f[6] : (int64_t)((cu32_p)reinterpret_cast<const uint32_t*>(f[3]))[kvh];
+    r.nz = reinterpret_cast<const uint4*>(f[1]) + start;
+    return r;
+}
+
+struct MqArgs {
+    SideArgs k, v;                       // the base views (unused when ntb == 0)
+    const mustafar_cache_view* k_ext;    // DEVICE tables of the extents (EXT)
+    const mustafar_cache_view* v_ext;
+    const h16* q;                        // [B', R, D]
+    const h16* k_win;                    // [B', w_cap, D]
+    const h16* v_win;
+    float* ws_o;                         // [runs + chunks, B', R, D]
+    float* ws_ml;                        // [runs + chunks, B', R, 2]
+    int ntb, ntb_base, bpw, runs, n_q, R, w_len, w_cap;
+    float inv_sqrt_d;
+};
+
+// Block tb of one side: from the head's rows of the base view, or (EXT) from the table behind them.
+template <int TILES, bool EXT>
+__device__ __forceinline__ BlockRef block_of(const uint64_t* bmp_h, const uint32_t* idx_h, const uint4* nz_h, const mustafar_cache_view* ext,
+                                             int ntb_base, int kvh, int tb)
+{
+    if constexpr (EXT) {
+        if (tb >= ntb_base) {
+            const int xb = tb - ntb_base;
+            return extent_block<TILES>(ext + (xb >> 2), kvh, xb & 3);
+        }
+    }
+    return BlockRef{bmp_h + (int64_t)tb * TILES, idx_h + (int64_t)tb * TILES, nz_h};
+}
+
+template <int D, int RT, bool EXT>
+__global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
+{
+    constexpr int TILES = D;                 // tiles of a 64-token block on either side (D / 64 per token)
+    constexpr int KS = D / 32;               // k-steps of the score product
+    constexpr int CT = D / 64;               // channel tiles of 16 a wave owns in the output product
+    constexpr int KROW = D + 8;              // halfs of a key image row (token-major): 144 / 272 bytes
+    constexpr int IMG = (64 * KROW > D * kRowPad) ? 64 * KROW : D * kRowPad;
+    __shared__ uint4 s_stream[8 * TILES];    // a block's key or value stream
+    __shared__ __attribute__((aligned(16))) h16 s_img[IMG];                 // key image [token][channel], then value image [channel][token]
+    __shared__ __attribute__((aligned(16))) h16 s_xe[RT * 16 * kRowPad];    // x, then e: [row][token]
+    __shared__ __attribute__((aligned(16))) float s_alpha[RT * 16];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bkv = blockIdx.y, x = blockIdx.x;
+    const int R = a.R;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const uint16_t* sb = reinterpret_cast<const uint16_t*>(s_stream);
+
+    // q fragments (A operand): lane holds q[row 16 rt + (l & 15)][32 s + 8 (l >> 4) ..+8); rows at or beyond R are zero
+    h16x8 qf[RT][KS];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) {
+        const int r = rt * 16 + l15;
+        const bool live = r < R;
+        const h16* qrow = a.q + ((int64_t)bkv * R + (live ? r : 0)) * D;
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            h16x8 v = *reinterpret_cast<const h16x8*>(qrow + 32 * s + 8 * l4);
+            if (!live) v = h16x8{};
+            qf[rt][s] = v;
+        }
+    }
+    f32x4 o[RT][CT];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int c = 0; c < CT; c++) o[rt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // softmax state of row tid >> 2 (the four lanes of a quad hold the same values; rows at or beyond 16 RT do not exist)
+    const int srow = tid >> 2, sq = tid & 3;
+    float M = -INFINITY, L = 0.f;
+
+    if (x < a.runs) {
+        // ---- compressed blocks [tb0, tb1) of this head
+        const int tb0 = x * a.bpw, tb1 = min(a.ntb, tb0 + a.bpw);
+        const uint4* kz = a.k.nz + (a.k.nz_stride ? (int64_t)bkv * a.k.nz_stride : (int64_t)a.k.nz_offset[bkv]);
+        const uint4* vz = a.v.nz + (a.v.nz_stride ? (int64_t)bkv * a.v.nz_stride : (int64_t)a.v.nz_offset[bkv]);
+        const uint64_t* kb_h = a.k.bmp + bkv * a.k.bmp_stride;
+        const uint32_t* ki_h = a.k.idx + bkv * a.k.idx_stride;
+        const uint64_t* vb_h = a.v.bmp + bkv * a.v.bmp_stride;
+        const uint32_t* vi_h = a.v.idx + bkv * a.v.idx_stride;
+
+        // the tiles this wave expands: K tile wave D / 4 + lane (lanes below D / 4), V tile 64 (lane >> 4) + 16 wave + (lane & 15) (lanes below D / 4)
+        const bool meta_on = lane < D / 4;
+        const int k_tile = wave * (D / 4) + lane, v_tile = (lane >> 4) * 64 + wave * 16 + l15;
+        BlockRef kc = block_of<TILES, EXT>(kb_h, ki_h, kz, a.k_ext, a.ntb_base, bkv, tb0);
+        BlockRef vc = block_of<TILES, EXT>(vb_h, vi_h, vz, a.v_ext, a.ntb_base, bkv, tb0);
+        TileMeta km = load_meta(kc.bmp, kc.idx, k_tile, meta_on);
+        TileMeta vm = load_meta(vc.bmp, vc.idx, v_tile, meta_on);
+        StreamRegs<TILES> kg{}, vg{};
+        load_block<TILES>(kc.nz, (cu32_p)kc.idx, tid, kg);
+        store_block<TILES>(kg, s_stream, tid);
+        uint32_t k0 = kg.i0;
+        __syncthreads();
+        for (int tb = tb0; tb < tb1; tb++) {
+            // requested now, used later: this block's value stream, the next block's bitmaps and offsets -- of the next block as resolved
+            load_block<TILES>(vc.nz, (cu32_p)vc.idx, tid, vg);
+            const int tn = min(tb + 1, tb1 - 1);
+            const BlockRef kn = block_of<TILES, EXT>(kb_h, ki_h, kz, a.k_ext, a.ntb_base, bkv, tn);
+            const BlockRef vn = block_of<TILES, EXT>(vb_h, vi_h, vz, a.v_ext, a.ntb_base, bkv, tn);
+            const TileMeta km_next = load_meta(kn.bmp, kn.idx, k_tile, meta_on);
+            const TileMeta vm_next = load_meta(vn.bmp, vn.idx, v_tile, meta_on);
+            expand_keys<D>(km, k0, sb, s_img, lane, wave);
+            __syncthreads();   // the key image is whole, the key stream is read
+            store_block<TILES>(vg, s_stream, tid);
+            score_tiles<D, RT>(qf, s_img, s_xe, a.inv_sqrt_d, wave, l15, l4);
+            __syncthreads();   // x is whole, the key image is read, the value stream is staged
+            if (tb + 1 < tb1) load_block<TILES>(kn.nz, (cu32_p)kn.idx, tid, kg);   // (requested now, stored behind the softmax)
+            expand_values<D>(vm, vg.i0, sb, s_img, lane, wave);
+            softmax_rows<RT, false>(s_xe, s_alpha, M, L, srow, sq, 64);
+            __syncthreads();   // e, alpha and the value image are whole, the value stream is read
+            if (tb + 1 < tb1) {
+                store_block<TILES>(kg, s_stream, tid);
+                k0 = kg.i0;
+            }
+            accumulate_out<D, RT>(o, s_img, s_xe, s_alpha, wave, l15, l4);
+            __syncthreads();   // the value image, e and alpha are read; the next key stream is staged
+            km = km_next;
+            vm = vm_next;
+            kc = kn;
+            vc = vn;
+        }
+    } else {
+        // ---- window chunk: rows [w0, w0 + 64) of this head's dense window (a chunk beyond the window leaves its slabs at weight zero)
+        const int w0 = (x - a.runs) * 64, w_len = a.w_len;
+        if (w0 < w_len) {
+            const h16* kw = a.k_win + (int64_t)bkv * a.w_cap * D;
+            const h16* vw = a.v_win + (int64_t)bkv * a.w_cap * D;
+            // value rows, requested first and held: item = (token pair u, 8-channel piece pc), 32 x D / 8 items over 256 threads
+            constexpr int VI = D / 64;
+            uint4 va[VI], vb[VI];
+#pragma unroll
+            for (int k = 0; k < VI; k++) {
+                const int it = tid + kThreads * k, w = w0 + 2 * (it & 31), pc = it >> 5;
+                va[k] = vb[k] = make_uint4(0u, 0u, 0u, 0u);
+                if (w < w_len) va[k] = *reinterpret_cast<const uint4*>(vw + (int64_t)w * D + 8 * pc);
+                if (w + 1 < w_len) vb[k] = *reinterpret_cast<const uint4*>(vw + (int64_t)(w + 1) * D + 8 * pc);
+            }
+            // key image: the rows as they are, 16-byte pieces; rows at or beyond w_len are zeros
+#pragma unroll
+            for (int k = 0; k < D / 32; k++) {
+                const int p = tid + kThreads * k, t = p / (D / 8), pc = p % (D / 8);
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if (w0 + t < w_len) v = *reinterpret_cast<const uint4*>(kw + (int64_t)(w0 + t) * D + 8 * pc);
+                *reinterpret_cast<uint4*>(s_img + t * KROW + 8 * pc) = v;
+            }
+            __syncthreads();   // the key image is whole
+            score_tiles<D, RT>(qf, s_img, s_xe, a.inv_sqrt_d, wave, l15, l4);
+            __syncthreads();   // x is whole, the key image is read
+            // value image: the transpose, two tokens of a channel per 4-byte store (the 32 lanes of a half wave: 32 consecutive banks)
+#pragma unroll
+            for (int k = 0; k < VI; k++) {
+                const int it = tid + kThreads * k, u = it & 31, pc = it >> 5;
+                uint32_t* dst = reinterpret_cast<uint32_t*>(s_img + 8 * pc * kRowPad + 2 * u);
+                const auto put = [&](uint32_t a, uint32_t b, int c) {   // channels c, c + 1 of both tokens
+                    dst[c * (kRowPad / 2)] = (a & 0xffffu) | (b << 16);
+                    dst[(c + 1) * (kRowPad / 2)] = (a >> 16) | (b & 0xffff0000u);
+                };
+                put(va[k].x, vb[k].x, 0);
+                put(va[k].y, vb[k].y, 2);
+                put(va[k].z, vb[k].z, 4);
+                put(va[k].w, vb[k].w, 6);
+            }
+            // the causal limit: query token j = row % n_q sees window rows [0, w_len - n_q + j], `visible` of them in this chunk
+            softmax_rows<RT, true>(s_xe, s_alpha, M, L, srow, sq, w_len - a.n_q + srow % a.n_q + 1 - w0);
+            __syncthreads();   // e, alpha and the value image are whole
+            accumulate_out<D, RT>(o, s_img, s_xe, s_alpha, wave, l15, l4);
+        }
+    }
+    write_slabs<D, RT>(o, M, L, a.ws_o, a.ws_ml, ((int64_t)x * gridDim.y + bkv) * R, R, wave, l15, l4, srow, sq);
+}
+
+// Rows [row0, row0 + n_q) of every head's K and V window <- k_new / v_new [B', n_q, D]; thread = one 16-byte piece, blockIdx.y = side.
+__global__ __launch_bounds__(kThreads) void multi_query_append_kernel(const uint4* __restrict__ k_new, const uint4* __restrict__ v_new,
+                                                                      uint4* __restrict__ k_win, uint4* __restrict__ v_win, int n_q, int row0,
+                                                                      int w_cap, int D8, int total)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int pc = i % D8, j = (i / D8) % n_q, b = i / (D8 * n_q);
+    const uint4* src = blockIdx.y ? v_new : k_new;
+    uint4* dst = blockIdx.y ? v_win : k_win;
+    dst[((int64_t)b * w_cap + row0 + j) * D8 + pc] = src[i];
+}
+
+bool mq_shape_ok(int T, int window_capacity, int Bp, int groups, int n_q, int head_dim)
+{
+    if (n_q < 1 || groups < 1 || groups > 8 || (int64_t)n_q * groups > kMaxRows || Bp < 1 || Bp > 65535 || T < 0 || (T & 63)) return false;
+    if (window_capacity < n_q || window_capacity > kMaxWindow) return false;
+    return head_dim == 64 || head_dim == 128;
+}
+
+template <int D, bool EXT>
+void mq_launch(hipStream_t st, const MqArgs& a, const dim3 grid)
+{
+    switch ((a.R + 15) / 16) {
+        case 1: multi_query_decode_kernel<D, 1, EXT><<<grid, kThreads, 0, st>>>(a); break;
+        case 2: multi_query_decode_kernel<D, 2, EXT><<<grid, kThreads, 0, st>>>(a); break;
+        case 3: multi_query_decode_kernel<D, 3, EXT><<<grid, kThreads, 0, st>>>(a); break;
+        default: multi_query_decode_kernel<D, 4, EXT><<<grid, kThreads, 0, st>>>(a); break;
+    }
+}
+
+}  // namespace
+}  // namespace mustafar_shared
+
+extern "C" int64_t mustafar_decode_multi_query_workspace_bytes(int T, int window_capacity, int Bp, int num_key_value_groups, int n_q, int head_dim)
+{
+    using namespace mustafar_shared;
+    if (!mq_shape_ok(T, window_capacity, Bp, num_key_value_groups, n_q, head_dim)) return 0;
+    const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R, head_dim);
+    return (int64_t)((ntb + bpw - 1) / bpw + (window_capacity + 63) / 64) * Bp * R * (head_dim + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int mustafar_decode_multi_query(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                           const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, int T, int Bp,
+                                           int num_key_value_groups, int n_q, const void* q, void* k_window, void* v_window, const void* k_new,
+                                           const void* v_new, int window_len, int window_capacity, void* out, float* lse, void* workspace,
+                                           float sqrt_d, int head_dim)
+{
+    using namespace mustafar_shared;
+    if (!mq_shape_ok(T, window_capacity, Bp, num_key_value_groups, n_q, head_dim) || !(sqrt_d > 0.f)) return MUSTAFAR_EINVAL;
+    if (window_len < n_q || window_len > window_capacity || (k_new == nullptr) != (v_new == nullptr)) return MUSTAFAR_EINVAL;
+    if (T_base < 0 || T_base > T || (T_base & 63) || (T > 0 && T_base == 0)) return MUSTAFAR_EINVAL;
+    if (T > T_base && ((T_base & 255) || ((T - T_base) & 255) || (T - T_base) / 256 > kMaxExtents || !k_extents || !v_extents))
+        return MUSTAFAR_EINVAL;
+    if (!q || !out || !k_window || !v_window || !workspace || !lse || !aligned16(q) || !aligned16(out) || !aligned16(k_window) ||
+        !aligned16(v_window) || !aligned16(workspace) || !aligned16(k_new) || !aligned16(v_new) || ((uintptr_t)lse & 3))
+        return MUSTAFAR_EINVAL;
+    MqArgs a{};
+    if (T_base && (!side_of(k_base, T_base, Bp, head_dim, &a.k) || !side_of(v_base, T_base, Bp, head_dim, &a.v))) return MUSTAFAR_EINVAL;
+    const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R, head_dim);
+    const int runs = (ntb + bpw - 1) / bpw, slabs = runs + (window_capacity + 63) / 64;
+    const bool ext = T > T_base;
+    a.k_ext = ext ? k_extents : nullptr;
+    a.v_ext = ext ? v_extents : nullptr;
+    a.q = static_cast<const h16*>(q);
+    a.k_win = static_cast<const h16*>(k_window);
+    a.v_win = static_cast<const h16*>(v_window);
+    a.ws_o = static_cast<float*>(workspace);
+    a.ws_ml = a.ws_o + (int64_t)slabs * Bp * R * head_dim;
+    a.ntb = ntb; a.ntb_base = T_base / 64; a.bpw = bpw; a.runs = runs; a.n_q = n_q; a.R = R; a.w_len = window_len; a.w_cap = window_capacity;
+    a.inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (k_new) {
+        const int D8 = head_dim / 8, total = Bp * n_q * D8;
+        multi_query_append_kernel<<<dim3((total + kThreads - 1) / kThreads, 2), kThreads, 0, st>>>(
+            static_cast<const uint4*>(k_new), static_cast<const uint4*>(v_new), static_cast<uint4*>(k_window), static_cast<uint4*>(v_window), n_q,
+            window_len - n_q, window_capacity, D8, total);
+    }
+    const dim3 grid(slabs, Bp);
+    if (head_dim == 64) { if (ext) mq_launch<64, true>(st, a, grid); else mq_launch<64, false>(st, a, grid); }
+    else { if (ext) mq_launch<128, true>(st, a, grid); else mq_launch<128, false>(st, a, grid); }
+    // the fold of every row's slabs: (kv_heads, G, R) = (B', R, R) addresses row bkv * R + r of out / lse and of every slab
+    if (head_dim == 64) shared_merge_kernel<64><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);
+    else shared_merge_kernel<128><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);
+    return (int)hipGetLastError();
+}

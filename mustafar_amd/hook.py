@@ -21,6 +21,7 @@ key SpMV (+ window scores) -> softmax -> value SpMV (+ window p.V partials) -> s
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Tuple
@@ -577,21 +578,30 @@ class MustafarAttention:
         if step_counter is not None:
             return out, (k_c, k_w, v_c, v_w, C, kv_seq_len - 1)   # lengths advance with the device counter
         k_w.len = v_w.len = w_len
-        new = (k_c, k_w, v_c, v_w, C, kv_seq_len)
+        return out, self._close_step((k_c, k_w, v_c, v_w, C, kv_seq_len), defer_trigger)
+
+    def _close_step(self, new, defer_trigger: bool):
+        """The tail of a fused step whose rows are appended and counted in `new`: the 256-token trigger (model :324-398) when it is due,
+        or nothing with `defer_trigger` (run_triggers() then).  Returns the past to hand back."""
+        cfg = self.cfg
+        k_c, k_w, v_c, v_w, C, kv_seq_len = new
+        use_arena = isinstance(k_c, CompressedArena)
         if defer_trigger:
             # run_triggers() works on arena and extent caches (a first trigger, C == 0, makes an arena when cfg.arena says so): anything
             # else would come back with a cache of the wrong kind, or fail inside run_triggers -- refuse here
             if not (cfg.hd64_extents or use_arena or (cfg.arena and C == 0)):
                 raise RuntimeError("decode_fused(defer_trigger=True) needs an arena cache (MustafarConfig(arena=True)); "
                                    "tuple caches run their trigger inside the step")
-            return out, new
+            return new
         if not self.trigger_due(new):                                                                   # :324
-            return out, new
+            return new
         if cfg.hd64_extents:
-            return out, self._run_triggers_ext64([new])[0]
+            return self._run_triggers_ext64([new])[0]
+        D = k_w.buf.shape[3]
         if use_arena or (cfg.arena and C == 0):
             # prune (:325-326) + compress + append (:328-390) of the raw window rows in one launch
-            return out, self._trigger_one(*new, *self._kth(D))
+            return self._trigger_one(*new, *self._kth(D))
+        Bkv = k_w.buf.shape[0] * k_w.buf.shape[1]
         k_new, v_new = self._compress_front(k_w.buf, v_w.buf)
         if C == 0:
             k_c, v_c = k_new, v_new
@@ -600,7 +610,107 @@ class MustafarAttention:
             v_c = append_compressed(v_c, v_new, Bkv, C, 256, D)
         k_w.drop_front(256)                                                                             # :392-393
         v_w.drop_front(256)
-        return out, (k_c, k_w, v_c, v_w, C + 256, kv_seq_len)
+        return (k_c, k_w, v_c, v_w, C + 256, kv_seq_len)
+
+    # ---- several query tokens per call (multi_query.hip) ------------------------------------------------------------
+    def _fits_before_trigger(self, past, n_q: int) -> int:
+        """The largest n <= n_q such that no row but the last of an n-token call reaches a trigger point (`trigger_due`)."""
+        k_w, C, L = past[1], past[4], past[5]
+        w_len = k_w.len if isinstance(k_w, Window) else k_w.shape[2]
+        for j in range(n_q - 1):
+            if (L + j + 1 - self.cfg.residual_length - C) % 256 == 0 and w_len + j + 1 >= 256:
+                return j + 1
+        return n_q
+
+    def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False):
+        """n_q consecutive tokens of every sequence in one call: q [bsz, H, n_q, D], their new k / v [bsz, Hkv, n_q, D] -> (out
+        [bsz, H, n_q, D], past'), or (out, lse fp32 [bsz, H, n_q], past') with `return_lse`.  Token j attends to the cache, the window
+        and the new rows 0 .. j: what n_q decode_fused steps compute, with the compressed cache read once (speculative decoding, a short
+        follow-up turn).  Needs api="fused"; every cache kind decode_fused serves at this head dim (reference-layout lists, arenas with
+        extents or in place, ExtentCache64, nothing compressed yet); 1 to 8 q heads per kv head.  More than 64 // groups tokens run as
+        consecutive calls of at most that many.
+
+        The call appends the rows and never compresses: close it with `accept()`, which drops the rejected rows and runs the 256-token
+        trigger when it is due.  A trigger point may only be the LAST row of a call -- a call that would step over one raises ValueError
+        naming the largest n_q that fits.  No attention_mask in this version: left-padded batches keep using decode_fused."""
+        cfg = self.cfg
+        if cfg.api != "fused":
+            raise ValueError("decode_multi needs MustafarConfig(api='fused')")
+        groups = self.num_key_value_groups
+        if groups > 8:
+            raise ValueError(f"decode_multi serves 1 to 8 q heads per kv head (got {groups})")
+        bsz, H, n_q, D = query_states.shape
+        if H != self.num_heads or D != self.head_dim or n_q < 1 or key_states.shape != (bsz, self.num_key_value_heads, n_q, D) or \
+                value_states.shape != key_states.shape:
+            raise ValueError(f"decode_multi: q [bsz, {self.num_heads}, n_q, {self.head_dim}] with k / v [bsz, {self.num_key_value_heads}, n_q, "
+                             f"{self.head_dim}] (got {tuple(query_states.shape)}, {tuple(key_states.shape)}, {tuple(value_states.shape)})")
+        fits = self._fits_before_trigger(past, n_q)
+        if fits < n_q:
+            raise ValueError(f"decode_multi: {n_q} tokens would step over a 256-token trigger point; at most {fits} fit in this call "
+                             "(the trigger point may only be the last row: accept() then runs the trigger)")
+        past = self.to_fused(past)
+        per = 64 // groups
+        outs, lses = [], []
+        for s0 in range(0, n_q, per):
+            s1 = min(n_q, s0 + per)
+            o, l, past = self._decode_multi_call(query_states[:, :, s0:s1], key_states[:, :, s0:s1], value_states[:, :, s0:s1], past)
+            outs.append(o)
+            lses.append(l)
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
+        if not return_lse:
+            return out, past
+        return out, (lses[0] if len(lses) == 1 else torch.cat(lses, dim=2)), past
+
+    def _decode_multi_call(self, q, k_rows, v_rows, past):
+        """One mustafar_decode_multi_query call: at most 64 // groups tokens, appended to the windows and counted in the returned past."""
+        k_c, k_w, v_c, v_w, C, kv_len = past
+        bsz, H, n, D = q.shape
+        Bkv, groups, dev = bsz * self.num_key_value_heads, self.num_key_value_groups, q.device
+        w_len = k_w.len + n
+        k_w.reserve(w_len)
+        v_w.reserve(w_len)
+        if k_w.cap != v_w.cap or k_w.len != v_w.len:
+            raise RuntimeError("key/value windows must have the same length and capacity")
+        q = q.contiguous()
+        kn, vn = k_rows.contiguous(), v_rows.contiguous()
+        if isinstance(k_c, (CompressedArena, ExtentCache64)):   # (an arena is poll()ed by decode_args)
+            tables = C > k_c.tokens or isinstance(k_c, ExtentCache64)
+            (kv, vv, t_base, kt, vt), keep = k_c.decode_args(v_c, tables=tables)
+        elif k_c is None:
+            kv, vv, t_base, kt, vt, keep = None, None, 0, None, None, ()
+        else:
+            kz, vz = _flat_stream(k_c), _flat_stream(v_c)
+            views = [_lib.CacheView(c[0].data_ptr(), z.data_ptr(), c[1].data_ptr(), c[3].data_ptr(), 0, 0, 0) for c, z in ((k_c, kz), (v_c, vz))]
+            kv, vv, t_base, kt, vt, keep = ctypes.byref(views[0]), ctypes.byref(views[1]), C, None, None, (kz, vz, views)
+        L = _lib.load()
+        ws_bytes = L.mustafar_decode_multi_query_workspace_bytes(C, k_w.cap, Bkv, groups, n, D)
+        if ws_bytes <= 0:
+            raise ValueError(f"decode_multi: the library serves no call of {n} tokens x {groups} q heads per kv head, {C} compressed tokens, "
+                             f"a window of {k_w.cap} rows, head_dim {D}")
+        _, ws = self._scratch(dev, 0, 0, ws_bytes)
+        out = torch.empty((bsz, H, n, D), dtype=torch.float16, device=dev)
+        lse = torch.empty((bsz, H, n), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            err = L.mustafar_decode_multi_query(torch.cuda.current_stream(dev).cuda_stream, kv, vv, t_base, kt, vt, C, Bkv, groups, n,
+                                                q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(), w_len,
+                                                k_w.cap, out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D)
+        _lib.check(err, "mustafar_decode_multi_query")
+        del keep   # (alive until here: the call has been issued)
+        k_w.len = v_w.len = w_len
+        return out, lse, (k_c, k_w, v_c, v_w, C, kv_len + n)
+
+    def accept(self, past, rejected: int = 0, defer_trigger: bool = False):
+        """Close a decode_multi call: drop the `rejected` newest rows (0 <= rejected < the rows the window holds) -- only the host lengths
+        change, the rows stay in the buffer and the next append overwrites them -- then run the 256-token trigger exactly as a decode_fused
+        step does when it is due.  `defer_trigger`: return with the trigger not run, for run_triggers() over all layers."""
+        k_c, k_w, v_c, v_w, C, kv_len = past
+        if not isinstance(k_w, Window) or not isinstance(v_w, Window):
+            raise ValueError("accept() closes a decode_multi call: the past it returned (windows in appendable buffers)")
+        if not 0 <= rejected < min(k_w.len, v_w.len):
+            raise ValueError(f"accept: rejected must be in [0, {min(k_w.len, v_w.len)}) -- the window holds {k_w.len} rows (got {rejected})")
+        k_w.len -= rejected
+        v_w.len -= rejected
+        return self._close_step((k_c, k_w, v_c, v_w, C, kv_len - rejected), defer_trigger)
 
     def decode_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None):
         """One decode step over frozen compressed segments + the live cache: `frozen` is a list of `(k_cache, v_cache, tokens)` that
