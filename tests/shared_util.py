@@ -32,10 +32,11 @@ def level(w):
     return max(16.0, 64.0 / w)
 
 
-def needle_x(Dd, w):
-    """x = fp16(fp16(score) * fp32(1 / sqrt d)), score = level * QB * w exactly (q is zero outside the slot)."""
+def needle_x(Dd, w, boost=1):
+    """x = fp16(fp16(score) * fp32(1 / sqrt d)), score = boost * level * QB * w exactly (q is zero outside the slot)."""
     inv = np.float32(1.0 / np.float64(np.float32(math.sqrt(Dd))))
-    return float(np.float16(np.float32(np.float16(level(w) * QB * w)) * inv))
+    assert boost * level(w) * QB * w <= 2048
+    return float(np.float16(np.float32(np.float16(boost * level(w) * QB * w)) * inv))
 
 
 def other_x_max(Dd, w):
@@ -67,15 +68,16 @@ def assign_rows(positions, n_seqs, H, rng, T):
     return calls
 
 
-def needle_data(Dd, n_seqs, groups, Hkv, T, pos, seed, k_sparsity=0.7, device="cpu"):
+def needle_data(Dd, n_seqs, groups, Hkv, T, pos, seed, k_sparsity=0.7, device="cpu", boost=1):
     """K, V [1, Hkv, T, Dd] (ONE copy) and q [n_seqs, Hkv * groups, 1, Dd]: query row (s, h) attends to token pos[s, h] of kv head
     h // groups only.  Key noise: multiples of 1/4 in [-1, 1]; V: multiples of 2^-5 in [-2, 2].  Row r of a kv head owns channels
     [r w, (r + 1) w).  Asserts the gap (> 39: every other e is 0 in fp16, every other weight is absorbed in fp32) and that the oracle's
-    prune keeps each needle's slot.  Returns K, V, q, w."""
+    prune keeps each needle's slot.  boost: a power of two the needles' level is multiplied by -- at 2, on slots of 8 channels, every needle's x stands
+    more than 88 above every other x, so exp(x - a maximum that missed the needle) overflows fp32.  Returns K, V, q, w."""
     H, R = Hkv * groups, n_seqs * groups
     w = slot_width(Dd, R)
-    lv = level(w)
-    assert needle_x(Dd, w) - other_x_max(Dd, w) > 39
+    lv = boost * level(w)
+    assert needle_x(Dd, w, boost) - other_x_max(Dd, w) > 39
     pos = np.asarray(pos, np.int64)
     assert pos.shape == (n_seqs, H) and (pos >= 0).all() and (pos < T).all()
     gen = torch.Generator(device=device).manual_seed(seed)

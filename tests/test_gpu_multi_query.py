@@ -92,6 +92,31 @@ class Call:
         return self.out, self.lse
 
 
+def _run_spans(L_, C, cap, Bkv, groups, n_q, Dd):
+    """[(first block, one past the last block)] of every compressed run of a call, from the public workspace size alone.  The run length
+    depends on R and D only, so it is the largest block count that the same (cap, Bkv, groups, n_q, D) still serves as ONE run; the slab
+    count at C must then be the runs of that length plus the window chunks."""
+    per, chunks = Bkv * n_q * groups * (Dd + 2) * 4, (cap + 63) // 64
+
+    def runs(T):
+        ws = L_.mustafar_decode_multi_query_workspace_bytes(T, cap, Bkv, groups, n_q, Dd)
+        assert ws > 0 and ws % per == 0
+        return ws // per - chunks
+
+    assert runs(0) == 0 and runs(64) == 1
+    bpw = 1
+    while runs(64 * (bpw + 1)) == 1:
+        bpw += 1
+    ntb = C // 64
+    assert runs(C) == -(-ntb // bpw)
+    return [(b, min(ntb, b + bpw)) for b in range(0, ntb, bpw)]
+
+
+def _rule(R, Dd):
+    """Blocks per run, DESIGN.md 4.10 restated: the smallest count whose stream bytes (about 88 D a block) reach the slab bytes 8 R (D + 2)."""
+    return -(-8 * R * (Dd + 2) // (88 * Dd))
+
+
 def _model_ratios(out, lse, q, Kp, Vp, first, groups):
     """max |out - hook_model| / bound and |lse - lse_model| / bound over the tokens of a call: token j sees rows [0, first + j + 1) of
     Kp / Vp (pruned where compressed)."""
@@ -122,15 +147,15 @@ def _rand(B, Hkv, Ltot, groups, n_q, Dd, seed):
 
 
 # ---- needles: row (b, h, j) attends to ONE token --------------------------------------------------------------------------------------------
-def needle_data(Dd, B, Hkv, groups, n_q, Ltot, pos, C, seed, ks=S, twice=None):
+def needle_data(Dd, B, Hkv, groups, n_q, Ltot, pos, C, seed, ks=S, twice=None, boost=1):
     """K, V [B, Hkv, Ltot, Dd], q [B, H, n_q, Dd]: the row of q head h and query token j attends to token pos[b, h, j] of its kv head.
     The R = n_q x groups rows of a kv head own a slot each (tests/shared_util.py: width, level, key noise |k| <= 1, V multiples of 2^-5).
     twice [B, H, n_q] (-1: none): a needle of twice the level in the same slot -- the winner wherever the row can see it.  Needles among
-    the first C tokens must survive the oracle's prune.  Returns K, V, q, slot width."""
+    the first C tokens must survive the oracle's prune.  boost: see tests/shared_util.py.  Returns K, V, q, slot width."""
     H, R = Hkv * groups, n_q * groups
     w = su.slot_width(Dd, R)
-    lv = su.level(w)
-    assert su.needle_x(Dd, w) - su.other_x_max(Dd, w) > 39
+    lv = boost * su.level(w)
+    assert su.needle_x(Dd, w, boost) - su.other_x_max(Dd, w) > 39
     gen = torch.Generator(device="cpu").manual_seed(seed)
     K = torch.randint(-4, 5, (B, Hkv, Ltot, Dd), generator=gen).half() * 0.25
     V = torch.randint(-64, 65, (B, Hkv, Ltot, Dd), generator=gen).half() * 2.0 ** -5
@@ -166,20 +191,24 @@ def needle_want(V, pos, C, groups, vs=S):
     return torch.from_numpy(want).to(V.device)
 
 
-def _assert_needles(out, lse, V, pos, C, groups, Dd, w, what):
+def _assert_needles(out, lse, V, pos, C, groups, Dd, w, what, boost=1):
     want = needle_want(V, pos, C, groups)
     miss = (out.float() != want.float()).any(-1)
     assert not miss.any(), f"{what}: rows {miss.nonzero().tolist()} differ from their needle's V row"
-    assert torch.equal(lse, torch.full_like(lse, su.needle_x(Dd, w))), f"{what}: an LSE is not the needle's x"
+    assert torch.equal(lse, torch.full_like(lse, su.needle_x(Dd, w, boost))), f"{what}: an LSE is not the needle's x"
 
 
 # ---- 1. exact needles in the compressed part and the window -------------------------------------------------------------------------------
-@pytest.mark.parametrize("n_q,groups", [(1, 4), (3, 3), (4, 4), (8, 4), (16, 4), (8, 8), (2, 1)])
+# R = 35, 42, 48, 34: three row tiles (odd n_q with padded rows, a tile exactly full, groups = 2); R = 49: one row into the fourth tile
+NEEDLE_ROWS = [(1, 4), (3, 3), (4, 4), (8, 4), (16, 4), (8, 8), (2, 1), (7, 5), (6, 7), (8, 6), (17, 2), (7, 7)]
+
+
+@pytest.mark.parametrize("n_q,groups", NEEDLE_ROWS)
 @pytest.mark.parametrize("T", [0, 64, 320])
 @pytest.mark.parametrize("Dd", [64, 128])
 def test_exact_on_needles(pkg, Dd, T, n_q, groups):
     """Needles on token 0, every block edge, T - 1, window row 0, the last old window row and each token's own new row, spread over
-    the rows of as many calls as it takes."""
+    the rows of as many calls as it takes.  (needle_data asserts the slot width and the gap: one channel at D = 64 from R = 33 on.)"""
     B, Hkv, w0 = 1, 2, 5
     H, Ltot = Hkv * groups, T + w0 + n_q
     targets = (su.edge_positions(T) if T else []) + [T, T + w0 - 1]
@@ -199,8 +228,12 @@ def test_exact_on_needles(pkg, Dd, T, n_q, groups):
 
 
 # ---- 2. the causal limit, exact ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("w0", [0, 1, 62, 63, 64, 250])
-@pytest.mark.parametrize("Dd,n_q,groups", [(64, 4, 4), (128, 8, 4), (128, 3, 3)])
+#   (the largest window: w0 = 1000 at n_q = 8 gives a capacity of 1024, sixteen chunks, and the spare row behind window_len still exists)
+CAUSAL = [(Dd, n_q, groups, w0) for Dd, n_q, groups in [(64, 4, 4), (128, 8, 4), (128, 3, 3), (64, 7, 5), (128, 6, 7), (128, 12, 4)]
+          for w0 in [0, 1, 62, 63, 64, 250]] + [(128, 8, 4, 1000)]
+
+
+@pytest.mark.parametrize("Dd,n_q,groups,w0", CAUSAL)
 def test_the_causal_limit_is_exact(pkg, Dd, n_q, groups, w0):
     """Every row of query token j has its needle on window row w0 + j, its own new row and the last it may see; a needle of twice the level
     sits in the same slot one row later, which it must not see (for the last token: in the spare row behind the window).  One row too few
@@ -212,6 +245,7 @@ def test_the_causal_limit_is_exact(pkg, Dd, n_q, groups, w0):
     pos[:] = T + w0 + np.arange(n_q)
     K, V, q, w = needle_data(Dd, B, Hkv, groups, n_q, Ltot + 1, pos, T, seed=Dd + w0, twice=pos + 1)
     c = Call(pkg, K[:, :, :Ltot], V[:, :, :Ltot], T, n_q, groups, cap=(w0 + n_q + 1 + 63) // 64 * 64)
+    assert c.cap > w0 + n_q and (w0 != 1000 or c.cap == 1024)
     c.kw[:, :, w0 + n_q], c.vw[:, :, w0 + n_q] = K[:, :, Ltot], V[:, :, Ltot]   # the spare row behind window_len: visible to nobody
     out, lse = c.call(q)
     _assert_needles(out, lse, V, pos, T, groups, Dd, w, f"w0 {w0}")
@@ -249,6 +283,11 @@ SHAPES = [(1, 4, 64, 1, 64, (1, 1)),          # the window at one row
           (5, 4, 192, 128, 128, (2, 2)),      # R = 20: two blocks per run and a shorter last run; the window at its capacity
           (8, 4, 320, 65, 128, (2, 3)),       # R = 32: three blocks per run, a last run of two
           (16, 4, 704, 40, 64, (2, 6))]       # R = 64: six blocks per run, a last run of five
+# Row tiles and group counts the rows above leave out.  T and the shape follow from the run-length rule at the head dim (_rule): two runs
+# with a shorter last one, T = 64 (2 bpw - 1), or three one-block runs; a window of 65 .. 70 rows in a capacity of 128: the first tokens
+# see nothing in the second chunk.
+SHAPES += [(n_q, groups, None, 65 + n_q * groups % 6, 128, None)
+           for n_q, groups in [(7, 5), (6, 7), (8, 6), (17, 2), (11, 3), (17, 1), (7, 7)]]
 
 
 @pytest.mark.parametrize("ks,vs", [(0.5, 0.7), (0.7, 0.9)])
@@ -256,6 +295,10 @@ SHAPES = [(1, 4, 64, 1, 64, (1, 1)),          # the window at one row
 @pytest.mark.parametrize("Dd", [64, 128])
 def test_random_data_against_the_models(pkg, Dd, n_q, groups, T, w_len, cap, shape, ks, vs):
     B, Hkv = 2, 2
+    if shape is None:
+        bpw = _rule(n_q * groups, Dd)
+        T, shape = (192, (3, 1)) if bpw == 1 else (64 * (2 * bpw - 1), (2, bpw))
+        assert 65 <= w_len <= 70 and w_len - n_q < 64   # token 0 sees no column of the second chunk
     K, V, q = _rand(B, Hkv, T + w_len, groups, n_q, Dd, seed=T + Dd + n_q * groups)
     c = Call(pkg, K, V, T, n_q, groups, cap=cap, ks=ks, vs=vs)
     assert c.runs() == shape and (T // 64) % shape[1] == (0 if shape[1] == 1 else shape[1] - 1)
@@ -264,7 +307,8 @@ def test_random_data_against_the_models(pkg, Dd, n_q, groups, T, w_len, cap, sha
 
 
 # ---- the hook: pasts of every cache kind ---------------------------------------------------------------------------------------------------
-KINDS = {"list": dict(), "arena": dict(arena=True), "ext64": dict(hd64_extents=True)}
+#   (inplace: the arena whose trigger appends in place instead of listing an extent)
+KINDS = {"list": dict(), "arena": dict(arena=True), "inplace": dict(arena=True, extents=False), "ext64": dict(hd64_extents=True)}
 
 
 def _attn(kind, groups=4, Hkv=2, **kw):
@@ -314,18 +358,43 @@ def _hook_models(attn, out, lse, q, K, V, past_before, what):
 
 
 # ---- 5. extents --------------------------------------------------------------------------------------------------------------------------
+def _crossings(spans, ntb_base=4, per_extent=4):
+    """What each run of `spans` crosses: (run, "base->extent") / (run, "extent->extent"), the base being blocks [0, ntb_base) and extent e
+    blocks [ntb_base + per_extent e, + per_extent)."""
+    region = lambda b: -1 if b < ntb_base else (b - ntb_base) // per_extent
+    out = []
+    for i, (b0, b1) in enumerate(spans):
+        for b in range(b0 + 1, b1):
+            if region(b) != region(b - 1):
+                out.append((i, "base->extent" if region(b - 1) < 0 else "extent->extent"))
+    return out
+
+
+@pytest.mark.parametrize("n_q", [3, 8, 11, 13])
 @pytest.mark.parametrize("extents", [1, 2])
 @pytest.mark.parametrize("kind", ["arena", "ext64"])
-def test_extents(kind, extents):
-    """T_base = 256 and one or two extents at R = 32 (three blocks per run: runs cross base -> extent and extent -> extent).  Random data
-    against the models; needles on the first and last token of each extent; the same tokens consolidated into one view: the same bits."""
-    B, Hkv, groups, n_q = 1, 2, 4, 8
+def test_extents(pkg, kind, extents, n_q):
+    """T_base = 256 and one or two extents at R = 12, 32, 44 and 52: one to four row tiles of the EXT instantiations (groups = 4: the
+    decode_fused steps that grow an arena by extents need it).  R = 12: two blocks per run, no run crosses a boundary (per-block resolution
+    alone); R = 32: three blocks per run, run 1 crosses base -> extent; R = 44 and 52: five blocks per run, run 0 crosses base -> extent
+    and, with two extents, run 1 extent -> extent -- all read off the workspace size.  Random data against the models; needles on the
+    first and last token of the base and of each extent; the same tokens consolidated into one view: the same bits."""
+    B, Hkv, groups = 1, 2, 4
     attn = _attn(kind)
     Dd = attn.head_dim
     total = 256 * (extents + 1) + 32 + n_q
     K, V, q = _rand(B, Hkv, total, groups, n_q, Dd, seed=extents + Dd)
     past, n = _grow(attn, K, V, q[:, :, :1].contiguous(), extents)
     assert n + n_q == total and len(past[0].extents) == extents and past[0].tokens == 256
+    spans = _run_spans(pkg[0], past[4], past[1].cap, B * Hkv, groups, n_q, Dd)
+    crossed = _crossings(spans)
+    print(f"{kind} R={n_q * groups} {extents} extents: runs {spans}, crossings {crossed}")
+    if n_q == 3:
+        assert spans[0] == (0, 2) and not crossed
+    elif n_q == 8:
+        assert spans[0] == (0, 3) and (1, "base->extent") in crossed
+    else:
+        assert spans[0] == (0, 5) and (0, "base->extent") in crossed and (extents == 1 or (1, "extent->extent") in crossed)
     out, lse, new = attn.decode_multi(q, K[:, :, n:], V[:, :, n:], past, return_lse=True)
     assert new[5] == total and new[1].len == 32 + n_q
     _hook_models(attn, out, lse, q, K, V, (past[4], n), f"{kind} {extents} extents")
@@ -349,7 +418,7 @@ def test_extents(kind, extents):
 
 
 # ---- 6. one token against the existing call -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,Dd", [("list", 64), ("list", 128), ("arena", 128), ("ext64", 64)])
+@pytest.mark.parametrize("kind,Dd", [("list", 64), ("list", 128), ("arena", 128), ("inplace", 128), ("ext64", 64)])
 def test_one_token_against_decode_fused(kind, Dd):
     B, Hkv, groups, L0 = 2, 2, 4, 256 + 70
     attn = _attn(kind, Dd=Dd)
@@ -380,7 +449,7 @@ def _within_twice_the_bound(a, b, q, Kp, Vp, first, groups):
         assert r <= 1.0, f"token {j}: |multi - stepwise| / (2 bound) = {r:.3f}"
 
 
-@pytest.mark.parametrize("kind", ["list", "arena", "ext64"])
+@pytest.mark.parametrize("kind", ["list", "arena", "inplace", "ext64"])
 def test_six_tokens_against_six_steps_through_a_trigger(kind):
     """The prefill leaves 256 compressed tokens and a window of 282 rows: the sixth row brings it to residual_length + 256 and the trigger
     runs inside accept, as it runs inside the sixth decode_fused step."""
@@ -466,7 +535,7 @@ def test_a_captured_call_is_replayed_with_new_queries(pkg, Dd):
 
 
 # ---- 11. layout ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,Dd", [("list", 64), ("arena", 128)])
+@pytest.mark.parametrize("kind,Dd", [("list", 64), ("arena", 128), ("inplace", 128)])
 def test_each_sequence_and_head_reads_its_own_cache(kind, Dd):
     """batch 2, kv heads 2, a query that is not contiguous: needles that differ per sequence and head, half of them in the compressed part."""
     B, Hkv, groups, n_q, L0 = 2, 2, 4, 4, 256 + 40
@@ -483,3 +552,140 @@ def test_each_sequence_and_head_reads_its_own_cache(kind, Dd):
     out, lse, _ = attn.decode_multi(q_nc, K[:, :, L0:], V[:, :, L0:], _past(attn, K, V, L0), return_lse=True)
     assert out.is_contiguous()
     _assert_needles(out, lse, V, pos, 256, groups, Dd, w, kind)
+
+
+# ---- 12. from an empty cache, through the first trigger -------------------------------------------------------------------------------------
+def _pruned(attn, K, V, C):
+    Kp, Vp = K.clone(), V.clone()
+    Kp[:, :, :C], Vp[:, :, :C] = oracle_prune(K[:, :, :C], attn.cfg.k_sparsity), oracle_prune(V[:, :, :C], attn.cfg.v_sparsity)
+    return Kp, Vp
+
+
+@pytest.mark.parametrize("kind,Dd", [("list", 64), ("list", 128), ("arena", 128), ("inplace", 128), ("ext64", 64)])
+def test_from_an_empty_cache_through_the_first_trigger(kind, Dd):
+    """A prefill of 250 rows compresses nothing (C = 0, no cache object).  decode_multi serves the window alone (at D = 128 too, with an
+    LSE: decode_fused(return_lse=True) refuses that call); further calls are sized by _fits_before_trigger until the last row of one is
+    the trigger point at 288 rows, and accept() runs the FIRST trigger of the kind: the compressed front of a list, an arena from the raw
+    rows, an extent cache's base.  A twin takes the same rows through decode_fused steps.  Then one more call over the new cache."""
+    B, Hkv, groups, L0 = 2, 2, 4, 250
+    attn = _attn(kind, Dd=Dd)
+    Dd = attn.head_dim
+    total = 288 + 5
+    K, V, q = _rand(B, Hkv, total, groups, total - L0, Dd, seed=Dd + 17)   # q[:, :, i]: the query of token L0 + i
+    pa, pb = _past(attn, K, V, L0), _past(attn, K, V, L0)
+    assert pa[4] == 0 and pa[0] is None and pa[2] is None and pa[1].len == L0
+    Kp, Vp = K, V   # nothing is pruned before the trigger
+    n, fired, capped = L0, False, False
+    for want in (6, 12, 12, 12):
+        fit = attn._fits_before_trigger(pa, want)
+        capped |= fit < want
+        qs = q[:, :, n - L0:n - L0 + fit].contiguous()
+        a, la, pa = attn.decode_multi(qs, K[:, :, n:n + fit], V[:, :, n:n + fit], pa, return_lse=True)
+        _assert_models(a, la, qs, Kp, Vp, n, groups, f"{kind} D={Dd} C=0 tokens [{n}, {n + fit})")
+        b, pb = _steps(attn, qs, K, V, pb, n, fit)
+        _within_twice_the_bound(a, b, qs, Kp, Vp, n, groups)
+        n += fit
+        assert pa[5] == n and pa[1].len == n and pa[4] == 0
+        fired = attn.trigger_due(pa)
+        pa = attn.accept(pa)
+        if fired:
+            break
+        assert pa[4] == 0 and pa[0] is None
+    assert fired and capped and n == 288, "no call ended on the trigger point"
+    assert pa[4] == pb[4] == 256 and pa[5] == pb[5] == 288 and pa[1].len == pb[1].len == 32 and pa[3].len == pb[3].len == 32
+    assert type(pa[0]) is type(pb[0]) and pa[0] is not None
+    assert torch.equal(_bits(pa[1].view()), _bits(pb[1].view())) and torch.equal(_bits(pa[3].view()), _bits(pb[3].view()))
+    assert _same_cache(pa[0], pb[0]) and _same_cache(pa[2], pb[2])
+    # one more call, over the cache the first trigger made
+    qs = q[:, :, n - L0:].contiguous()
+    assert qs.shape[2] == 5
+    a, la, pa = attn.decode_multi(qs, K[:, :, n:], V[:, :, n:], pa, return_lse=True)
+    _hook_models(attn, a, la, qs, K, V, (256, n), f"{kind} D={Dd} after the first trigger")
+    assert pa[4] == 256 and pa[5] == total and pa[1].len == 37
+
+
+# ---- 13. a speculative loop with rejections, across a trigger, the spare rows poisoned ------------------------------------------------------
+#          (tokens asked for, drafts rejected): capped by _fits_before_trigger.  Round 2 ends on the trigger point and its rejection takes the
+#          window back off it; round 3 is capped to the four rows that reach it again, nothing rejected: the trigger fires; three rounds follow.
+ROUNDS = [(8, 3), (8, 0), (5, 4), (12, 0), (12, 7), (3, 2), (16, 0)]
+
+
+@pytest.mark.parametrize("kind,Dd", [("list", 64), ("arena", 128)])
+def test_a_speculative_loop_with_rejections_across_a_trigger(kind, Dd):
+    """Rounds of decode_multi + accept(rejected) against a twin that takes the accepted tokens alone through decode_fused steps.  On the
+    multi side the rows [len, cap) of both window buffers are NaN after every accept: they are spare by contract (the rejected rows
+    among them), so a stale read shows as NaN in out or lse.  A rejected draft's rows differ from the token accepted in its place."""
+    B, Hkv, groups, L0 = 2, 2, 4, 256 + 270
+    attn = _attn(kind, Dd=Dd)
+    accepted = sum(a - r for a, r in ROUNDS)   # (an upper limit: capped rounds accept fewer)
+    K, V, q = _rand(B, Hkv, L0 + accepted, groups, accepted, Dd, seed=Dd + 23)            # the accepted stream; q[:, :, i]: token L0 + i
+    Kd, Vd, qd = _rand(B, Hkv, 16, groups, 16, Dd, seed=Dd + 24)                          # drafts that get rejected
+    pruned = {C: _pruned(attn, K, V, C) for C in (256, 512)}
+    pa, pb = _past(attn, K, V, L0), _past(attn, K, V, L0)
+    n, fired_at, held_back = L0, None, False
+    for i, (want, rej) in enumerate(ROUNDS):
+        fit = attn._fits_before_trigger(pa, want)
+        assert rej < fit
+        keep = fit - rej
+        sl = slice(n - L0, n - L0 + keep)
+        qs = torch.cat([q[:, :, sl], qd[:, :, :rej]], 2).contiguous()
+        ks = torch.cat([K[:, :, n:n + keep], Kd[:, :, :rej]], 2)
+        vs = torch.cat([V[:, :, n:n + keep], Vd[:, :, :rej]], 2)
+        C = pa[4]
+        a, la, pa = attn.decode_multi(qs, ks, vs, pa, return_lse=True)
+        assert torch.isfinite(a.float()).all() and torch.isfinite(la).all(), f"round {i}: NaN / Inf in out or lse"
+        due = attn.trigger_due(pa)
+        pa = attn.accept(pa, rejected=rej)
+        for w in (pa[1], pa[3]):
+            w.buf[:, :, w.len:] = NAN
+        b, pb = _steps(attn, qs, K, V, pb, n, keep)
+        _within_twice_the_bound(a[:, :, :keep], b, qs, *pruned[C], n, groups)
+        n += keep
+        if due and rej:      # the window reached the trigger point, the rejection took it back: nothing fires
+            held_back = True
+            assert not attn.trigger_due(pa) and pa[4] == C and pa[1].len == 288 - rej
+        if due and not rej:
+            assert fired_at is None and held_back and fit < want and pa[4] == C + 256 and pa[1].len == 32
+            fired_at = i
+        assert pa[4] == pb[4] and pa[5] == pb[5] == n and pa[1].len == pb[1].len == pa[3].len == pb[3].len == n - pa[4]
+    assert held_back and fired_at is not None and len(ROUNDS) - 1 - fired_at >= 3
+    assert pa[4] == pb[4] == 512 and pa[5] == pb[5] == n
+    assert torch.equal(_bits(pa[1].view()), _bits(pb[1].view())) and torch.equal(_bits(pa[3].view()), _bits(pb[3].view()))
+    assert _same_cache(pa[0], pb[0]) and _same_cache(pa[2], pb[2])
+
+
+# ---- 14. many slabs through the merge; the largest window -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("Dd", [64, 128])
+def test_more_than_64_slabs_through_the_merge(pkg, Dd):
+    """R = 8 is one block per run: 4608 tokens are 72 runs, with the window chunks more than the 64 lanes of the merge's max loop and
+    several trips of its phase loop, in the (B', R, R) addressing of this entry point."""
+    B, Hkv, groups, n_q, T, w_len = 2, 2, 4, 2, 4608, 70
+    K, V, q = _rand(B, Hkv, T + w_len, groups, n_q, Dd, seed=Dd + 31)
+    c = Call(pkg, K, V, T, n_q, groups, cap=128)
+    runs, bpw = c.runs()
+    assert (runs, bpw) == (72, 1) and runs + (c.cap + 63) // 64 > 64
+    out, lse = c.call(q)
+    _assert_models(out, lse, q, c.Kp, c.Vp, T + w_len - n_q, groups, f"D={Dd} {runs} runs + 2 chunks")
+    # On random data every slab's maximum is much the same, and the fold is the same sum under any maximum that does not overflow.  So:
+    # needles of twice the level on the first and last token of runs 64 .. 71.  Their x stands more than 88 above everything in the
+    # first 64 slabs: a maximum taken over those alone makes exp() overflow.
+    pos = np.zeros((B, Hkv * groups, n_q), np.int64)
+    late = [t for b in range(64, 72) for t in (64 * b, 64 * b + 63)]
+    for i, idx in enumerate(np.ndindex(*pos.shape)):
+        pos[idx] = late[i % len(late)]
+    K, V, q, w = needle_data(Dd, B, Hkv, groups, n_q, T + w_len, pos, T, seed=Dd + 32, boost=2)
+    assert su.needle_x(Dd, w, 2) - su.other_x_max(Dd, w) > 88.8   # (exp(88.73) is the first fp32 infinity)
+    out, lse = Call(pkg, K, V, T, n_q, groups, cap=128).call(q)
+    _assert_needles(out, lse, V, pos, T, groups, Dd, w, f"D={Dd} needles in runs 64 .. 71", boost=2)
+
+
+@pytest.mark.parametrize("Dd", [64, 128])
+def test_the_largest_window(pkg, Dd):
+    """window_len = capacity = 1024, the library's limit: sixteen chunks, every one of them full."""
+    B, Hkv, groups, n_q, T, w_len = 2, 2, 4, 8, 64, 1024
+    K, V, q = _rand(B, Hkv, T + w_len, groups, n_q, Dd, seed=Dd + 37)
+    c = Call(pkg, K, V, T, n_q, groups, cap=1024)
+    assert c.w_len == c.cap == 1024 and c.runs() == (1, 1)
+    assert pkg[0].mustafar_decode_multi_query_workspace_bytes(T, 1025, B * Hkv, groups, n_q, Dd) == 0   # (1024 is the limit)
+    out, lse = c.call(q)
+    _assert_models(out, lse, q, c.Kp, c.Vp, T + w_len - n_q, groups, f"D={Dd} window 1024")

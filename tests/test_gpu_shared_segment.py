@@ -52,7 +52,11 @@ def _assert_models(out, lse, q, Kp, Vp, groups, what):
 
 
 # ---- 1. exact, on needles ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,groups", [(1, 4), (3, 3), (4, 4), (8, 4), (16, 4), (8, 8)])
+# R = 35, 48 and 33: three row tiles (wave 3 idles in the softmax step) -- padded rows, a tile exactly full, one row into the tile
+RT3 = [(5, 7), (12, 4), (11, 3)]
+
+
+@pytest.mark.parametrize("n,groups", [(1, 4), (3, 3), (4, 4), (8, 4), (16, 4), (8, 8)] + RT3)
 @pytest.mark.parametrize("T", [64, 576])
 @pytest.mark.parametrize("Dd", [64, 128])
 def test_exact_on_needles(pkg, Dd, T, n, groups):
@@ -68,6 +72,24 @@ def test_exact_on_needles(pkg, Dd, T, n, groups):
         miss = xd.needle_misses(out, su.needle_expect(V, pos, groups))
         assert not miss.any(), f"call {i}: rows {miss.nonzero().tolist()} differ from their needle's V row"
         assert torch.equal(lse, torch.full_like(lse, su.needle_x(Dd, w))), f"call {i}: an LSE is not the needle's x"
+
+
+@pytest.mark.parametrize("Dd", [64, 128])
+def test_needles_beyond_the_64th_slab(pkg, Dd):
+    """R = 8 is one block per run: 4608 tokens are 72 slabs, more than the 64 lanes of the merge's max loop.  On random data (shape c) the
+    fold is the same sum under any maximum that does not overflow; here every row's needle, of twice the level, sits in slabs 64 .. 71
+    and its x stands more than 88 above everything in the first 64: a maximum taken over those alone makes exp() overflow."""
+    n, groups, Hkv, T = 2, 4, 2, 4608
+    assert su.run_shape(pkg[0], T, Hkv, groups, n, Dd) == (72, 1, 1)
+    late = [t for b in range(64, 72) for t in (64 * b, 64 * b + 63)]
+    pos = np.asarray([late[i % len(late)] for i in range(n * Hkv * groups)], np.int64).reshape(n, Hkv * groups)
+    K, V, q, w = su.needle_data(Dd, n, groups, Hkv, T, pos, seed=Dd + 9, boost=2)
+    assert su.needle_x(Dd, w, 2) - su.other_x_max(Dd, w) > 88.8   # (exp(88.73) is the first fp32 infinity)
+    K, V, q = K.to(DEV), V.to(DEV), q.to(DEV)
+    out, lse = su.SharedCall(pkg, oracle_prune(K, S), oracle_prune(V, S), groups, n).call(q)
+    miss = xd.needle_misses(out, su.needle_expect(V, pos, groups))
+    assert not miss.any(), f"rows {miss.nonzero().tolist()} differ from their needle's V row"
+    assert torch.equal(lse, torch.full_like(lse, su.needle_x(Dd, w, 2))), "an LSE is not the needle's x"
 
 
 # ---- 2. random data against the models ----------------------------------------------------------------------------------------------------
@@ -89,8 +111,8 @@ def _t_for(L_, shape, Hkv, groups, n, Dd):
 
 
 @pytest.mark.parametrize("ks,vs", [(0.5, 0.7), (0.7, 0.9)])
-@pytest.mark.parametrize("shape", ["a", "b", "c"])
-@pytest.mark.parametrize("n,groups", [(1, 4), (5, 4), (8, 4), (8, 8)])
+@pytest.mark.parametrize("n,groups,shape", [(n, groups, shape) for n, groups in [(1, 4), (5, 4), (8, 4), (8, 8)] for shape in "abc"] +
+                         [(n, groups, shape) for n, groups in RT3 for shape in "ab"])   # (c is 32512 tokens: not again per row tile)
 @pytest.mark.parametrize("Dd", [64, 128])
 def test_random_data_against_the_models(pkg, Dd, n, groups, shape, ks, vs):
     Hkv = 1 if shape == "c" else 2
