@@ -44,47 +44,36 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+from .compression import pieces_of
+from .reflayout import FlatStreams, StatusPool, _round_up, append_compressed, nz_offset_from_idxs
 
 DEFAULT_SLACK = 0.03
 
 
-class ExtentPool:
+class ExtentPool(StatusPool):
     """ONE allocation holding the extents of one trigger of every layer (2 per layer: K, V -- all of one geometry: 256 tokens, the
     largest region any layer expects), their status words ([flag, K lengths, V lengths] per layer) and the compression scratch;
     initialised by four launches.  The extents are `CompressedArena`s carved from it (they keep the allocation alive)."""
 
     def __init__(self, n_layers: int, heads: int, device, nz_cap: int):
-        self.n, self.heads, self.device, self.nz_cap, self.used = n_layers, heads, device, nz_cap, False
+        super().__init__(n_layers, heads, device)
+        self.nz_cap, self.used = nz_cap, False
         offs, ext_bytes = CompressedArena._layout(heads, 256, nz_cap)
         self.ext_bytes, self._offs = ext_bytes, offs
         ne = 2 * n_layers
-        self.status_words = 1 + 2 * heads                                  # int64 per layer: flag (low 4 bytes), K totals, V totals
         status_bytes = _round_up(n_layers * self.status_words * 8, 256)
         scratch_bytes = _round_up(n_layers * int(_lib.load().mustafar_compress_scratch_bytes(heads, 256)), 256)
         self.buf = torch.empty(ne * ext_bytes + status_bytes + scratch_bytes, dtype=torch.uint8, device=device)
-        self.status = self.buf[ne * ext_bytes:ne * ext_bytes + n_layers * self.status_words * 8].view(torch.int64).view(n_layers, self.status_words)
         self.scratch = self.buf[ne * ext_bytes + status_bytes:]
         tiles = 256 * CompressedArena.TILES_PER_TOKEN
         w = self.buf[:ne * ext_bytes].view(torch.int32).view(ne, ext_bytes // 4)
         w[:, offs["nz_offset"] // 4:offs["nz_offset"] // 4 + heads] = _head_index(heads, device) * (nz_cap // 8)      # stream starts of the heads
         torch.as_strided(w, (ne, heads), (ext_bytes // 4, tiles + 1), offs["idx"] // 4).zero_()                         # offset 0 of every head
         w[:, offs["totals"] // 4:offs["flag"] // 4 + 1].zero_()                                                          # the extents' OWN lengths / flag words (an in-place append into one would read them)
-        self.status.zero_()                                                                                              # flags (and lengths)
-        self._host = torch.empty((n_layers, self.status_words), dtype=torch.int64).pin_memory()                         # landing area of read_status()
+        self._adopt_status(self.buf[ne * ext_bytes:ne * ext_bytes + n_layers * self.status_words * 8])                  # flags (and lengths), landing area of read_status()
 
     def extent(self, j: int, which: str, slack: float) -> "CompressedArena":
         return CompressedArena(self.heads, which, self.device, 256, self.nz_cap, slack, storage=self.buf[j * self.ext_bytes:(j + 1) * self.ext_bytes])
-
-    def totals_ptr(self, j: int) -> int:       # extent j = 2 * layer + side
-        return self.status.data_ptr() + ((j // 2) * self.status_words + 1 + (j % 2) * self.heads) * 8
-
-    def flag_ptr(self, layer: int) -> int:
-        return self.status.data_ptr() + layer * self.status_words * 8
-
-    def read_status(self) -> torch.Tensor:
-        self._host.copy_(self.status, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self._host
 
 
 compress_fallbacks = 0   # appends repeated in the two-pass form because a block of the one-pass launch gave up waiting (round 5; never seen outside tests)
@@ -93,10 +82,6 @@ compress_fallbacks = 0   # appends repeated in the two-pass form because a block
 class ArenaAppendTimeout(RuntimeError):
     """The one-pass compression launch gave up waiting for a predecessor block's length (device flag bit 1).  The appended
     tokens are incomplete; MUSTAFAR_COMPRESS=twopass selects the form without that dependence."""
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 def _cap_rows(tokens: int, slack: float) -> int:
@@ -124,6 +109,7 @@ class CompressedArena:
     MAX_EXTENTS = 512     # appended 256-token extents listed in the device table before a consolidation: 128 k tokens of generation, i.e. every
                           # length the one-pass launch serves (round 3: 64 -- a 170-ms copy of the cache every 16 k tokens at c3; the table is 28 KB)
     VIEW_BYTES = ctypes.sizeof(_lib.CacheView)
+    lse_reads_tables = False   # a call with an LSE over the base alone passes null tables (hook._call_decode)
 
     def __init__(self, heads: int, which: str, device, cap_tokens: int, nz_cap: int, slack: float = DEFAULT_SLACK,
                  storage: Optional[torch.Tensor] = None):
@@ -230,13 +216,15 @@ class CompressedArena:
         return ctypes.byref(self._view)
 
     def decode_args(self, v_arena: "CompressedArena", tables: bool):
-        """How this K arena and its V arena arrive at a fused decode call (hook._call_decode): `(k_view_ptr, v_view_ptr, T_base,
-        k_table, v_table)` -- the device tables of the extents when `tables`, else None -- and the tensors to keep until the call is
-        issued (none: the arenas own everything named)."""
+        """How this K arena and its V arena arrive at a call (the cache protocol of reflayout.py; hook._call_decode): `(k_view_ptr,
+        v_view_ptr, T_base, k_table, v_table)` -- the device tables of the extents when `tables`, else None -- and the tensors to keep
+        until the call is issued (none: the arenas own everything named).  The views are taken anew at every call."""
         self.poll()      # a failed asynchronous append is reported before the cache is read again (no host stall)
         v_arena.poll()
         kt, vt = (self.ext_table.data_ptr(), v_arena.ext_table.data_ptr()) if tables else (None, None)
         return (self.view_ptr(), v_arena.view_ptr(), self.tokens, kt, vt), ()
+
+    view_args = decode_args   # (an arena always arrives as views)
 
     def bytes_in_use(self) -> int:
         t = self.tokens * self.TILES_PER_TOKEN
@@ -654,7 +642,6 @@ class CompressedArena:
 
     def to_reference(self) -> list:
         """[bitmaps int64 [B', 2T], idxs int32 [B', 2T+1], list of B' fp16 streams, nz_offset] (contiguous copies)."""
-        from .hook import append_compressed
         base = self._base_reference()
         if not self.extents:
             return base
@@ -665,8 +652,6 @@ class CompressedArena:
         return [base[0].view(self.heads, -1), base[1].view(self.heads, -1), base[2], base[3]]
 
     def _base_reference(self) -> list:
-        from .compression import pieces_of
-        from .hook import FlatStreams, nz_offset_from_idxs
         t = self.tokens * self.TILES_PER_TOKEN
         bmp = self.bmp[:, :t].contiguous()
         idx = self.idx[:, :t + 1].contiguous()

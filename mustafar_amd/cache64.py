@@ -1,27 +1,28 @@
-"""The head_dim-64 compressed cache that grows by extents (MustafarConfig(hd64_extents=True)).
+"""The head_dim-64 compressed cache that grows by extents (MustafarConfig(hd64_extents=True)), and the head_dim-64 prefill compressed
+from the raw rows (MustafarConfig(hd64_raw_prefill=True): `compress_raw_pair_hd64`, which shares the extent layout and the gather launch).
 
 At D = 64 the cache is the reference's tuple `[bitmaps, idxs, nzs, nz_offset]`, and the reference's 256-token trigger re-copies all of
-it (`hook.append_compressed`: a `torch.cat` per array and head), so every array moves and a captured decode graph dies with every
+it (`reflayout.append_compressed`: a `torch.cat` per array and head), so every array moves and a captured decode graph dies with every
 trigger.  `ExtentCache64` keeps one side (K or V) of one layer the way `CompressedArena` keeps it at D = 128 once extents are on:
 
   * the BASE is the reference-layout arrays of the prefill, exactly as the two-pass conversion makes them.  Nothing is ever appended
     to it in place, so it needs no spare room and no strides;
   * a trigger compresses its 256 window rows into a small cache of their own, an EXTENT (mustafar_trigger_compress_batch_hd: one launch
     per layer from the raw rows), and lists the extent's view in a DEVICE table of `MAX_EXTENTS` mustafar_cache_view entries that
-    the extents form of the fused decode call reads (hook._call_decode).  The table is created with the cache -- before any graph can name it (a table created
+    the extents form of the fused decode call reads (`decode_args` / `view_args`: the cache protocol of reflayout.py).  The table is created with the cache -- before any graph can name it (a table created
     inside a capture would live in the graph's pool and be zero-filled again by every replay) -- and an entry is written once;
   * the extents of ONE trigger of ALL layers are carved from one pooled allocation (`ExtentPool64`) together with the layers' status
     words `[flag, K lengths, V lengths]`, which one copy brings to the host.  Regions are housed tight -- the base's measured halfs per
     token + 4 %, as cache.py does at D = 128; a worst-case region would be as large as the dense rows -- and a layer whose flag shows
     bit 0 (a head outgrew its region: rows full of ties) is redone on its own at the measured size before any window slides.
 
-`to_reference()` concatenates base and extents the way the model appends (`hook.append_compressed`): the same tensors, bit for bit,
+`to_reference()` concatenates base and extents the way the model appends (`reflayout.append_compressed`): the same tensors, bit for bit,
 that the tuple path holds after the same triggers.  `consolidate()` (a full table: 512 extents are 128 k generated tokens) builds the
 same cache on the device: the reference-layout arrays at exact size from the lengths the host already holds (`base_used`, every
 extent's `used`), and ONE mustafar_cache_gather_hd launch over base + table that copies bitmaps, shifts offsets and moves every head's
 stream into place -- one copy of the cache, nothing read back, every address new, so a captured graph must be taken again.
 `consolidate(via_reference=True)` keeps the route through `to_reference()` (a `torch.cat` of the whole cache per extent) for comparison.
-The same launch ends a prefill compressed from the raw rows in 256-token chunks (`compression.compress_raw_pair_hd64`).
+The same launch ends a prefill compressed from the raw rows in 256-token chunks (`compress_raw_pair_hd64`, below).
 """
 from __future__ import annotations
 
@@ -31,14 +32,12 @@ from typing import List, Optional
 import torch
 
 from . import _lib
+from .compression import _compress, _offsets_mirror, _stream_ptr, hd64_staging_region, pieces_of   # (hd64_staging_region: also this module's name for it)
+from .reflayout import FlatStreams, ListCache, StatusPool, _round_up, append_compressed
 
 D = 64
 EXT_TOKENS = 256
 VIEW_BYTES = ctypes.sizeof(_lib.CacheView)
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 def _head_lengths(idx: torch.Tensor, heads: int) -> torch.Tensor:
@@ -62,25 +61,22 @@ class Extent64:
 
     def reference(self) -> list:
         """[bitmaps, idxs, per-head streams, None]: what `_compress` returns for these 256 tokens (append_compressed reads the first three)."""
-        from .hook import FlatStreams
         return [self.bmp.reshape(-1), self.idx.reshape(-1), FlatStreams([self.nz[h, :int(self.used[h])] for h in range(self.heads)]), None]
 
 
-class ExtentPool64:
+class ExtentPool64(StatusPool):
     """ONE allocation for the 2 x n extents of one trigger of n layers (K, V per layer; one region size) and the layers' status words
-    (int64 [n][1 + 2 heads]: flag in the low 4 bytes, K lengths, V lengths).  Only the status words are initialised (zeroed): the
-    compression launch writes every other word it or the decode launch reads."""
+    (reflayout.StatusPool).  Only the status words are initialised (zeroed): the compression launch writes every other word it or the
+    decode launch reads."""
 
     def __init__(self, n_layers: int, heads: int, device, region_halfs: int):
         assert region_halfs > 0 and region_halfs % 8 == 0
-        self.n, self.heads, self.device, self.region = n_layers, heads, device, region_halfs
+        super().__init__(n_layers, heads, device)
+        self.region = region_halfs
         _, self.ext_bytes = self.layout(heads, region_halfs)
-        self.status_words = 1 + 2 * heads
         ne = 2 * n_layers
         self.buf = torch.empty(ne * self.ext_bytes + n_layers * self.status_words * 8, dtype=torch.uint8, device=device)
-        self.status = self.buf[ne * self.ext_bytes:].view(torch.int64).view(n_layers, self.status_words)
-        self.status.zero_()
-        self._host = torch.empty((n_layers, self.status_words), dtype=torch.int64).pin_memory()
+        self._adopt_status(self.buf[ne * self.ext_bytes:])
 
     @staticmethod
     def layout(heads: int, region_halfs: int):
@@ -93,33 +89,19 @@ class ExtentPool64:
     def extent(self, j: int) -> Extent64:   # j = 2 * layer + side
         return Extent64(self.buf[j * self.ext_bytes:(j + 1) * self.ext_bytes], self.heads, self.region)
 
-    def totals_ptr(self, j: int) -> int:
-        return self.status.data_ptr() + ((j // 2) * self.status_words + 1 + (j % 2) * self.heads) * 8
-
-    def flag_ptr(self, layer: int) -> int:
-        return self.status.data_ptr() + layer * self.status_words * 8
-
-    def read_status(self) -> torch.Tensor:
-        """ONE copy into pinned memory + ONE wait."""
-        self._host.copy_(self.status, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self._host
-
 
 class ExtentCache64:
     MAX_EXTENTS = 512   # entries of the device table (the extents form of the fused decode call takes at most 512)
+    lse_reads_tables = True   # a call with an LSE reads the extents form even over the base alone (hook._call_decode)
 
     def __init__(self, base: list, which: str, heads: int, tokens: int):
         """base: the reference-layout `[bitmaps, idxs, FlatStreams, nz_offset]` of `tokens` tokens (a multiple of 256)."""
         assert which in ("key", "value") and tokens > 0 and tokens % 256 == 0
         self.base, self.which, self.heads, self.tokens = base, which, heads, tokens
-        bmp, idx, nzs, off = base
-        self.device = bmp.device
-        flat = nzs.flat
-        self.base_used = _head_lengths(idx, heads)
-        self._flat = flat   # (kept: the view below holds its address)
-        self.base_view = _lib.CacheView(bmp.data_ptr(), flat.data_ptr() if flat is not None and flat.numel() else None, idx.data_ptr(),
-                                        off.data_ptr(), 0, 0, 0)
+        self.device = base[0].device
+        self.base_used = _head_lengths(base[1], heads)
+        self._base = ListCache(base, tokens)   # (kept: it holds the flat stream and the view of the base)
+        self.base_view = self._base.view
         self.table = torch.zeros(self.MAX_EXTENTS * VIEW_BYTES, dtype=torch.uint8, device=self.device)
         self.extents: List[Extent64] = []
 
@@ -130,14 +112,21 @@ class ExtentCache64:
     def view_ptr(self):
         return ctypes.byref(self.base_view)
 
+    def bytes_in_use(self) -> int:
+        """Bytes of the four arrays of the base and of every extent."""
+        return self._base.bytes_in_use() + \
+            sum(self.heads * (256 * 8 + 257 * 4 + 4) + int(e.used.sum()) * 2 for e in self.extents)
+
+    def view_args(self, v_cache: "ExtentCache64", tables: bool):
+        """`(k_view_ptr, v_view_ptr, T_base, k_table, v_table)`, the tables null unless `tables`, and the tensors to keep until the call
+        is issued (none: the caches own everything named)."""
+        kt, vt = (self.table.data_ptr(), v_cache.table.data_ptr()) if tables else (None, None)
+        return (self.view_ptr(), v_cache.view_ptr(), self.tokens, kt, vt), ()
+
     def decode_args(self, v_cache: "ExtentCache64", tables: bool):
-        """How this K cache and its V cache arrive at a fused decode call (hook._call_decode): `(k_view_ptr, v_view_ptr, T_base,
-        k_table, v_table)` when `tables`, else the eight arrays of the two bases (the plain D = 64 launch: the base alone) -- and the
-        tensors to keep until the call is issued (none: the caches own everything named)."""
-        if tables:
-            return (self.view_ptr(), v_cache.view_ptr(), self.tokens, self.table.data_ptr(), v_cache.table.data_ptr()), ()
-        kb, vb = self.base_view, v_cache.base_view
-        return (kb.bmp, kb.nz, kb.idx, kb.nz_offset, vb.bmp, vb.nz, vb.idx, vb.nz_offset), ()
+        """How this K cache and its V cache arrive at a fused decode call (hook._call_decode): `view_args` when `tables`, else the
+        eight arrays of the two bases (the plain D = 64 launch: the base alone)."""
+        return self.view_args(v_cache, True) if tables else (self._base.decode_args(v_cache._base)[0], ())
 
     def slot_ptr(self, i: int) -> int:
         return self.table.data_ptr() + i * VIEW_BYTES
@@ -214,8 +203,7 @@ class ExtentCache64:
 
     # ---- back to the reference layout ----------------------------------------------------------------------------------------------
     def to_reference(self) -> list:
-        """`[bitmaps, idxs, FlatStreams, nz_offset]` of base + extents, built the way the model appends (hook.append_compressed)."""
-        from .hook import append_compressed
+        """`[bitmaps, idxs, FlatStreams, nz_offset]` of base + extents, built the way the model appends (reflayout.append_compressed)."""
         ref, tokens = self.base, self.tokens
         for e in self.extents:
             ref = append_compressed(ref, e.reference(), self.heads, tokens, EXT_TOKENS, D)
@@ -229,8 +217,6 @@ class ExtentCache64:
             return self
         if via_reference or self.base_view.nz is None:   # (a base without any stream: nothing for the launch to align on)
             return type(self)(self.to_reference(), self.which, self.heads, self.total_tokens)
-        from .compression import pieces_of
-        from .hook import FlatStreams
         T, H, dev = self.total_tokens, self.heads, self.device
         used = self.base_used.clone()
         for e in self.extents:
@@ -248,3 +234,94 @@ class ExtentCache64:
                                                        self.table.data_ptr(), len(self.extents), H, D)
         _lib.check(err, "mustafar_cache_gather_hd")
         return type(self)([bmp, idx, FlatStreams(pieces_of(packed, offs), flat=packed), nz_offset], self.which, H, T)
+
+
+# ---- a prefill compressed from the RAW rows (MustafarConfig(hd64_raw_prefill=True)) ---------------------------------------------------------
+HD64_MAX_RAW_TOKENS = 512 * 256   # mustafar_prefill_compress_hd / mustafar_cache_gather_hd take at most 512 chunks
+hd64_prefill_repeats = 0          # compression launches repeated at the measured region size (rows with ties at the threshold)
+
+
+def _prune_kth_hd64(x: torch.Tensor, kth: int) -> torch.Tensor:
+    """prune_magnitude with the k-th-smallest index given (0: the rows are pruned already)."""
+    xc = x.contiguous()
+    if xc.data_ptr() % 16:
+        xc = xc.clone()
+    if kth <= 0:
+        return xc
+    out = torch.empty_like(xc)
+    with torch.cuda.device(x.device):
+        err = _lib.load().mustafar_prune_magnitude(_stream_ptr(x.device), xc.data_ptr(), out.data_ptr(), xc.numel() // 64, 64, kth)
+    _lib.check(err, "mustafar_prune_magnitude")
+    return out
+
+
+def compress_raw_pair_hd64(k: torch.Tensor, v: torch.Tensor, tokens: int, kth_k: int, kth_v: int):
+    """Raw K / V [B, Hkv, L, 64] fp16 -> the reference-layout caches `[bitmaps, idxs, FlatStreams, nz_offset]` of the first `tokens` rows
+    of every head (a multiple of 256): what `compression._compress(prune_magnitude(x[:, :, :tokens]).reshape(B', -1, 64), which)` returns, tensor
+    for tensor, without a pruned copy and with ONE read of the rows and ONE host wait:
+      1. mustafar_prefill_compress_hd: every 256-token chunk of every head becomes an extent of its own in a staging allocation;
+      2. one copy of the flag and the chunk lengths to pinned memory and one wait (the return type needs the sizes);
+      3. mustafar_cache_gather_hd per side: the chunks, offsets shifted, into the exact-size arrays.
+    A chunk whose rows tie at the threshold keeps more than the staging bound: flag bit 0, and the launch is repeated ONCE at the
+    measured maximum (counted in `hd64_prefill_repeats`).  More than 131072 tokens: the prune + two-pass route."""
+    global hd64_prefill_repeats
+    if k.shape != v.shape or k.dim() != 4 or k.shape[3] != 64 or k.dtype != torch.float16 or v.dtype != torch.float16 or not k.is_cuda:
+        raise RuntimeError("compress_raw_pair_hd64 expects two float16 [B, Hkv, L, 64] tensors of one shape on the GPU")
+    B, H, L, D = k.shape
+    if tokens <= 0 or tokens % 256 or tokens > L or not 0 <= kth_k <= 64 or not 0 <= kth_v <= 64:
+        raise RuntimeError("compress_raw_pair_hd64: tokens must be a positive multiple of 256 within the rows, kth within [0, 64]")
+    Bp, n, dev = B * H, tokens // 256, k.device
+    if tokens > HD64_MAX_RAW_TOKENS:
+        return (_compress(_prune_kth_hd64(k[:, :, :tokens], kth_k).reshape(Bp, -1, D), "key"),
+                _compress(_prune_kth_hd64(v[:, :, :tokens], kth_v).reshape(Bp, -1, D), "value"))
+    k = k if k.is_contiguous() and k.data_ptr() % 16 == 0 else k.contiguous().clone()   # (a transpose(1, 2) view of [B, L, H, 64])
+    v = v if v.is_contiguous() and v.data_ptr() % 16 == 0 else v.contiguous().clone()
+    Lb = _lib.load()
+    words = 1 + 2 * n * Bp   # status: [flag | K lengths [n][B'] | V lengths [n][B']]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        st = stream.cuda_stream
+        host = _offsets_mirror(dev, words - 1)[0]   # (pinned int64 [words], this thread's: a call has read it before it returns)
+
+        def launch(region_k: int, region_v: int):
+            (ok_, kb), (ov_, vb) = ExtentPool64.layout(Bp, region_k), ExtentPool64.layout(Bp, region_v)
+            buf = torch.empty((n * (kb + vb) + 2 * n * VIEW_BYTES + words * 8,), dtype=torch.uint8, device=dev)
+            tables = buf.data_ptr() + n * (kb + vb)
+            status = buf[n * (kb + vb) + 2 * n * VIEW_BYTES:].view(torch.int64)
+            status[0] = 0
+            views = []
+            for base, off, region in ((buf.data_ptr(), ok_, region_k), (buf.data_ptr() + n * kb, ov_, region_v)):
+                views.append(_lib.CacheView(base + off["bmp"], base + off["nz"], base + off["idx"], base + off["nz_offset"], 256, 257, region // 8))
+            err = Lb.mustafar_prefill_compress_hd(st, k.data_ptr(), v.data_ptr(), L * D, Bp, tokens, D, kth_k, kth_v, views[0], views[1], kb, vb,
+                                                  tables, tables + n * VIEW_BYTES, status.data_ptr() + 8, status.data_ptr() + 8 * (1 + n * Bp),
+                                                  region_k, region_v, status.data_ptr())
+            _lib.check(err, "mustafar_prefill_compress_hd")
+            host.copy_(status, non_blocking=True)   # the ONE copy + wait: flag and every chunk's lengths
+            stream.synchronize()
+            return buf, tables
+
+        buf, tables = launch(hd64_staging_region(kth_k), hd64_staging_region(kth_v))
+        if int(host[0]) & 1:   # a (head, chunk) outgrew its region: once more, at the measured maximum (the raw rows are still in place)
+            hd64_prefill_repeats += 1
+            lens = host[1:].view(2, n * Bp)
+            need_k, need_v = ((int(lens[i].max()) + 7) // 8 * 8 for i in range(2))
+            buf, tables = launch(max(need_k, hd64_staging_region(kth_k)), max(need_v, hd64_staging_region(kth_v)))
+            if int(host[0]) & 0xffffffff:
+                raise RuntimeError("compress_raw_pair_hd64: the repeat at the measured size overflowed: this is a bug")
+        lens = host[1:].view(2, n, Bp).sum(1)   # [side][head] halfs
+        out = []
+        for side in range(2):
+            offs = [0] + torch.cumsum(lens[side], 0).tolist()
+            if offs[-1] // 8 > 0xffffffff:
+                raise RuntimeError("compress_raw_pair_hd64: the packed stream exceeds what nz_offset (uint4 units, 32 bits) can address")
+            bitmaps = torch.empty((Bp, tokens), dtype=torch.int64, device=dev)
+            accum = torch.empty((Bp, tokens + 1), dtype=torch.int32, device=dev)
+            packed = torch.empty((offs[-1],), dtype=torch.float16, device=dev)
+            nz_offset = torch.tensor([o // 8 for o in offs[:-1]], dtype=torch.int32, device=dev)
+            room = packed if offs[-1] else torch.empty((8,), dtype=torch.float16, device=dev)   # (no stream at all: nothing is written)
+            dst = _lib.CacheView(bitmaps.data_ptr(), room.data_ptr(), accum.data_ptr(), nz_offset.data_ptr(), 0, 0, 0)
+            err = Lb.mustafar_cache_gather_hd(st, dst, None, 0, tables + side * n * VIEW_BYTES, n, Bp, D)
+            _lib.check(err, "mustafar_cache_gather_hd")
+            out.append([bitmaps, accum, FlatStreams(pieces_of(packed, offs), flat=packed), nz_offset])
+        del buf   # (stream-ordered: the gather launches are queued in front of any reuse)
+    return out[0], out[1]

@@ -28,6 +28,7 @@ from typing import List, Tuple
 import torch
 
 from . import _lib
+from .reflayout import FlatStreams, nz_offset_from_idxs
 
 
 class _Backing:
@@ -305,13 +306,8 @@ def convert_value_batched(inputs: torch.Tensor):
     return _convert(inputs, "value")
 
 
-# ---- head_dim 64: a prefill compressed from the RAW rows (MustafarConfig(hd64_raw_prefill=True)) ---------------------------------------------
-HD64_MAX_RAW_TOKENS = 512 * 256   # mustafar_prefill_compress_hd / mustafar_cache_gather_hd take at most 512 chunks
-hd64_prefill_repeats = 0          # compression launches repeated at the measured region size (rows with ties at the threshold)
-
-
 def hd64_staging_region(kth: int) -> int:
-    """Halfs the staging keeps for one (head, 256-token chunk).  Tie-free rows keep 64 - kth + 1 values each; a V tile is one row, a K
+    """(The head_dim-64 prefill from the raw rows, cache64.compress_raw_pair_hd64; pure arithmetic, kept importable from here.)  Halfs the staging keeps for one (head, 256-token chunk).  Tie-free rows keep 64 - kth + 1 values each; a V tile is one row, a K
     tile one channel of a 64-token block, and every tile is padded to 8 halfs: at most 7 more per tile, 256 tiles per chunk on
     either side.  kth = 0 (rows pruned by the caller: anything may be kept) or a bound above the dense rows: the dense rows."""
     full = 256 * 64
@@ -320,99 +316,8 @@ def hd64_staging_region(kth: int) -> int:
     return min(full, (256 * (64 - kth + 1) + 7 * 256 + 7) // 8 * 8)
 
 
-def _prune_kth_hd64(x: torch.Tensor, kth: int) -> torch.Tensor:
-    """prune_magnitude with the k-th-smallest index given (0: the rows are pruned already)."""
-    xc = x.contiguous()
-    if xc.data_ptr() % 16:
-        xc = xc.clone()
-    if kth <= 0:
-        return xc
-    out = torch.empty_like(xc)
-    with torch.cuda.device(x.device):
-        err = _lib.load().mustafar_prune_magnitude(_stream_ptr(x.device), xc.data_ptr(), out.data_ptr(), xc.numel() // 64, 64, kth)
-    _lib.check(err, "mustafar_prune_magnitude")
-    return out
-
-
-def _status_mirror(dev: torch.device, words: int) -> torch.Tensor:
-    """Pinned int64 [words] the status words are copied to: one per thread, device and size, reused from call to call (a call has read
-    it before it returns)."""
-    pool = _mirrors.__dict__.setdefault("status", {})
-    m = pool.get((dev.index, words))
-    if m is None:
-        m = pool[(dev.index, words)] = torch.empty((words,), dtype=torch.int64, pin_memory=True)
-    return m
-
-
-def compress_raw_pair_hd64(k: torch.Tensor, v: torch.Tensor, tokens: int, kth_k: int, kth_v: int):
-    """Raw K / V [B, Hkv, L, 64] fp16 -> the reference-layout caches `[bitmaps, idxs, FlatStreams, nz_offset]` of the first `tokens` rows
-    of every head (a multiple of 256): what `hook._compress(prune_magnitude(x[:, :, :tokens]).reshape(B', -1, 64), which)` returns, tensor
-    for tensor, without a pruned copy and with ONE read of the rows and ONE host wait:
-      1. mustafar_prefill_compress_hd: every 256-token chunk of every head becomes an extent of its own in a staging allocation;
-      2. one copy of the flag and the chunk lengths to pinned memory and one wait (the return type needs the sizes);
-      3. mustafar_cache_gather_hd per side: the chunks, offsets shifted, into the exact-size arrays.
-    A chunk whose rows tie at the threshold keeps more than the staging bound: flag bit 0, and the launch is repeated ONCE at the
-    measured maximum (counted in `hd64_prefill_repeats`).  More than 131072 tokens: the prune + two-pass route."""
-    global hd64_prefill_repeats
-    from .cache64 import ExtentPool64, VIEW_BYTES
-    from .hook import FlatStreams, _compress
-    if k.shape != v.shape or k.dim() != 4 or k.shape[3] != 64 or k.dtype != torch.float16 or v.dtype != torch.float16 or not k.is_cuda:
-        raise RuntimeError("compress_raw_pair_hd64 expects two float16 [B, Hkv, L, 64] tensors of one shape on the GPU")
-    B, H, L, D = k.shape
-    if tokens <= 0 or tokens % 256 or tokens > L or not 0 <= kth_k <= 64 or not 0 <= kth_v <= 64:
-        raise RuntimeError("compress_raw_pair_hd64: tokens must be a positive multiple of 256 within the rows, kth within [0, 64]")
-    Bp, n, dev = B * H, tokens // 256, k.device
-    if tokens > HD64_MAX_RAW_TOKENS:
-        return (_compress(_prune_kth_hd64(k[:, :, :tokens], kth_k).reshape(Bp, -1, D), "key"),
-                _compress(_prune_kth_hd64(v[:, :, :tokens], kth_v).reshape(Bp, -1, D), "value"))
-    k = k if k.is_contiguous() and k.data_ptr() % 16 == 0 else k.contiguous().clone()   # (a transpose(1, 2) view of [B, L, H, 64])
-    v = v if v.is_contiguous() and v.data_ptr() % 16 == 0 else v.contiguous().clone()
-    Lb = _lib.load()
-    words = 1 + 2 * n * Bp   # status: [flag | K lengths [n][B'] | V lengths [n][B']]
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        st = stream.cuda_stream
-        host = _status_mirror(dev, words)
-
-        def launch(region_k: int, region_v: int):
-            (ok_, kb), (ov_, vb) = ExtentPool64.layout(Bp, region_k), ExtentPool64.layout(Bp, region_v)
-            buf = torch.empty((n * (kb + vb) + 2 * n * VIEW_BYTES + words * 8,), dtype=torch.uint8, device=dev)
-            tables = buf.data_ptr() + n * (kb + vb)
-            status = buf[n * (kb + vb) + 2 * n * VIEW_BYTES:].view(torch.int64)
-            status[0] = 0
-            views = []
-            for base, off, region in ((buf.data_ptr(), ok_, region_k), (buf.data_ptr() + n * kb, ov_, region_v)):
-                views.append(_lib.CacheView(base + off["bmp"], base + off["nz"], base + off["idx"], base + off["nz_offset"], 256, 257, region // 8))
-            err = Lb.mustafar_prefill_compress_hd(st, k.data_ptr(), v.data_ptr(), L * D, Bp, tokens, D, kth_k, kth_v, views[0], views[1], kb, vb,
-                                                  tables, tables + n * VIEW_BYTES, status.data_ptr() + 8, status.data_ptr() + 8 * (1 + n * Bp),
-                                                  region_k, region_v, status.data_ptr())
-            _lib.check(err, "mustafar_prefill_compress_hd")
-            host.copy_(status, non_blocking=True)   # the ONE copy + wait: flag and every chunk's lengths
-            stream.synchronize()
-            return buf, tables
-
-        buf, tables = launch(hd64_staging_region(kth_k), hd64_staging_region(kth_v))
-        if int(host[0]) & 1:   # a (head, chunk) outgrew its region: once more, at the measured maximum (the raw rows are still in place)
-            hd64_prefill_repeats += 1
-            lens = host[1:].view(2, n * Bp)
-            need_k, need_v = ((int(lens[i].max()) + 7) // 8 * 8 for i in range(2))
-            buf, tables = launch(max(need_k, hd64_staging_region(kth_k)), max(need_v, hd64_staging_region(kth_v)))
-            if int(host[0]) & 0xffffffff:
-                raise RuntimeError("compress_raw_pair_hd64: the repeat at the measured size overflowed: this is a bug")
-        lens = host[1:].view(2, n, Bp).sum(1)   # [side][head] halfs
-        out = []
-        for side in range(2):
-            offs = [0] + torch.cumsum(lens[side], 0).tolist()
-            if offs[-1] // 8 > 0xffffffff:
-                raise RuntimeError("compress_raw_pair_hd64: the packed stream exceeds what nz_offset (uint4 units, 32 bits) can address")
-            bitmaps = torch.empty((Bp, tokens), dtype=torch.int64, device=dev)
-            accum = torch.empty((Bp, tokens + 1), dtype=torch.int32, device=dev)
-            packed = torch.empty((offs[-1],), dtype=torch.float16, device=dev)
-            nz_offset = torch.tensor([o // 8 for o in offs[:-1]], dtype=torch.int32, device=dev)
-            room = packed if offs[-1] else torch.empty((8,), dtype=torch.float16, device=dev)   # (no stream at all: nothing is written)
-            dst = _lib.CacheView(bitmaps.data_ptr(), room.data_ptr(), accum.data_ptr(), nz_offset.data_ptr(), 0, 0, 0)
-            err = Lb.mustafar_cache_gather_hd(st, dst, None, 0, tables + side * n * VIEW_BYTES, n, Bp, D)
-            _lib.check(err, "mustafar_cache_gather_hd")
-            out.append([bitmaps, accum, FlatStreams(pieces_of(packed, offs), flat=packed), nz_offset])
-        del buf   # (stream-ordered: the gather launches are queued in front of any reuse)
-    return out[0], out[1]
+def _compress(x: torch.Tensor, which: str):
+    """x: pruned [B', t, D] -> [bitmaps, idxs, FlatStreams, nz_offset] (model :328-337, :422-434)."""
+    conv = convert_key_batched if which == "key" else convert_value_batched
+    bmps, idxs, nzs = conv(x)
+    return [bmps, idxs, FlatStreams(nzs), nz_offset_from_idxs(idxs, x.shape[0])]

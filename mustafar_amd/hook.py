@@ -9,7 +9,9 @@ the Mustafar operators -- with the same cache tuple, the same trigger rule and t
                         dense window p.V, and every 256th step prune+compress the oldest 256 window tokens
 
 `past` is the reference's 6-tuple (k_compressed, k_local_window, v_compressed, v_local_window,
-compressed_length, kv_seq_len) (:445), k_compressed = [bitmaps, idxs, nzs(list per kv-head), nz_offset].
+compressed_length, kv_seq_len) (:445), k_compressed = [bitmaps, idxs, nzs(list per kv-head), nz_offset]; `Past` names its fields.
+The layers below: reflayout.py (the list's primitives and the protocol by which a cache of any kind arrives at a call), compression.py,
+cache.py / cache64.py; their names that callers import from here are re-exported.  partial.py is the one layer above.
 
 `api="reference"` issues exactly the reference's calls (query/probabilities zero-padded to 8 rows :273/:313,
 `torch.cat` of the per-head streams on every call :274/:314, 8-row outputs sliced to row 0 :275/:315).
@@ -21,17 +23,21 @@ key SpMV (+ window scores) -> softmax -> value SpMV (+ window p.V partials) -> s
 """
 from __future__ import annotations
 
-import ctypes
+import glob
+import importlib.util
 import math
+import os
 from dataclasses import dataclass
-from typing import List, NamedTuple, Optional, Tuple
+from typing import Any, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib, compression, mustafar_package
 from .cache import CompressedArena
-from .cache64 import ExtentCache64
+from .cache64 import ExtentCache64, compress_raw_pair_hd64
+from .compression import _compress                                                                          # noqa: F401  (re-exported)
+from .reflayout import FlatStreams, _flat_stream, append_compressed, as_cache, nz_offset_from_idxs         # noqa: F401  (re-exported)
 
 
 def _operator_module():
@@ -40,7 +46,6 @@ def _operator_module():
     ~5 us of host time per call) when it has been built, else the ctypes mirror (~12 us).  Same checks, same C-ABI calls."""
     global _OPERATORS
     if _OPERATORS is None:
-        import importlib.util, glob, os
         _OPERATORS = mustafar_package
         hits = glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin", "mustafar_package*.so"))
         if hits and os.environ.get("MUSTAFAR_OPERATORS", "compiled") != "ctypes":
@@ -82,7 +87,7 @@ class MustafarConfig:
     # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
     hd64_extents: bool = False
     # head_dim 64, api="fused", arena=False only: the prefill is compressed from the raw K / V rows in 256-token chunks and gathered into
-    # the reference-layout arrays (compression.compress_raw_pair_hd64: one read of the rows, one host wait) instead of prune + two
+    # the reference-layout arrays (cache64.compress_raw_pair_hd64: one read of the rows, one host wait) instead of prune + two
     # conversions.  The same tensors, bit for bit; off by default
     hd64_raw_prefill: bool = False
 
@@ -94,57 +99,6 @@ def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
         return hidden_states
     hidden_states = hidden_states[:, :, None, :, :].expand(batch, num_key_value_heads, n_rep, slen, head_dim)
     return hidden_states.reshape(batch, num_key_value_heads * n_rep, slen, head_dim)
-
-
-class FlatStreams(list):
-    """The reference's per-head list of packed-nz tensors.  `streams.flat` is the packed stream of all heads as ONE tensor --
-    `torch.cat(streams)`, what the model does on every decode step (:274/:314), which costs nothing when the elements are the
-    `StreamPiece`s that `convert_*_batched` returns (compression.py: the pieces of one buffer, in order, ARE that buffer)."""
-
-    def __init__(self, per_head: List[torch.Tensor], flat: Optional[torch.Tensor] = None):
-        super().__init__(per_head)
-        self._flat = flat
-
-    @property
-    def flat(self) -> Optional[torch.Tensor]:
-        if self._flat is None and len(self):
-            self._flat = torch.cat(self)
-        return self._flat
-
-
-def nz_offset_from_idxs(idxs: torch.Tensor, heads: int) -> torch.Tensor:
-    """model :329-331 / :423-425 without the per-head Python loop: nz_offset[i] = sum_{j<i} idxs[j][-1] // 4."""
-    last = idxs.view(heads, -1)[:, -1].to(torch.int64) // 4
-    off = torch.zeros(heads, dtype=torch.int32, device=idxs.device)
-    if heads > 1:
-        off[1:] = torch.cumsum(last, 0)[:-1].to(torch.int32)
-    return off
-
-
-def _compress(x: torch.Tensor, which: str):
-    """x: pruned [B', t, D] -> [bitmaps, idxs, FlatStreams, nz_offset] (model :328-337, :422-434)."""
-    conv = compression.convert_key_batched if which == "key" else compression.convert_value_batched
-    bmps, idxs, nzs = conv(x)
-    return [bmps, idxs, FlatStreams(nzs), nz_offset_from_idxs(idxs, x.shape[0])]
-
-
-def append_compressed(old: list, new: list, heads: int, old_tokens: int, new_tokens: int, head_dim: int) -> list:
-    """Cache append of model :339-368 (K) / :372-390 (V): shift the new offsets by each head's old total, splice
-    bitmaps/offsets per head, concatenate the streams per head, advance nz_offset.  Tensor ops only (the
-    reference builds `last_elements` through a Python list of device scalars, :341)."""
-    o_bmp, o_idx, o_nz, o_off = old
-    n_bmp, n_idx, n_nz, _ = new
-    tiles_per_token = head_dim // 64
-    n_last = n_idx.view(heads, -1)[:, -1].to(torch.int64) // 4                      # :341-342
-    off = o_off.clone()
-    if heads > 1:
-        off[1:] += torch.cumsum(n_last, 0)[:-1].to(torch.int32)                      # :343-344
-    base = o_idx.view(heads, -1)[:, -1:]                                             # :352-353
-    idx = torch.cat([o_idx.view(heads, -1)[:, :-1], n_idx.view(heads, -1) + base], dim=1).flatten()   # :356-360
-    bmp = torch.cat([o_bmp.view(heads, old_tokens * tiles_per_token),
-                     n_bmp.view(heads, new_tokens * tiles_per_token)], dim=1).flatten()               # :364
-    per_head = [torch.cat([o_nz[b], n_nz[b]], dim=0) for b in range(heads)]                           # :368
-    return [bmp, idx, FlatStreams(per_head), off]
 
 
 def mask_args(attention_mask: Optional[torch.Tensor], bsz: int, columns: int, dev, row_len: Optional[int] = None, exact: bool = False):
@@ -167,6 +121,17 @@ def mask_args(attention_mask: Optional[torch.Tensor], bsz: int, columns: int, de
     return attention_mask, (attention_mask.stride(0) if bsz > 1 else attention_mask.shape[3])
 
 
+class Past(NamedTuple):
+    """The reference's cache tuple (model :445) with names.  Still a tuple: it compares equal to the plain 6-tuple, unpacks, and indexes
+    by `[4]` and `[-1]`; every public method takes either and hands back a `Past`."""
+    k_cache: Any             # [bitmaps, idxs, nzs, nz_offset] | CompressedArena | ExtentCache64 | None (nothing compressed yet)
+    k_window: Any            # dense tensor [B, Hkv, w, D], or a `Window` (api="fused")
+    v_cache: Any
+    v_window: Any
+    compressed_length: int
+    kv_seq_len: int
+
+
 def _ld_scores(columns: int) -> int:
     """Row pitch of the score scratch for `columns` = compressed tokens + window capacity: rows on 64-byte lines of their own
     (one-pass form: mustafar_hip.h)."""
@@ -182,30 +147,14 @@ class DecodeOperands(NamedTuple):
     flags: int           # `flags` as in `tail`
 
 
-def _flat_stream(c):
-    """The packed stream of all heads of a reference-layout cache as one tensor: a FlatStreams' `.flat`, a plain tensor, or a plain
-    list of per-head tensors, concatenated here."""
-    nz = c[2]
-    return nz.flat if hasattr(nz, "flat") else (nz if isinstance(nz, torch.Tensor) else torch.cat(list(nz)))
-
-
-def _list_decode_args(k_c, v_c):
-    """How two reference-layout caches `[bitmaps, idxs, nzs, nz_offset]` arrive at a fused decode call: the eight array addresses
-    (bitmaps, stream, idxs, nz_offset of K, then of V) and the tensors to keep until the call is issued.  None (nothing compressed
-    yet) and empty tensors become null addresses."""
-    if k_c is None:
-        return (None,) * 8, ()
-    kz, vz = _flat_stream(k_c), _flat_stream(v_c)
-    p = lambda t: t.data_ptr() if t is not None and t.numel() else None
-    return (p(k_c[0]), p(kz), p(k_c[1]), p(k_c[3]), p(v_c[0]), p(vz), p(v_c[1]), p(v_c[3])), (kz, vz)
-
-
 def _call_decode(k_c, v_c, T: int, ops: DecodeOperands, D: int, t_device: Optional[torch.Tensor] = None,
                  lse: Optional[torch.Tensor] = None) -> None:
     """Issue ONE fused decode call: the only place that chooses among the seven entry points of the C ABI.  k_c / v_c: the two caches
     (None: nothing compressed yet); T: the compressed tokens the launch is sized for (what `ops` was built with); t_device: the
     tokens in use as a device int, or None; lse: the fp32 tensor the row kernel fills, or None.  Each cache kind says how it
-    arrives (`decode_args` of the two cache classes, `_list_decode_args`): eight arrays, or base views + T_base + device tables.
+    arrives (`decode_args`: reflayout.ListCache for a list or None, CompressedArena, ExtentCache64): eight arrays, or base views +
+    T_base + device tables.  The tables are asked for when the launch reads beyond the base tokens; a kind whose `lse_reads_tables`
+    is set (ExtentCache64) also whenever there is an LSE.
 
         cache                            no LSE                                              LSE
         list / None                      mustafar_decode_attention (D 128) / _hd (D 64)      _lse_hd
@@ -216,13 +165,9 @@ def _call_decode(k_c, v_c, T: int, ops: DecodeOperands, D: int, t_device: Option
 
     Whether the launch form asked for can read a grown arena at all is the caller's business (`_decode_fused`)."""
     L = _lib.load()
-    extent64 = isinstance(k_c, ExtentCache64)
-    if isinstance(k_c, CompressedArena):
-        cache, keep = k_c.decode_args(v_c, tables=T > k_c.tokens)
-    elif extent64:   # (with an LSE and T == T_base the extents form reads the base alone, as the plain launch does)
-        cache, keep = k_c.decode_args(v_c, tables=lse is not None or bool(k_c.extents) or t_device is not None)
-    else:
-        cache, keep = _list_decode_args(k_c, v_c)
+    k, v = as_cache(k_c, T), as_cache(v_c, T)
+    # (with an LSE and T == T_base the extents form reads the base alone, as the plain launch does)
+    cache, keep = k.decode_args(v, tables=T > k.tokens or (lse is not None and k.lse_reads_tables))
     arrays = len(cache) == 8
     td = t_device.data_ptr() if t_device is not None else None
     dev = ops.out.device
@@ -236,7 +181,7 @@ def _call_decode(k_c, v_c, T: int, ops: DecodeOperands, D: int, t_device: Option
             err = L.mustafar_decode_attention(st, *cache, *ops.tail)
         elif lse is not None:
             err = L.mustafar_decode_attention_extents_lse_hd(st, *cache, *ops.tail, td, D, lse.data_ptr())
-        elif extent64:
+        elif D == 64:
             err = L.mustafar_decode_attention_extents_hd(st, *cache, *ops.tail, td, D)
         elif cache[3] is None:   # an arena that is its base alone: the two views
             err = L.mustafar_decode_attention_view(st, cache[0], cache[1], *ops.tail)
@@ -244,6 +189,30 @@ def _call_decode(k_c, v_c, T: int, ops: DecodeOperands, D: int, t_device: Option
             err = L.mustafar_decode_attention_extents(st, *cache, *ops.tail, td)
     _lib.check(err, "mustafar_decode_attention")
     del keep   # (alive until here: the call has been issued)
+
+
+def merge_states(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor]):
+    """Merge partial attention states over disjoint token sets: outs[i] fp16 [bsz, H, 1, D] (normalised), lses[i] fp32 [bsz, H].
+    Returns (out fp16 [bsz, H, 1, D], lse fp32 [bsz, H]) of the attention over all of them; one launch behind the stacking."""
+    n = len(outs)
+    if n < 1 or n > 64 or len(lses) != n:
+        raise ValueError(f"merge_states: 1 to 64 parts with one LSE each (got {n} outputs, {len(lses)} LSEs)")
+    bsz, H, _, D = outs[0].shape
+    if D not in (64, 128):
+        raise ValueError(f"merge_states: head_dim 64 or 128 (got {D})")
+    for o, l in zip(outs, lses):
+        if o.shape != outs[0].shape or o.dtype != torch.float16 or tuple(l.shape) != (bsz, H) or l.dtype != torch.float32:
+            raise ValueError("merge_states: parts are fp16 [bsz, H, 1, D] outputs with fp32 [bsz, H] LSEs of one shape")
+    dev = outs[0].device
+    o_all = torch.stack([o.reshape(bsz * H, D) for o in outs])       # [n, BH, D]
+    l_all = torch.stack([l.reshape(bsz * H) for l in lses])          # [n, BH]
+    out = torch.empty((bsz, H, 1, D), dtype=torch.float16, device=dev)
+    lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        err = _lib.load().mustafar_merge_attention_states(torch.cuda.current_stream(dev).cuda_stream, o_all.data_ptr(), bsz * H * D,
+                                                          l_all.data_ptr(), bsz * H, n, bsz * H, D, out.data_ptr(), lse.data_ptr())
+    _lib.check(err, "mustafar_merge_attention_states")
+    return out, lse
 
 
 class Window:
@@ -368,7 +337,7 @@ class MustafarAttention:
         # :416 computes ((L - R)//256)*256, which is -256 for L < R; clamp at 0.
         compressed_length = max(0, ((kv_seq_len - self.cfg.residual_length) // 256) * 256)
         if compressed_length == 0:
-            return (None, key_states, None, value_states, 0, kv_seq_len)
+            return Past(None, key_states, None, value_states, 0, kv_seq_len)
         arena = self.cfg.arena and self.cfg.api == "fused"
         if arena or self.cfg.hd64_raw_prefill:
             # In the model K and V arrive as transpose(1, 2) views of [B, L, H, D] projections (model :224-226; RoPE keeps the
@@ -380,7 +349,7 @@ class MustafarAttention:
                 k_compressed, v_compressed = CompressedArena.from_raw_pair(ks, vs, compressed_length, *self._kth(D), None, self._slack())
             else:
                 # head_dim 64 from the raw rows: one chunked compression launch, one host wait, one gather per side
-                k_compressed, v_compressed = compression.compress_raw_pair_hd64(ks, vs, compressed_length, *self._kth(D))
+                k_compressed, v_compressed = compress_raw_pair_hd64(ks, vs, compressed_length, *self._kth(D))
             del ks, vs
         else:
             k_pruned = self.dh_prune_key(key_states[:, :, :compressed_length, :])                     # :419
@@ -389,7 +358,7 @@ class MustafarAttention:
             v_compressed = _compress(v_pruned.reshape(total_batch_kv, -1, D), "value")                # :430-434
         k_local_window = key_states[:, :, compressed_length:, :].clone().contiguous()                 # :427
         v_local_window = value_states[:, :, compressed_length:, :].clone().contiguous()               # :435
-        return (k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, kv_seq_len)   # :445
+        return Past(k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, kv_seq_len)   # :445
 
     def prefill(self, query_states, key_states, value_states):
         """q [B,Hq,L,D], k/v [B,Hkv,L,D] fp16 -> (attn_output [B,Hq,L,D], past)."""
@@ -412,10 +381,10 @@ class MustafarAttention:
             v_c = CompressedArena.from_reference(v_c, "value", C, None, self._slack())
         if self.cfg.extents and isinstance(k_c, CompressedArena):
             k_c.ext_table, v_c.ext_table   # (exist before any graph that names them is captured: see decode_fused)
-        if isinstance(k_w, Window):
-            return (k_c, k_w, v_c, v_w, C, L)
-        cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
-        return (k_c, Window(k_w, cap), v_c, Window(v_w, cap), C, L)
+        if not isinstance(k_w, Window):
+            cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
+            k_w, v_w = Window(k_w, cap), Window(v_w, cap)
+        return Past(k_c, k_w, v_c, v_w, C, L)
 
     @staticmethod
     def advance(past, n: int):
@@ -423,7 +392,7 @@ class MustafarAttention:
         k_c, k_w, v_c, v_w, C, L = past
         k_w.len += n
         v_w.len += n
-        return (k_c, k_w, v_c, v_w, C, L + n)
+        return Past(k_c, k_w, v_c, v_w, C, L + n)
 
     def _scratch(self, device, BH, ld, ws_bytes):
         """Score scratch and slab workspace of the fused entry point, one pair per (device, stream): calls on different
@@ -538,8 +507,8 @@ class MustafarAttention:
         cfg = self.cfg
         bsz, _, q_len, D = query_states.shape
         assert q_len == 1 and ((D == 128 and not cfg.hd64_extents) or (D == 64 and self.head_dim == 64))
-        Bkv = bsz * self.num_key_value_heads
-        k_c, k_w, v_c, v_w, C, _ = self.to_fused(past)
+        past = self.to_fused(past)
+        k_c, k_w, v_c, v_w, C, _ = past
         use_arena = isinstance(k_c, CompressedArena)
         T = C   # the compressed tokens the launch is sized for
         if t_device is not None:   # the launch is sized for the capacity; the kernels read the tokens in use from `t_device`
@@ -553,7 +522,7 @@ class MustafarAttention:
             elif t_capacity is None or t_capacity < C or (t_capacity - C) % 256 or not use_arena or t_capacity <= k_c.tokens:
                 raise ValueError("decode_fused: t_device needs an arena cache and t_capacity = compressed length + a multiple of 256, beyond the base tokens")
             T = t_capacity
-        kv_seq_len = past[-1] + 1
+        kv_seq_len = past.kv_seq_len + 1
         ops, w_len = self._step_operands(query_states, key_states, value_states, k_w, v_w, T, kv_seq_len, step_counter, attention_mask)
         if use_arena:
             if cfg.extents and (k_c._ext_table is None or v_c._ext_table is None):
@@ -573,18 +542,19 @@ class MustafarAttention:
                                        "(MustafarConfig(extents=False), or consolidate() the arenas first)")
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()   # (T == their base tokens now: the view form)
                 k_c.ext_table, v_c.ext_table
+                past = past._replace(k_cache=k_c, v_cache=v_c)
         _call_decode(k_c, v_c, T, ops, D, t_device, lse)
         out = ops.out
         if step_counter is not None:
-            return out, (k_c, k_w, v_c, v_w, C, kv_seq_len - 1)   # lengths advance with the device counter
+            return out, past   # lengths advance with the device counter
         k_w.len = v_w.len = w_len
-        return out, self._close_step((k_c, k_w, v_c, v_w, C, kv_seq_len), defer_trigger)
+        return out, self._close_step(Past(k_c, k_w, v_c, v_w, C, kv_seq_len), defer_trigger)
 
     def _close_step(self, new, defer_trigger: bool):
         """The tail of a fused step whose rows are appended and counted in `new`: the 256-token trigger (model :324-398) when it is due,
         or nothing with `defer_trigger` (run_triggers() then).  Returns the past to hand back."""
         cfg = self.cfg
-        k_c, k_w, v_c, v_w, C, kv_seq_len = new
+        k_c, k_w, v_c, v_w, C = new[:5]
         use_arena = isinstance(k_c, CompressedArena)
         if defer_trigger:
             # run_triggers() works on arena and extent caches (a first trigger, C == 0, makes an arena when cfg.arena says so): anything
@@ -600,7 +570,7 @@ class MustafarAttention:
         D = k_w.buf.shape[3]
         if use_arena or (cfg.arena and C == 0):
             # prune (:325-326) + compress + append (:328-390) of the raw window rows in one launch
-            return self._trigger_one(*new, *self._kth(D))
+            return self._trigger_one(new, *self._kth(D))
         Bkv = k_w.buf.shape[0] * k_w.buf.shape[1]
         k_new, v_new = self._compress_front(k_w.buf, v_w.buf)
         if C == 0:
@@ -610,12 +580,12 @@ class MustafarAttention:
             v_c = append_compressed(v_c, v_new, Bkv, C, 256, D)
         k_w.drop_front(256)                                                                             # :392-393
         v_w.drop_front(256)
-        return (k_c, k_w, v_c, v_w, C + 256, kv_seq_len)
+        return new._replace(k_cache=k_c, v_cache=v_c, compressed_length=C + 256)
 
     # ---- several query tokens per call (multi_query.hip) ------------------------------------------------------------
     def _fits_before_trigger(self, past, n_q: int) -> int:
         """The largest n <= n_q such that no row but the last of an n-token call reaches a trigger point (`trigger_due`)."""
-        k_w, C, L = past[1], past[4], past[5]
+        _, k_w, _, _, C, L = past
         w_len = k_w.len if isinstance(k_w, Window) else k_w.shape[2]
         for j in range(n_q - 1):
             if (L + j + 1 - self.cfg.residual_length - C) % 256 == 0 and w_len + j + 1 >= 256:
@@ -663,7 +633,8 @@ class MustafarAttention:
 
     def _decode_multi_call(self, q, k_rows, v_rows, past):
         """One mustafar_decode_multi_query call: at most 64 // groups tokens, appended to the windows and counted in the returned past."""
-        k_c, k_w, v_c, v_w, C, kv_len = past
+        past = Past(*past)
+        k_c, k_w, v_c, v_w, C = past[:5]
         bsz, H, n, D = q.shape
         Bkv, groups, dev = bsz * self.num_key_value_heads, self.num_key_value_groups, q.device
         w_len = k_w.len + n
@@ -673,15 +644,8 @@ class MustafarAttention:
             raise RuntimeError("key/value windows must have the same length and capacity")
         q = q.contiguous()
         kn, vn = k_rows.contiguous(), v_rows.contiguous()
-        if isinstance(k_c, (CompressedArena, ExtentCache64)):   # (an arena is poll()ed by decode_args)
-            tables = C > k_c.tokens or isinstance(k_c, ExtentCache64)
-            (kv, vv, t_base, kt, vt), keep = k_c.decode_args(v_c, tables=tables)
-        elif k_c is None:
-            kv, vv, t_base, kt, vt, keep = None, None, 0, None, None, ()
-        else:
-            kz, vz = _flat_stream(k_c), _flat_stream(v_c)
-            views = [_lib.CacheView(c[0].data_ptr(), z.data_ptr(), c[1].data_ptr(), c[3].data_ptr(), 0, 0, 0) for c, z in ((k_c, kz), (v_c, vz))]
-            kv, vv, t_base, kt, vt, keep = ctypes.byref(views[0]), ctypes.byref(views[1]), C, None, None, (kz, vz, views)
+        k = as_cache(k_c, C)   # (an arena is poll()ed by view_args; an ExtentCache64 always names its tables here)
+        (kv, vv, t_base, kt, vt), keep = k.view_args(as_cache(v_c, C), tables=C > k.tokens or k.lse_reads_tables)
         L = _lib.load()
         ws_bytes = L.mustafar_decode_multi_query_workspace_bytes(C, k_w.cap, Bkv, groups, n, D)
         if ws_bytes <= 0:
@@ -697,57 +661,81 @@ class MustafarAttention:
         _lib.check(err, "mustafar_decode_multi_query")
         del keep   # (alive until here: the call has been issued)
         k_w.len = v_w.len = w_len
-        return out, lse, (k_c, k_w, v_c, v_w, C, kv_len + n)
+        return out, lse, past._replace(kv_seq_len=past.kv_seq_len + n)
 
     def accept(self, past, rejected: int = 0, defer_trigger: bool = False):
         """Close a decode_multi call: drop the `rejected` newest rows (0 <= rejected < the rows the window holds) -- only the host lengths
         change, the rows stay in the buffer and the next append overwrites them -- then run the 256-token trigger exactly as a decode_fused
         step does when it is due.  `defer_trigger`: return with the trigger not run, for run_triggers() over all layers."""
-        k_c, k_w, v_c, v_w, C, kv_len = past
+        past = Past(*past)
+        k_w, v_w = past.k_window, past.v_window
         if not isinstance(k_w, Window) or not isinstance(v_w, Window):
             raise ValueError("accept() closes a decode_multi call: the past it returned (windows in appendable buffers)")
         if not 0 <= rejected < min(k_w.len, v_w.len):
             raise ValueError(f"accept: rejected must be in [0, {min(k_w.len, v_w.len)}) -- the window holds {k_w.len} rows (got {rejected})")
         k_w.len -= rejected
         v_w.len -= rejected
-        return self._close_step((k_c, k_w, v_c, v_w, C, kv_len - rejected), defer_trigger)
+        return self._close_step(past._replace(kv_seq_len=past.kv_seq_len - rejected), defer_trigger)
 
     def decode_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None):
         """One decode step over frozen compressed segments + the live cache: `frozen` is a list of `(k_cache, v_cache, tokens)` that
         precede the live cache in sequence order (partial.decode_segment says what a segment may be), and / or of
-        `partial.SharedSegment`s -- one copy of kv_heads heads that every sequence of the batch reads (no mask then).  One window-less call per
-        segment, one decode_fused(return_lse=True) call on `past`, one merge (partial.merge_states).  `attention_mask`: additive fp16
+        `partial.SharedSegment`s -- one copy of kv_heads heads that every sequence of the batch reads (no mask then): anything that is not
+        a tuple is taken for one, and asked for its `tokens` and to `decode(attn, q)`.  One window-less call per
+        segment, one decode_fused(return_lse=True) call on `past`, one merge (merge_states).  `attention_mask`: additive fp16
         [bsz, 1, 1, frozen tokens + kv_seq_len]; every call reads its own columns (the pointer moves, rows need no alignment).
         Returns (out, past) with the contract of decode(); the 256-token trigger runs on the live cache only."""
-        from . import partial
         if self.cfg.api != "fused":
             raise ValueError("decode_split needs MustafarConfig(api='fused')")
         outs, lses, col = [], [], 0
-        shared = [isinstance(f, partial.SharedSegment) for f in frozen]
+        shared = [not isinstance(f, (tuple, list)) for f in frozen]
         if any(shared) and attention_mask is not None:
             raise ValueError("decode_split: a SharedSegment in `frozen` takes no attention mask (left padding and a shared prefix do not "
                              "coexist); pass attention_mask=None")
-        total = sum(f.tokens if sh else int(f[2]) for f, sh in zip(frozen, shared)) + past[-1] + 1
+        total = sum(f.tokens if sh else int(f[2]) for f, sh in zip(frozen, shared)) + Past(*past).kv_seq_len + 1
         if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[3] != total):
             raise ValueError(f"Attention mask should be of size {(query_states.shape[0], 1, 1, total)}, but is {tuple(attention_mask.size())}")
         for f, sh in zip(frozen, shared):
             if sh:   # one copy for the whole batch: mustafar_decode_shared_segment
-                o, l = partial.decode_segment(self, query_states, f)
-                outs.append(o)
-                lses.append(l)
-                continue
-            k_cache, v_cache, tokens = f
-            m = attention_mask[..., col:col + tokens] if attention_mask is not None else None
-            o, l = partial.decode_segment(self, query_states, k_cache, v_cache, tokens, m)
+                o, l = f.decode(self, query_states)
+            else:
+                k_cache, v_cache, tokens = f
+                m = attention_mask[..., col:col + tokens] if attention_mask is not None else None
+                o, l = self.decode_segment(query_states, k_cache, v_cache, tokens, m)
+                col += tokens
             outs.append(o)
             lses.append(l)
-            col += tokens
         m = attention_mask[..., col:] if attention_mask is not None else None
         o, l, new = self.decode_fused(query_states, key_states, value_states, past, attention_mask=m, return_lse=True)
         outs.append(o)
         lses.append(l)
-        out, _ = partial.merge_states(outs, lses)
+        out, _ = merge_states(outs, lses)
         return out, new
+
+    def _segment_query(self, query_states) -> None:
+        bsz, H, q_len, D = query_states.shape
+        if q_len != 1 or H != self.num_heads or D != self.head_dim:
+            raise ValueError(f"decode_segment: query of shape {tuple(query_states.shape)} for {self.num_heads} heads of {self.head_dim}")
+
+    def decode_segment(self, query_states, k_cache, v_cache, tokens, attention_mask=None):
+        """The window-less call of partial.decode_segment over one per-sequence segment (documented there)."""
+        self._segment_query(query_states)
+        bsz, H, _, D = query_states.shape
+        if v_cache is None or tokens is None:
+            raise ValueError("decode_segment: a per-sequence segment is (k_cache, v_cache, tokens)")
+        if tokens <= 0 or tokens % 64:
+            raise ValueError(f"decode_segment: a segment holds a positive multiple of 64 tokens (got {tokens})")
+        if D == 128:   # the LSE comes from the one-pass forms (mustafar_hip.h)
+            self._lse_served(tokens)
+        k, v = as_cache(k_cache, tokens), as_cache(v_cache, tokens)
+        if type(k) is not type(v) or k.total_tokens != tokens or v.total_tokens != tokens:
+            raise ValueError(f"decode_segment: the caches hold {k.total_tokens} / {v.total_tokens} tokens, not {tokens}")
+        dev = query_states.device
+        # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
+        ops = self._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
+        lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
+        _call_decode(k, v, tokens, ops, D, None, lse)
+        return ops.out, lse
 
     # ---- head_dim 64 over a cache that grows by extents (MustafarConfig(hd64_extents=True); cache64.py) ---------------------------------
     def _run_triggers_ext64(self, pasts):
@@ -755,50 +743,49 @@ class MustafarAttention:
         reference's way (prune, two-pass conversion: the base is reference-layout arrays); every other layer's 256 rows become an
         extent, all layers in one batched call (ExtentCache64.append_extents).  A full table is consolidated first."""
         kth_k, kth_v = self._kth(self.head_dim)
-        out = list(pasts)
+        out = [Past(*p) for p in pasts]
         groups = {}
-        for i, p in enumerate(pasts):
+        for i, p in enumerate(out):
             if not self.trigger_due(p):
                 continue
-            k_c, k_w, v_c, v_w, C, L = p
+            k_c, k_w, v_c, v_w = p[:4]
             Bkv = k_w.buf.shape[0] * k_w.buf.shape[1]
-            if C == 0:
+            if p.compressed_length == 0:
                 k_new, v_new = self._compress_front(k_w.buf, v_w.buf)
                 k_c, v_c = self.EXTENT_CACHE_64(k_new, "key", Bkv, 256), self.EXTENT_CACHE_64(v_new, "value", Bkv, 256)
                 k_w.drop_front(256)
                 v_w.drop_front(256)
-                out[i] = (k_c, k_w, v_c, v_w, 256, L)
+                out[i] = p._replace(k_cache=k_c, v_cache=v_c, compressed_length=256)
                 continue
             if len(k_c.extents) >= k_c.MAX_EXTENTS:   # table full: one copy of the cache (new addresses), then extents again
-                k_c, v_c = k_c.consolidate(), v_c.consolidate()
-                out[i] = (k_c, k_w, v_c, v_w, C, L)
+                out[i] = p._replace(k_cache=k_c.consolidate(), v_cache=v_c.consolidate())
             groups.setdefault((k_w.len, tuple(k_w.buf.shape)), []).append(i)
         for (wl, _), idxs in groups.items():   # (one group in a model: every layer's window has the same shape and length)
-            ExtentCache64.append_extents([(out[i][0], out[i][2]) for i in idxs], [(out[i][1].buf, out[i][3].buf) for i in idxs],
-                                         kth_k, kth_v, wl)
+            ExtentCache64.append_extents([(out[i].k_cache, out[i].v_cache) for i in idxs],
+                                         [(out[i].k_window.buf, out[i].v_window.buf) for i in idxs], kth_k, kth_v, wl)
             for i in idxs:
-                k_c, k_w, v_c, v_w, C, L = out[i]
-                k_w.len = v_w.len = wl - 256
-                out[i] = (k_c, k_w, v_c, v_w, C + 256, L)
+                out[i].k_window.len = out[i].v_window.len = wl - 256
+                out[i] = out[i]._replace(compressed_length=out[i].compressed_length + 256)
         return out
 
     # ---- the 256-token trigger of all layers at once (round 4) ----------------------------------------------------------------------
     def trigger_due(self, past) -> bool:
         """The step that produced `past` (its kv_seq_len already counted) reached the trigger of model :324."""
-        k_c, k_w, v_c, v_w, C, L = past
+        _, k_w, _, _, C, L = past
         return isinstance(k_w, Window) and (L - self.cfg.residual_length - C) % 256 == 0 and k_w.len >= 256
 
     def _batched_ok(self, past) -> bool:
-        k_c, k_w, v_c, v_w, C, L = past
+        k_c, C = past.k_cache, past.compressed_length
         return self.cfg.extents and isinstance(k_c, CompressedArena) and C > 0 and k_c.tokens % 256 == 0 and \
-            len(k_c.extents) < k_c.MAX_EXTENTS and self._reads_extents(C + 256 + k_w.cap)
+            len(k_c.extents) < k_c.MAX_EXTENTS and self._reads_extents(C + 256 + past.k_window.cap)
 
     def prepare_triggers(self, pasts):
         """Allocate and initialise the storage of the coming trigger of every layer ahead of it (one allocation, three launches):
         run_triggers() then allocates nothing.  Returns the pool to hand to run_triggers (None where the batched form does not apply)."""
+        pasts = [Past(*p) for p in pasts]
         if not pasts or not all(self._batched_ok(p) for p in pasts):
             return None
-        return CompressedArena.prepare_extents([(p[0], p[2]) for p in pasts], *self._kth(self.head_dim))
+        return CompressedArena.prepare_extents([(p.k_cache, p.v_cache) for p in pasts], *self._kth(self.head_dim))
 
     def run_triggers(self, pasts, pool=None):
         """The trigger (model :324-398) of every layer whose last step reached it (decode_fused(defer_trigger=True), or a replayed
@@ -809,34 +796,33 @@ class MustafarAttention:
         if cfg.hd64_extents:
             return self._run_triggers_ext64(pasts)
         kth_k, kth_v = self._kth(self.head_dim)
-        out = list(pasts)
-        due = [i for i, p in enumerate(pasts) if self.trigger_due(p)]
+        out = [Past(*p) for p in pasts]
+        due = [i for i, p in enumerate(out) if self.trigger_due(p)]
         if not due:
             return out
         for i in due:
-            if not (isinstance(pasts[i][0], CompressedArena) or (cfg.arena and pasts[i][4] == 0)):
+            if not (isinstance(out[i].k_cache, CompressedArena) or (cfg.arena and out[i].compressed_length == 0)):
                 raise RuntimeError("run_triggers works on arena caches (MustafarConfig(arena=True)); a tuple cache runs its trigger inside decode()")
-        batch = [i for i in due if self._batched_ok(pasts[i])]
-        wl = {pasts[i][1].len for i in batch}
-        if batch and len(wl) == 1 and len({pasts[i][1].buf.shape for i in batch}) == 1:
-            CompressedArena.append_extent_pairs([(pasts[i][0], pasts[i][2]) for i in batch], [(pasts[i][1].buf, pasts[i][3].buf) for i in batch],
-                                                kth_k, kth_v, wl.pop(), pool if len(batch) == len(pasts) else None)
+        batch = [i for i in due if self._batched_ok(out[i])]
+        wl = {out[i].k_window.len for i in batch}
+        if batch and len(wl) == 1 and len({out[i].k_window.buf.shape for i in batch}) == 1:
+            CompressedArena.append_extent_pairs([(out[i].k_cache, out[i].v_cache) for i in batch],
+                                                [(out[i].k_window.buf, out[i].v_window.buf) for i in batch],
+                                                kth_k, kth_v, wl.pop(), pool if len(batch) == len(out) else None)
             for i in batch:
-                k_c, k_w, v_c, v_w, C, L = pasts[i]
-                k_w.len = v_w.len = k_w.len - 256
-                out[i] = (k_c, k_w, v_c, v_w, C + 256, L)
+                out[i].k_window.len = out[i].v_window.len = out[i].k_window.len - 256
+                out[i] = out[i]._replace(compressed_length=out[i].compressed_length + 256)
         else:
             batch = []
         for i in due:
-            if i in batch:
-                continue
-            k_c, k_w, v_c, v_w, C, L = pasts[i]
-            out[i] = self._trigger_one(k_c, k_w, v_c, v_w, C, L, kth_k, kth_v)
+            if i not in batch:
+                out[i] = self._trigger_one(out[i], kth_k, kth_v)
         return out
 
-    def _trigger_one(self, k_c, k_w, v_c, v_w, C, L, kth_k, kth_v):
+    def _trigger_one(self, past, kth_k, kth_v):
         """One layer's trigger over an arena cache (the body decode_fused runs when it is not deferred)."""
         cfg = self.cfg
+        k_c, k_w, v_c, v_w, C = past[:5]
         if C == 0:
             k_c, v_c = CompressedArena.from_raw_pair(k_w.buf, v_w.buf, 256, kth_k, kth_v, None, self._slack())
             if cfg.extents:
@@ -851,7 +837,7 @@ class MustafarAttention:
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()
             CompressedArena.append_window_pair(k_c, v_c, k_w.buf, v_w.buf, 256, kth_k, kth_v)
         Window.drop_front_pair(k_w, v_w, 256)                                                   # :392-393, in place
-        return (k_c, k_w, v_c, v_w, C + 256, L)
+        return past._replace(k_cache=k_c, v_cache=v_c, compressed_length=C + 256)
 
     # ---- decode (model :256-400) -----------------------------------------------------------------------------
     def decode(self, query_states, key_states, value_states, past, attention_mask=None):
@@ -859,16 +845,17 @@ class MustafarAttention:
         cfg = self.cfg
         if cfg.api == "fused":
             return self.decode_fused(query_states, key_states, value_states, past, attention_mask=attention_mask)
-        if isinstance(past[1], Window):   # a fused cache handed to the unfused path
-            past = (past[0], past[1].view(), past[2], past[3].view(), past[4], past[5])
-        if isinstance(past[0], (CompressedArena, ExtentCache64)):
-            past = (past[0].to_reference(), past[1], past[2].to_reference(), past[3], past[4], past[5])
+        past = Past(*past)
+        if isinstance(past.k_window, Window):   # a fused cache handed to the unfused path
+            past = past._replace(k_window=past.k_window.view(), v_window=past.v_window.view())
+        if hasattr(past.k_cache, "to_reference"):   # an arena or an extent cache
+            past = past._replace(k_cache=past.k_cache.to_reference(), v_cache=past.v_cache.to_reference())
         bsz, _, q_len, D = query_states.shape
         total_batch_size = bsz * self.num_heads
         total_batch_kv = bsz * self.num_key_value_heads
         groups = self.num_key_value_groups
         k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, _ = past
-        kv_seq_len = past[-1] + 1                                                                      # :251
+        kv_seq_len = past.kv_seq_len + 1                                                               # :251
         reference_api = cfg.api == "reference"
 
         k_local_window = torch.cat([k_local_window, key_states], dim=2)                                # :270
@@ -930,5 +917,4 @@ class MustafarAttention:
             v_local_window = v_local_window[:, :, 256:, :].clone().contiguous()                        # :393
             compressed_length = compressed_length + 256                                                # :398
 
-        past = (k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, kv_seq_len)
-        return attn_output, past
+        return attn_output, Past(k_compressed, k_local_window, v_compressed, v_local_window, compressed_length, kv_seq_len)

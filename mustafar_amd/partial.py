@@ -5,25 +5,25 @@ such states over disjoint token sets combine exactly into the attention over the
 
     M = max_i lse_i,  w_i = exp(lse_i - M),  out = sum_i w_i out_i / sum_i w_i,  lse = M + log(sum_i w_i)
 
-`decode_segment` reads a frozen, already compressed segment -- a long document, an earlier turn -- that has no dense window at all;
-`merge_states` is one launch of `mustafar_merge_attention_states`.  A `SharedSegment` is such a segment held ONCE, `kv_heads` heads, for
+`decode_segment` reads a frozen, already compressed segment -- a long document, an earlier turn -- that has no dense window at all
+(per sequence: `MustafarAttention.decode_segment`, through hook._call_decode); `merge_states` is one launch of
+`mustafar_merge_attention_states` (hook.py holds it, below `decode_split`; re-exported here).  A `SharedSegment` is such a segment held ONCE, `kv_heads` heads, for
 every sequence of the batch (a system prompt, a document several requests ask about, n samples of one prompt): `decode_segment` reads
 it through `mustafar_decode_shared_segment`, which expands each block once and serves all rows of a kv head on the matrix pipe
 (DESIGN.md 4.10).  `MustafarAttention.decode_split` strings them together with the
-live cache.  No CPU fallback: both are calls into libmustafar_hip.so.
+live cache.  No CPU fallback: both are calls into libmustafar_hip.so.  This is the top layer: it imports hook.py, nothing imports it.
 """
 from __future__ import annotations
 
-import ctypes
 import math
-from typing import List, Optional, Sequence
+from typing import Optional
 
 import torch
 
 from . import _lib
-from .cache import CompressedArena
-from .cache64 import ExtentCache64
-from .hook import _call_decode, _compress, _flat_stream, mask_args
+from .compression import _compress
+from .hook import merge_states   # noqa: F401  (re-exported: `partial.merge_states`)
+from .reflayout import ListCache
 
 
 class SharedSegment:
@@ -39,10 +39,8 @@ class SharedSegment:
         if tokens <= 0 or tokens % 64:
             raise ValueError(f"SharedSegment: a segment holds a positive multiple of 64 tokens (got {tokens})")
         self.tokens = int(tokens)
-        self._keep = {}
-        for c, name in ((k_cache, "k_cache"), (v_cache, "v_cache")):
-            self._view(c, name)
-        heads = [self._heads(c) for c in (k_cache, v_cache)]
+        self._k, self._v = (self._checked(c, name) for c, name in ((k_cache, "k_cache"), (v_cache, "v_cache")))
+        heads = [self._k.heads, self._v.heads]
         if heads[0] != heads[1] or (kv_heads is not None and heads[0] != kv_heads):
             raise ValueError(f"SharedSegment: the caches hold {heads[0]} / {heads[1]} heads" +
                              (f", not the {kv_heads} kv heads of one sequence" if kv_heads is not None else "") +
@@ -50,32 +48,29 @@ class SharedSegment:
         self.kv_heads = heads[0]
         self.k_cache, self.v_cache = k_cache, v_cache
 
-    @staticmethod
-    def _heads(c) -> int:
-        return c.heads if isinstance(c, (CompressedArena, ExtentCache64)) else int(c[3].numel())
-
-    def _view(self, c, name):
-        if isinstance(c, (CompressedArena, ExtentCache64)):
-            if c.extents:
-                raise ValueError(f"SharedSegment: {name} has grown by {len(c.extents)} extents; consolidate() it first "
-                                 "(a shared segment is one view per side)")
-            if c.tokens != self.tokens:
-                raise ValueError(f"SharedSegment: {name} holds {c.tokens} tokens, not {self.tokens}")
-            if isinstance(c, CompressedArena):
-                c.poll()
-            return c.view_ptr()
-        if not isinstance(c, (list, tuple)) or len(c) != 4:
+    def _checked(self, c, name):
+        """`c` as it arrives at a call (reflayout.py), still frozen.  A list is wrapped ONCE, at construction: the flat stream and the
+        view are kept."""
+        if isinstance(c, (list, tuple)) and len(c) == 4:
+            return ListCache(c, self.tokens)
+        if not hasattr(c, "view_args"):
             raise ValueError(f"SharedSegment: {name} is a reference-layout [bitmaps, idxs, nzs, nz_offset], a CompressedArena or an "
                              "ExtentCache64 (a cache that grows by extents: consolidate() it first)")
-        if name not in self._keep:   # (the flat stream and the view, made once and kept: the view holds the stream's address)
-            flat = _flat_stream(c)
-            self._keep[name] = (flat, _lib.CacheView(c[0].data_ptr(), flat.data_ptr() if flat is not None and flat.numel() else None,
-                                                     c[1].data_ptr(), c[3].data_ptr(), 0, 0, 0))
-        return ctypes.byref(self._keep[name][1])
+        if c.extents:
+            raise ValueError(f"SharedSegment: {name} has grown by {len(c.extents)} extents; consolidate() it first "
+                             "(a shared segment is one view per side)")
+        if c.tokens != self.tokens:
+            raise ValueError(f"SharedSegment: {name} holds {c.tokens} tokens, not {self.tokens}")
+        return c
 
     def view_ptrs(self):
-        """The two `mustafar_cache_view` pointers of a call, checked and taken now."""
-        return self._view(self.k_cache, "k_cache"), self._view(self.v_cache, "v_cache")
+        """The two `mustafar_cache_view` pointers of a call, checked and taken now (an arena is poll()ed)."""
+        return self._checked(self._k, "k_cache").view_args(self._checked(self._v, "v_cache"), tables=False)[0][:2]
+
+    def decode(self, attn, query_states: torch.Tensor):
+        """decode_segment(attn, query_states, self): what MustafarAttention.decode_split calls for an entry that is no tuple."""
+        attn._segment_query(query_states)
+        return _decode_shared(attn, query_states, self)
 
     @classmethod
     def from_dense(cls, attn, key_states: torch.Tensor, value_states: torch.Tensor) -> "SharedSegment":
@@ -91,14 +86,7 @@ class SharedSegment:
 
     def bytes_in_use(self) -> int:
         """Bytes of the four arrays of both sides that hold the segment."""
-        def side(c, name):
-            if isinstance(c, CompressedArena):
-                return c.bytes_in_use()
-            flat = _flat_stream(c.base) if isinstance(c, ExtentCache64) else self._keep[name][0]
-            if isinstance(c, ExtentCache64):
-                c = c.base
-            return c[0].numel() * 8 + c[1].numel() * 4 + c[3].numel() * 4 + (flat.numel() * 2 if flat is not None else 0)
-        return side(self.k_cache, "k_cache") + side(self.v_cache, "v_cache")
+        return self._k.bytes_in_use() + self._v.bytes_in_use()
 
 
 def _decode_shared(attn, query_states: torch.Tensor, seg: SharedSegment):
@@ -143,51 +131,11 @@ def decode_segment(attn, query_states: torch.Tensor, k_cache, v_cache=None, toke
     k_cache / v_cache: the segment, of bsz * kv_heads heads: a reference-layout `[bitmaps, idxs, nzs, nz_offset]`, a CompressedArena
     (its extents included) or an ExtentCache64.  attention_mask: None or additive fp16 [bsz, 1, 1, >= tokens], column 0 = the
     segment's first token.  Returns (out fp16 [bsz, num_heads, 1, D], lse fp32 [bsz, num_heads])."""
-    bsz, H, q_len, D = query_states.shape
-    if q_len != 1 or H != attn.num_heads or D != attn.head_dim:
-        raise ValueError(f"decode_segment: query of shape {tuple(query_states.shape)} for {attn.num_heads} heads of {attn.head_dim}")
     if isinstance(k_cache, SharedSegment):
+        attn._segment_query(query_states)
         if v_cache is not None or tokens is not None:
             raise ValueError("decode_segment: a SharedSegment carries both caches and its token count")
         if attention_mask is not None:
             raise ValueError("decode_segment: a shared segment takes no attention mask (left padding and a shared prefix do not coexist)")
         return _decode_shared(attn, query_states, k_cache)
-    if v_cache is None or tokens is None:
-        raise ValueError("decode_segment: a per-sequence segment is (k_cache, v_cache, tokens)")
-    if tokens <= 0 or tokens % 64:
-        raise ValueError(f"decode_segment: a segment holds a positive multiple of 64 tokens (got {tokens})")
-    if D == 128:   # the LSE comes from the one-pass forms (mustafar_hip.h)
-        attn._lse_served(tokens)
-    if isinstance(k_cache, (CompressedArena, ExtentCache64)) and \
-            (type(k_cache) is not type(v_cache) or k_cache.total_tokens != tokens or v_cache.total_tokens != tokens):
-        raise ValueError(f"decode_segment: the caches hold {k_cache.total_tokens} / {v_cache.total_tokens} tokens, not {tokens}")
-    dev = query_states.device
-    # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
-    ops = attn._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
-    lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-    _call_decode(k_cache, v_cache, tokens, ops, D, None, lse)
-    return ops.out, lse
-
-
-def merge_states(outs: Sequence[torch.Tensor], lses: Sequence[torch.Tensor]):
-    """Merge partial attention states over disjoint token sets: outs[i] fp16 [bsz, H, 1, D] (normalised), lses[i] fp32 [bsz, H].
-    Returns (out fp16 [bsz, H, 1, D], lse fp32 [bsz, H]) of the attention over all of them; one launch behind the stacking."""
-    n = len(outs)
-    if n < 1 or n > 64 or len(lses) != n:
-        raise ValueError(f"merge_states: 1 to 64 parts with one LSE each (got {n} outputs, {len(lses)} LSEs)")
-    bsz, H, _, D = outs[0].shape
-    if D not in (64, 128):
-        raise ValueError(f"merge_states: head_dim 64 or 128 (got {D})")
-    for o, l in zip(outs, lses):
-        if o.shape != outs[0].shape or o.dtype != torch.float16 or tuple(l.shape) != (bsz, H) or l.dtype != torch.float32:
-            raise ValueError("merge_states: parts are fp16 [bsz, H, 1, D] outputs with fp32 [bsz, H] LSEs of one shape")
-    dev = outs[0].device
-    o_all = torch.stack([o.reshape(bsz * H, D) for o in outs])       # [n, BH, D]
-    l_all = torch.stack([l.reshape(bsz * H) for l in lses])          # [n, BH]
-    out = torch.empty((bsz, H, 1, D), dtype=torch.float16, device=dev)
-    lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        err = _lib.load().mustafar_merge_attention_states(torch.cuda.current_stream(dev).cuda_stream, o_all.data_ptr(), bsz * H * D,
-                                                          l_all.data_ptr(), bsz * H, n, bsz * H, D, out.data_ptr(), lse.data_ptr())
-    _lib.check(err, "mustafar_merge_attention_states")
-    return out, lse
+    return attn.decode_segment(query_states, k_cache, v_cache, tokens, attention_mask)

@@ -4,7 +4,10 @@ the real function, so every case also runs the kernels it names: the outputs mus
 
 Geometry: bsz 1, 8 query heads over 2 kv heads, residual_length 32.  A 543-token prefill leaves 256 compressed tokens and a 287-row
 window, so the first decode step fires the 256-token trigger and the second one reads a cache that has grown; a 40-token prefill leaves
-the compressed cache empty."""
+the compressed cache empty.
+
+The same recorder classifies the calls of `decode_multi` (mustafar_decode_multi_query: views, T_base, tables) and of `decode_segment` over a
+`SharedSegment` (mustafar_decode_shared_segment: two views and the token count), per cache kind."""
 import pytest
 import torch
 
@@ -170,3 +173,85 @@ def test_route_decode_segment(calls):
         assert o.shape == (1, HQ, 1, D) and l.shape == (1, HQ) and torch.isfinite(o).all() and torch.isfinite(l).all()
     for o, l in ((o_lst, l_lst), (o_one, l_one)):
         assert torch.equal(o.view(torch.int16), o_ref.view(torch.int16)) and torch.equal(l.view(torch.int32), l_ref.view(torch.int32))
+
+
+# ---- decode_multi and shared segments: how every cache kind arrives as views ----------------------------------------------------------------
+def _view_routes(calls):
+    """[(entry point, "views" | "null views", T_base | tokens, "tables" | "no tables")] of the multi-query and shared-segment calls made."""
+    out = []
+    for name, args in calls:
+        if name not in ("mustafar_decode_multi_query", "mustafar_decode_shared_segment"):
+            continue
+        assert _null(args[1]) == _null(args[2]), name
+        tables = "no tables"
+        if name == "mustafar_decode_multi_query":
+            assert _null(args[4]) == _null(args[5])
+            tables = "no tables" if _null(args[4]) else "tables"
+        out.append((name[len("mustafar_decode_"):], "null views" if _null(args[1]) else "views", args[3], tables))
+    return out
+
+
+def _multi(attn, past, D, seed=11):
+    """One decode_multi call of n_q = 2 (out and LSE finite), closed by accept().  Returns the past."""
+    q, k, v = _rand(D, 2, seed)
+    out, lse, past = attn.decode_multi(q, k, v, past, return_lse=True)
+    assert out.shape == (1, HQ, 2, D) and lse.shape == (1, HQ, 2) and torch.isfinite(out).all() and torch.isfinite(lse).all()
+    past = attn.accept(past)
+    torch.cuda.synchronize()
+    return past
+
+
+@pytest.mark.parametrize("D,kw", [(128, {}), (64, {}), (128, {"arena": True}), (64, {"hd64_extents": True})],
+                         ids=["d128-list", "d64-list", "d128-arena", "d64-extents"])
+def test_multi_query_route_nothing_compressed(calls, D, kw):
+    attn = _hook(D, **kw)
+    past = _multi(attn, _prefilled(attn, D, 40), D)
+    assert past[0] is None and past[4] == 0 and past[5] == 42
+    assert _view_routes(calls) == [("multi_query", "null views", 0, "no tables")]
+
+
+MULTI_GROWN = [
+    # D, config, T_base and tables of the call over the cache one trigger has grown to 512 tokens
+    (128, {}, 512, "no tables"),                                   # a list: T_base = C
+    (64, {}, 512, "no tables"),
+    (128, {"arena": True, "extents": False}, 512, "no tables"),    # an arena appended in place: at its base, its tokens
+    (128, {"arena": True}, 256, "tables"),                         # an arena that grew by an extent: its base tokens
+    (64, {"hd64_extents": True}, 256, "tables"),                   # ExtentCache64: its base tokens, always tables
+]
+
+
+@pytest.mark.parametrize("D,kw,t_base,tables", MULTI_GROWN, ids=["d128-list", "d64-list", "d128-arena-base", "d128-arena-grown", "d64-extents"])
+def test_multi_query_route_after_a_trigger(calls, D, kw, t_base, tables):
+    attn = _hook(D, **kw)
+    past = _steps(attn, _prefilled(attn, D, 543), D, steps=1)
+    assert past[4] == 512
+    if kw:
+        assert past[0].tokens == t_base and len(past[0].extents) == (512 - t_base) // 256
+    past = _multi(attn, past, D)
+    assert past[4] == 512 and past[5] == 546 and past[1].len == 34
+    assert _view_routes(calls) == [("multi_query", "views", t_base, tables)]
+
+
+def test_multi_query_route_extent_cache_at_its_base(calls):
+    """An ExtentCache64 with no extent listed (consolidated) still names its tables."""
+    attn = _hook(64, hd64_extents=True)
+    p = _steps(attn, _prefilled(attn, 64, 543), 64, steps=1)
+    past = _multi(attn, (p[0].consolidate(), p[1], p[2].consolidate(), p[3], p[4], p[5]), 64)
+    assert past[0].tokens == 512 and not past[0].extents
+    assert _view_routes(calls) == [("multi_query", "views", 512, "tables")]
+
+
+@pytest.mark.parametrize("D,kw", [(128, {}), (64, {}), (128, {"arena": True}), (64, {"hd64_extents": True})],
+                         ids=["d128-list", "d64-list", "d128-arena", "d64-extents"])
+def test_shared_segment_route(calls, D, kw):
+    """decode_segment over a SharedSegment of 256 tokens: two views and tokens = 256, whatever holds the segment."""
+    attn = _hook(D, **kw)
+    past = attn.to_fused(_prefilled(attn, D, 543))
+    if kw:
+        assert not isinstance(past[0], list) and past[0].tokens == 256 and not past[0].extents
+    seg = partial.SharedSegment(past[0], past[2], 256, kv_heads=HKV)
+    q, _, _ = _rand(D, 1, seed=5)
+    out, lse = partial.decode_segment(attn, q, seg)
+    torch.cuda.synchronize()
+    assert out.shape == (1, HQ, 1, D) and lse.shape == (1, HQ) and torch.isfinite(out).all() and torch.isfinite(lse).all()
+    assert _view_routes(calls) == [("shared_segment", "views", 256, "no tables")]

@@ -1,5 +1,5 @@
 """GPU: the head_dim-64 prefill compressed from the raw rows (mustafar_prefill_compress_hd + mustafar_cache_gather_hd behind
-compression.compress_raw_pair_hd64 and MustafarConfig(hd64_raw_prefill=True)) and ExtentCache64.consolidate() on the device.  Every
+cache64.compress_raw_pair_hd64 and MustafarConfig(hd64_raw_prefill=True)) and ExtentCache64.consolidate() on the device.  Every
 comparison is bit for bit: against prune + the two-pass conversion, against the oracle, against to_reference()."""
 import ctypes
 
@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from mustafar_amd import cache64
 from oracle import oracle as orc
 from tests.hd64_ext_util import SENTINEL, ExtCase, Trigger, kth, run_triggers, same_reference
 from tests.hd64_util import DEV, D, _cache, _rand, needle_data_64, needle_expect_64, oracle_prune
@@ -42,7 +43,7 @@ def _same(got, want):
 
 
 def _both(comp, K, V, C, ks, vs):
-    gk, gv = comp.compress_raw_pair_hd64(K, V, C, kth(ks), kth(vs))
+    gk, gv = cache64.compress_raw_pair_hd64(K, V, C, kth(ks), kth(vs))
     _same(gk, _old_route(K, C, ks, "key"))
     _same(gv, _old_route(V, C, vs, "value"))
     return gk, gv
@@ -107,10 +108,10 @@ def test_a_chunk_full_of_ties_overflows_its_region_and_is_repeated_once(pkg):
     C = 512
     K, V, _ = _rand(1, 3, C + 40, 1, seed=31)
     K[0, 1, 256:512] = 0.5                                   # head 1, second chunk only: every value is kept, 256 x 64 halfs
-    assert comp.hd64_staging_region(kth(0.7)) < 256 * D
-    before = comp.hd64_prefill_repeats
+    assert cache64.hd64_staging_region(kth(0.7)) < 256 * D
+    before = cache64.hd64_prefill_repeats
     _both(comp, K, V, C, 0.7, 0.7)
-    assert comp.hd64_prefill_repeats == before + 1
+    assert cache64.hd64_prefill_repeats == before + 1
 
 
 # ---- 5. kth == 0 ----------------------------------------------------------------------------------------------------------------------------------
@@ -119,9 +120,9 @@ def test_raw_prefill_with_kth_0_takes_pruned_rows_as_they_are(pkg):
     C = 512
     K, V, _ = _rand(1, 3, C + 40, 1, seed=41)
     Kp, Vp = oracle_prune(K, 0.5), oracle_prune(V, 0.8)
-    before = comp.hd64_prefill_repeats
-    gk, gv = comp.compress_raw_pair_hd64(Kp, Vp, C, 0, 0)
-    assert comp.hd64_prefill_repeats == before, "kth = 0 houses every chunk at the dense size"
+    before = cache64.hd64_prefill_repeats
+    gk, gv = cache64.compress_raw_pair_hd64(Kp, Vp, C, 0, 0)
+    assert cache64.hd64_prefill_repeats == before, "kth = 0 houses every chunk at the dense size"
     _same(gk, _old_route(Kp, C, None, "key", pruned=True))
     _same(gv, _old_route(Vp, C, None, "value", pruned=True))
 

@@ -1,5 +1,5 @@
 """CPU: the head_dim-64 prefill / gather surface of the C ABI (ABI 109), the hook's hd64_raw_prefill rule and the staging bound of
-compression.compress_raw_pair_hd64.  No kernel runs: every call here must fail validation before a launch."""
+cache64.compress_raw_pair_hd64.  No kernel runs: every call here must fail validation before a launch."""
 import ctypes
 import os
 import re
@@ -118,15 +118,15 @@ def _distinct_rows(rng, rows):
 @pytest.mark.parametrize("kth", list(range(1, 65)))
 def test_staging_region_bounds_the_oracles_longest_chunk_on_tie_free_rows(kth):
     """The bound, not luck, keeps the common case from repeating: on 200 random tie-free rows (the chunk's other 56 rows repeat some of
-    them) the oracle's stream of a 256-token chunk, K and V geometry, is no longer than compression.hd64_staging_region(kth)."""
-    from mustafar_amd import compression
+    them) the oracle's stream of a 256-token chunk, K and V geometry, is no longer than cache64.hd64_staging_region(kth)."""
+    from mustafar_amd import cache64
     rng = np.random.default_rng(kth)
     rows = _distinct_rows(rng, 200)
     chunk = np.concatenate([rows, rows[rng.integers(0, 200, 56)]])[None]
     pruned = orc.prune_magnitude(chunk, kth / 64)            # max(1, int(kth / 64 * 64)) == kth exactly
     assert orc.kth_from_sparsity(kth / 64, 64) == kth
     assert ((pruned.view(np.uint16) & 0x7fff) != 0).sum(-1).tolist() == [[64 - kth + 1] * 256], "the rows are not tie-free"
-    bound = compression.hd64_staging_region(kth)
+    bound = cache64.hd64_staging_region(kth)
     assert bound % 8 == 0 and bound <= 256 * 64
     for conv in (orc.convert_key_batched, orc.convert_value_batched):
         _, accum, _ = conv(pruned)
@@ -134,8 +134,8 @@ def test_staging_region_bounds_the_oracles_longest_chunk_on_tie_free_rows(kth):
 
 
 def test_staging_region_formula():
-    from mustafar_amd import compression
-    assert compression.hd64_staging_region(0) == 256 * 64                          # rows pruned by the caller: anything may be kept
-    assert compression.hd64_staging_region(44) == 256 * 21 + 7 * 256               # 70 %
-    assert compression.hd64_staging_region(1) == compression.hd64_staging_region(8) == 256 * 64   # bound above the dense rows
-    assert compression.hd64_staging_region(64) == 256 + 7 * 256
+    from mustafar_amd import cache64
+    assert cache64.hd64_staging_region(0) == 256 * 64                          # rows pruned by the caller: anything may be kept
+    assert cache64.hd64_staging_region(44) == 256 * 21 + 7 * 256               # 70 %
+    assert cache64.hd64_staging_region(1) == cache64.hd64_staging_region(8) == 256 * 64   # bound above the dense rows
+    assert cache64.hd64_staging_region(64) == 256 + 7 * 256

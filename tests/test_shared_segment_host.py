@@ -125,10 +125,10 @@ def test_shared_segment_refuses_the_wrong_number_of_heads():
 def test_a_list_of_per_head_streams_is_concatenated_once():
     from mustafar_amd import partial
     seg = partial.SharedSegment(_fake_cache(2, 128, 64), _fake_cache(2, 128, 64), 128)
-    flat = seg._keep["k_cache"][0]
+    flat = seg._k.flat
     assert flat.numel() == 16 and seg.bytes_in_use() == 2 * (2 * 128 * 8 + 2 * 129 * 4 + 2 * 4 + 16 * 2)
     seg.view_ptrs()
-    assert seg._keep["k_cache"][0] is flat
+    assert seg._k.flat is flat
 
 
 def test_decode_split_refuses_a_mask_together_with_a_shared_entry():

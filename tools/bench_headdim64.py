@@ -18,7 +18,7 @@ instantiation against the plain one at the same T with no extent listed.
 --prefill (default off; --prefill-runs N, default 21) adds a prefill leg at L = 8192, one layer, alternated A B A B in one process behind
 a warm-up of 3 runs each, median wall time of N runs per way, every run ended by a device synchronise:
   prefill_old_us    the parent's route: prune + two conversions of K and V (build_cache; its host waits included)
-  prefill_raw_us    MustafarConfig(hd64_raw_prefill=True): compression.compress_raw_pair_hd64 (its one wait included) + the windows
+  prefill_raw_us    MustafarConfig(hd64_raw_prefill=True): cache64.compress_raw_pair_hd64 (its one wait included) + the windows
 and consolidate() of one side at a base of 7936 tokens plus 3 and plus 32 extents, on the device and through to_reference(), the same way.
 The results of both ways are compared bit for bit before anything is timed.
 Needs an MI355X; it does not fall back to anything.  Usage: python tools/bench_headdim64.py [--lengths 4096,8192,32768] [--steps 64]
