@@ -193,7 +193,40 @@ typedef struct mustafar_cache_view {
     int64_t   idx_head_stride;
     int64_t   nz_head_stride;   /* != 0: nz_offset[h] == h * nz_head_stride (uint4 units, < 2^32): the SpMV kernels then compute
                                    the head's stream start instead of loading it (one memory latency less per wave) */
+    uint32_t  flags;            /* 0: the tile format above.  MUSTAFAR_VIEW_KEY_ROWS (ABI 113): a KEY cache held as token rows, see below */
 } mustafar_cache_view;
+
+/*
+ * Token-row key blocks (ABI 113): the form the GQA-4 one-pass super-block launch reads a key BASE in.  Made from a
+ * tile-format key cache by mustafar_key_rows_plan + mustafar_key_rows_fill and turned back, bit for bit, by mustafar_key_rows_to_tiles.
+ * Per kv head and 64-token block:
+ *   w            the largest number of channels a token of the block keeps, rounded up to even (2 .. 128; an all-zero block: 2)
+ *   ceil(w / 4)  rows of 64 x 4 bytes: the channels of slots 4j .. 4j + 3 of token t in lane t, then
+ *   w / 2        rows of 64 half2: the values of slots 2j, 2j + 1 of token t in lane t
+ * A token's slots hold its non-zero channels in ascending order; the slots behind them hold value +0 / channel 0.  A row is 256 bytes.
+ * A view with MUSTAFAR_VIEW_KEY_ROWS in `flags` names such a cache:
+ *   nz               the rows; head h starts at h * nz_head_stride uint4 units (nz_head_stride != 0, a multiple of 16)
+ *   idx              u32 [B', idx_head_stride] block table: entry b = (first row of block b, counted from the head's start) << 8 | w
+ *   bmp, nz_offset   unused (may be NULL)
+ * Only mustafar_decode_attention_view / _extents / _extents_lse_hd read such a view, and only as the key BASE of a launch for which
+ * mustafar_decode_reads_key_rows() is 1; every other entry point, and every other use, returns MUSTAFAR_EINVAL.
+ */
+#define MUSTAFAR_VIEW_KEY_ROWS 1u
+/* Pass 1: block widths and the block table.  src: a tile-format KEY view of `tokens` tokens (tokens % 64 == 0) and Bp heads.
+ * table u32 [Bp][tokens / 64] and head_rows i64 [Bp] (each head's number of rows) are written; the caller reads head_rows to size `nz`. */
+int mustafar_key_rows_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_rows);
+/* Pass 2: every row of every block.  dst: a MUSTAFAR_VIEW_KEY_ROWS view whose idx is the table of pass 1 (idx_head_stride == tokens / 64). */
+int mustafar_key_rows_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens);
+/* Back to tiles: bitmaps, offsets (idx[h][0] = 0 included) and the stream of the first `tokens` tokens of every head of `dst`, a tile-format
+ * view with equally spaced stream regions (nz_head_stride != 0) that hold the streams; head_total i64 [Bp]: each head's stream length in halfs.
+ * Three launches; nothing is read on the host.  What tiles -> rows -> tiles leaves is what it started from, bit for bit. */
+int mustafar_key_rows_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total);
+/* Whether the launch that a fused call of this shape runs reads a key base of token rows: 1 for the GQA-4 one-pass super-block launch of four
+ * blocks per workgroup on v_fma_mix or v_dot2 (num_key_value_groups % 4 == 0), 0 for its launches of two blocks per workgroup (under 768
+ * workgroups: measured slower on rows), for the pair, small and two-launch forms and for the matrix pipe.  T: the
+ * compressed tokens the launch is sized for; gy: B' * num_key_value_groups / 4, the head groups of its grid.  Answered from the shape
+ * rule of the launch itself, with the largest window standing in for the call's own (as mustafar_decode_reads_extents does). */
+int mustafar_decode_reads_key_rows(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
 
 /*
  * mustafar_decode_attention over a cache that GROWS BY EXTENTS (the 256-token trigger of models/llama_mustafar_kernel.py:324-398

@@ -17,7 +17,10 @@ _vp, _i32, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 class CacheView(ctypes.Structure):
     """`mustafar_cache_view` of include/mustafar_hip.h: the four arrays of the compressed format + the head strides."""
     _fields_ = [("bmp", _vp), ("nz", _vp), ("idx", _vp), ("nz_offset", _vp),
-                ("bmp_head_stride", _i64), ("idx_head_stride", _i64), ("nz_head_stride", _i64)]
+                ("bmp_head_stride", _i64), ("idx_head_stride", _i64), ("nz_head_stride", _i64), ("flags", ctypes.c_uint32)]
+
+
+VIEW_KEY_ROWS = 1   # MUSTAFAR_VIEW_KEY_ROWS: a key base held as token rows (cache.CompressedArena.to_key_rows)
 
 
 _view_p = ctypes.POINTER(CacheView)
@@ -64,6 +67,10 @@ SIGNATURES = {
                                            _i64, _i64, _vp]),
     "mustafar_cache_gather_hd": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _i32, _i32, _i32]),
     "mustafar_decode_reads_extents": (_i32, [_i32, _i32, ctypes.c_uint32]),
+    "mustafar_decode_reads_key_rows": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_uint32]),
+    "mustafar_key_rows_plan": (_i32, [_vp, _view_p, _i32, _i32, _vp, _vp]),
+    "mustafar_key_rows_fill": (_i32, [_vp, _view_p, _view_p, _i32, _i32]),
+    "mustafar_key_rows_to_tiles": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _vp]),
     "mustafar_cache_append_bitmap_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_bitmap_value": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_pack_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32]),

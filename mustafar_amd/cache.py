@@ -162,6 +162,72 @@ class CompressedArena:
                                     tiles, tiles + 1,
                                     nz_cap // 8 if (H * (nz_cap // 8) < 2 ** 32 and os.environ.get("MUSTAFAR_NZ_STRIDE", "1") != "0") else 0)
 
+    # ---- token-row key blocks (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS) -------------------------------------
+    @property
+    def key_rows(self) -> bool:
+        """True while the base of this KEY arena is held as token rows.  Then `nz` is the rows (fp16 [H, 128 x rows per head]), `idx` the
+        block table (int32 [H, tokens / 64]) and `bmp` is empty; only the GQA-4 one-pass super-block launch reads it.  Everything else
+        calls `require_tiles()` first."""
+        return bool(self._view.flags & _lib.VIEW_KEY_ROWS)
+
+    def to_key_rows(self) -> bool:
+        """Retile the base from tiles to token rows on the device, in place of the tile arrays (which are released).  One small host
+        read (the heads' row counts size the allocation).  False, and nothing changed, where this arena cannot take the form: a value
+        arena, an empty one, one without equally spaced stream regions, or under stream capture.  hook.MustafarAttention.to_fused() is
+        the only caller outside the tests."""
+        if self.key_rows:
+            return True
+        if self.which != "key" or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
+            return False
+        used = self.used   # (resolves an asynchronous append still in flight)
+        H, nb, dev = self.heads, self.tokens // 64, self.device
+        L = _lib.load()
+        table = torch.empty((H, nb), dtype=torch.int32, device=dev)
+        head_rows = torch.empty(H, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(L.mustafar_key_rows_plan(st, ctypes.byref(self._view), H, self.tokens, table.data_ptr(), head_rows.data_ptr()),
+                       "mustafar_key_rows_plan")
+            counts = head_rows.cpu()
+            stride_rows = int(counts.max())
+            rows = torch.empty((H, stride_rows * 128), dtype=torch.float16, device=dev)
+            view = _lib.CacheView(None, rows.data_ptr(), table.data_ptr(), None, 0, nb, stride_rows * 16, _lib.VIEW_KEY_ROWS)
+            _lib.check(L.mustafar_key_rows_fill(st, ctypes.byref(self._view), ctypes.byref(view), H, self.tokens), "mustafar_key_rows_fill")
+        # (the tile arrays are released behind the launch that read them: the allocator is stream-ordered)
+        self._tile_caps = (self.cap_tokens, self.nz_cap)
+        self._row_counts = counts
+        self._buf = None
+        self.bmp = torch.empty((H, 0), dtype=torch.int64, device=dev)
+        self.idx, self.nz = table, rows
+        self.nz_offset = self.nz_offset.clone()
+        self._totals, self._overflow = self._totals.clone(), self._overflow.clone()
+        self._view = view
+        self._used = used
+        return True
+
+    keep_tiles = False   # set by require_tiles(): to_fused() does not retile this arena into rows again (no ping-pong between a caller's
+                         # decode_fused and decode_multi / shared-segment calls); consolidate() clears it for its result
+
+    def require_tiles(self, sticky: bool = True) -> None:
+        """Back to the tile format on the device, bit for bit what `to_key_rows()` started from (same row capacity, same stream regions;
+        the addresses are new).  Nothing to do for an arena in tiles.  Raises under stream capture: a captured graph holds the addresses.
+        sticky: the arena then stays in tiles (`keep_tiles`) -- whoever needed tiles once will need them again."""
+        if not self.key_rows:
+            return
+        self.keep_tiles = sticky
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("CompressedArena.require_tiles: the key base is held as token rows and this call needs tiles; the retile cannot run "
+                               "under graph capture (call require_tiles() before the capture, or MustafarConfig(key_rows=False))")
+        used, tokens, rows_view, keep = self._used, self.tokens, self._view, (self.idx, self.nz)
+        self._alloc(*self._tile_caps)
+        self._init_empty()
+        with torch.cuda.device(self.device):
+            err = _lib.load().mustafar_key_rows_to_tiles(torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(rows_view),
+                                                         ctypes.byref(self._view), self.heads, tokens, self._totals.data_ptr())
+        _lib.check(err, "mustafar_key_rows_to_tiles")
+        del keep
+        self.used, self.tokens = used, tokens
+
     def _init_empty(self):
         """An arena that starts empty: stream starts of the heads, offset 0 of every head, flag 0."""
         torch.mul(_head_index(self.heads, self.device), self.nz_cap // 8, out=self.nz_offset)
@@ -224,11 +290,17 @@ class CompressedArena:
         kt, vt = (self.ext_table.data_ptr(), v_arena.ext_table.data_ptr()) if tables else (None, None)
         return (self.view_ptr(), v_arena.view_ptr(), self.tokens, kt, vt), ()
 
-    view_args = decode_args   # (an arena always arrives as views)
+    def view_args(self, v_arena: "CompressedArena", tables: bool):
+        """`decode_args` for the calls that take views of TILES (multi-query, shared segment): a key base in token rows is retiled back."""
+        self.require_tiles()
+        return self.decode_args(v_arena, tables)
 
     def bytes_in_use(self) -> int:
+        ext = sum(e.bytes_in_use() for e in self.extents)
+        if self.key_rows:   # the block table + every head's rows of 256 bytes
+            return self.heads * (self.tokens // 64) * 4 + int(self._row_counts.sum()) * 256 + ext
         t = self.tokens * self.TILES_PER_TOKEN
-        return self.heads * (t * 8 + (t + 1) * 4 + 4) + int(self.used.sum()) * 2 + sum(e.bytes_in_use() for e in self.extents)
+        return self.heads * (t * 8 + (t + 1) * 4 + 4) + int(self.used.sum()) * 2 + ext
 
     def bytes_reserved(self) -> int:
         own = sum(x.numel() * x.element_size() for x in (self.bmp, self.idx, self.nz, self.nz_offset))
@@ -380,6 +452,7 @@ class CompressedArena:
         """One base arena holding everything (a copy of the cache; the addresses of the result are new).  Round 5: on the device -- two
         launches, no host read (mustafar_cache_rehouse for the base, mustafar_cache_consolidate_extents for the extents, found through
         the device table the decode launch reads): c3, 32 layers, K and V: 162 ms through the reference layout on the host -> a few ms."""
+        self.require_tiles(sticky=False)   # (the result is a tile arena; the next to_fused() may retile it again)
         if not self.extents:
             return self
         n = len(self.extents)
@@ -408,6 +481,7 @@ class CompressedArena:
     def _rehouse(self, cap_tokens: int, nz_cap: int):
         """Move the cache into rows of `cap_tokens` tokens and stream regions of `nz_cap` halfs (never below what it holds):
         one allocation, one launch (mustafar_cache_rehouse); the old storage is released when the copy has been enqueued."""
+        self.require_tiles()
         used, tokens = self.used.clone(), self.tokens              # (resolves a pending asynchronous append)
         m = int(used.max()) if tokens else 0
         assert cap_tokens >= tokens and nz_cap >= m
@@ -453,6 +527,7 @@ class CompressedArena:
         """x: pruned fp16 [B', t, 128], t % 64 == 0 -> appended behind the tokens in use."""
         if x.dim() != 3 or x.shape[0] != self.heads or x.shape[2] != 128 or x.shape[1] % 64 or x.dtype != torch.float16:
             raise RuntimeError("CompressedArena.append expects a pruned fp16 [B', t, 128] tensor with t % 64 == 0")
+        self.require_tiles()
         if not x.is_contiguous():
             x = x.contiguous()
         t = x.shape[1]
@@ -503,6 +578,7 @@ class CompressedArena:
             raise RuntimeError("append_window_pair: K and V arenas must describe the same heads and tokens; t % 64 == 0")
         if k_arena.extents or v_arena.extents:
             raise RuntimeError("append_window_pair: the cache has grown by extents; append_extent_pair() or consolidate()")
+        k_arena.require_tiles()   # (an append in place writes tiles behind tiles)
         for x in (k_rows, v_rows):
             if x.dtype != torch.float16 or x.dim() != 4 or x.shape[0] * x.shape[1] != heads or x.shape[3] != 128 or x.shape[2] < t \
                     or not x.is_contiguous():
@@ -652,6 +728,7 @@ class CompressedArena:
         return [base[0].view(self.heads, -1), base[1].view(self.heads, -1), base[2], base[3]]
 
     def _base_reference(self) -> list:
+        self.require_tiles()
         t = self.tokens * self.TILES_PER_TOKEN
         bmp = self.bmp[:, :t].contiguous()
         idx = self.idx[:, :t + 1].contiguous()

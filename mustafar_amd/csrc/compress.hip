@@ -809,7 +809,7 @@ inline Rows fresh_rows(int t) { const int64_t tiles = (int64_t)t * kD / 64; retu
 // Rows of a cache view behind `old_tokens`; false if the view cannot take t more tokens.
 inline bool view_rows(const mustafar_cache_view* v, int old_tokens, int t, Rows& rows)
 {
-    if (!v || !v->bmp || !v->idx || !v->nz_offset || old_tokens < 0 || (old_tokens & 63)) return false;
+    if (!v || v->flags || !v->bmp || !v->idx || !v->nz_offset || old_tokens < 0 || (old_tokens & 63)) return false;   // (flags: tiles only, not token rows)
     const int64_t tiles = (int64_t)(old_tokens + t) * kD / 64;
     rows = Rows{v->bmp_head_stride ? v->bmp_head_stride : tiles, v->idx_head_stride ? v->idx_head_stride : tiles + 1,
                 (int64_t)old_tokens * kD / 64};
@@ -1191,7 +1191,7 @@ int mustafar_cache_rehouse(void* stream, const mustafar_cache_view* src, const m
                            int64_t stream_halfs)
 {
     const int64_t tiles = (int64_t)tokens * kD / 64;
-    if (!src || !dst || Bp < 1 || tokens < 0 || (tokens & 63) || stream_halfs < 0 || (stream_halfs & 7) || !src->bmp || !src->idx ||
+    if (!src || !dst || src->flags || dst->flags || Bp < 1 || tokens < 0 || (tokens & 63) || stream_halfs < 0 || (stream_halfs & 7) || !src->bmp || !src->idx ||
         !src->nz || !src->nz_offset || !dst->bmp || !dst->idx || !dst->nz || !dst->nz_offset || dst->nz_head_stride <= 0 ||
         stream_halfs > 8 * dst->nz_head_stride || (src->bmp_head_stride ? src->bmp_head_stride : tiles) < tiles ||
         (dst->bmp_head_stride ? dst->bmp_head_stride : tiles) < tiles || (src->idx_head_stride ? src->idx_head_stride : tiles + 1) < tiles + 1 ||
@@ -1228,7 +1228,7 @@ int mustafar_compress_test_skip_publish(int block)
 int mustafar_cache_consolidate_extents(void* stream, const mustafar_cache_view* dst, const mustafar_cache_view* extents, int n_extents, int Bp,
                                        int base_tokens, int64_t max_extent_halfs)
 {
-    if (!dst || !extents || n_extents < 1 || Bp < 1 || base_tokens < 0 || (base_tokens & 63) || max_extent_halfs < 0 || !dst->bmp || !dst->idx ||
+    if (!dst || dst->flags || !extents || n_extents < 1 || Bp < 1 || base_tokens < 0 || (base_tokens & 63) || max_extent_halfs < 0 || !dst->bmp || !dst->idx ||
         !dst->nz || dst->nz_head_stride <= 0 || 3 * (int64_t)n_extents > 65535)
         return MUSTAFAR_EINVAL;
     const int64_t tiles = ((int64_t)base_tokens + 256ll * n_extents) * kD / 64;

@@ -185,7 +185,7 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // A side's view with its strides resolved, or false: rows shorter than the tokens, a stream the kernel cannot address.
 inline bool side_of(const mustafar_cache_view* v, int T, int kv_heads, int D, SideArgs* s)
 {
-    if (!v || !v->bmp || !v->idx || !v->nz || !aligned16(v->nz)) return false;
+    if (!v || v->flags || !v->bmp || !v->idx || !v->nz || !aligned16(v->nz)) return false;   // (flags: tiles only, not token rows)
     const int64_t tiles = (int64_t)T * D / 64;
     if ((v->bmp_head_stride && v->bmp_head_stride < tiles) || (v->idx_head_stride && v->idx_head_stride < tiles + 1)) return false;
     if (v->nz_head_stride < 0 || (int64_t)kv_heads * v->nz_head_stride > 0xffffffffll || (!v->nz_head_stride && !v->nz_offset)) return false;

@@ -531,7 +531,7 @@ struct ExtArgs {
 struct NoExt {};
 template <bool EXT> struct ExtOf { typedef NoExt type; };
 template <> struct ExtOf<true> { typedef ExtArgs type; };
-static_assert(sizeof(mustafar_cache_view) == 56, "the EXT kernel reads a table entry as seven 8-byte words");
+static_assert(sizeof(mustafar_cache_view) == 64, "the EXT kernel reads the first seven 8-byte words of a table entry (the eighth holds the flags: extents are tiles)");
 // The row kernel's LSE output, carried the same way: the instantiation without one takes an empty struct and stays what it was.
 struct LseArg { float* ptr; };
 struct NoLse {};
@@ -933,6 +933,7 @@ int decode(const DecodeCall& c, hipEvent_t* ev, bool* ran_extents)
 {
     *ran_extents = false;
     const mustafar_cache_view* b[2] = {&c.k, &c.v};
+    if (c.k.flags || c.v.flags) return MUSTAFAR_EINVAL;   // (token rows are a head_dim 128 form)
     if (!c.k_ext) {   // the plain launch; base views that carry row strides (T == T_base at an extents entry point) must have rows exactly T long
         for (int i = 0; i < 2; i++)
             if ((b[i]->bmp_head_stride && b[i]->bmp_head_stride != c.T) || (b[i]->idx_head_stride && b[i]->idx_head_stride != c.T + 1))

@@ -190,7 +190,7 @@ struct BlockRef {
     const uint32_t* idx;
     const uint4* nz;
 };
-static_assert(sizeof(mustafar_cache_view) == 56, "a table entry is read as seven 8-byte words");
+static_assert(sizeof(mustafar_cache_view) == 64, "the first seven 8-byte words of a table entry are read (the eighth holds the flags: extents are tiles)");
 // Block j (0..3) of a table entry, head kvh: every field a scalar load (the entry is wave-uniform), offsets relative to the extent.
 template <int TILES>
 __device__ __forceinline__ BlockRef extent_block(const mustafar_cache_view* entry, int kvh, int j)

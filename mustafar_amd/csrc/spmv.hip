@@ -1556,6 +1556,9 @@ struct OneArgs {   // operands of the one-pass launch beyond the two caches (by 
     // workgroups of a launch's LAST, nearly empty round (a cache a trigger or two past one resident round of workgroups: T = 8448 at c3's
     // geometry is 2112 workgroups on 2048 slots) start when the first slots free up and would otherwise crawl along at an eighth of a SIMD
     int hi_prio_from = 0x7fffffff;
+    // round 7 (super-block pair form, GQA-4 on the vector engines): the key BASE arrives as token rows (MUSTAFAR_VIEW_KEY_ROWS): k_nz = the
+    // rows, k_idx = the block table, k_nz_stride / k_idx_stride their head strides.  Appended extents stay tiles.
+    int key_rows = 0;
 };
 
 // Window workgroup: 64 window tokens of one head batch -> scores, softmax partial, p.V partial -> slab (S + chunk).
@@ -2605,6 +2608,131 @@ __device__ __forceinline__ uint32_t ld_at(const void* __restrict__ sbase, uint32
 {
     return *reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(sbase) + voff);
 }
+// ---- key phase over TOKEN ROWS (round 7; include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS).  Lane = token.  A block of width w is
+// ceil(w / 4) rows of 64 x 4 channel bytes and w / 2 rows of 64 half2 (slots 2j, 2j + 1 of every token); a WORD is one channel row and the two
+// value rows that go with it: three coalesced 256-byte loads per wave (scalar row offset + lane offset: no address arithmetic), then per slot
+// one shift of its channel byte, one ds_read_b64 of the q table ([128 channels][4 heads] fp16 at a FIXED LDS address, so that the table's
+// place is the instruction's offset field) and four v_fma_mix.  No bitmap, no rank, no zeroing, no EXEC switch, no staging of the stream.
+// The even wave of a pair takes the first half of a block's words (rounded up), the odd wave the rest; the words of blocks A and B are
+// walked side by side, the next two requested while the current two are multiplied, and the eight table reads of a step are issued
+// ahead of its 32 products.  Slots behind a token's non-zeros hold value +0 / channel 0 and add +0.  Exact fp16 x fp16 products.
+struct KeyRowWord {
+    uint32_t ch, v0, v1;   // four channel bytes; slots 0, 1 and slots 2, 3 as half2
+};
+// A block as a buffer of its own (rows_of(w) x 256 bytes: channel rows, then value rows): a load is scalar row offset + lane offset, no
+// address arithmetic.  Non-temporal as the tile stream's loads: every byte is read once.  A width that is no multiple of four (42 is
+// the common one at 70 %: 40 kept channels and one magnitude tie among a block's 64 tokens) ends in a HALF word: one value row, two slots.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t key_row_block(const unsigned char* __restrict__ rows, uint32_t ent)
+{
+    const int w = ent & 0xffu;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(rows + 256ull * (ent >> 8)), (short)0, 256 * ((w >> 1) + ((w + 3) >> 2)), 0x00020000);
+}
+template <bool HALF = false>
+__device__ __forceinline__ KeyRowWord key_row_word(__amdgpu_buffer_rsrc_t blk, int nword, int wd, int lane4)
+{
+    constexpr int kStreamAux = 2;
+    KeyRowWord r;
+    r.ch = __builtin_amdgcn_raw_buffer_load_b32(blk, lane4, 256 * wd, kStreamAux);
+    r.v0 = __builtin_amdgcn_raw_buffer_load_b32(blk, lane4, 256 * (nword + 2 * wd), kStreamAux);
+    r.v1 = 0u;
+    if constexpr (!HALF) r.v1 = __builtin_amdgcn_raw_buffer_load_b32(blk, lane4, 256 * (nword + 2 * wd + 1), kStreamAux);
+    return r;
+}
+template <int K = 4>   // K slots of the word: 4, or 2 for a half word
+__device__ __forceinline__ void key_row_q(uint32_t ch, const unsigned char* qtab, uint2 (&q)[4])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) q[k] = *reinterpret_cast<const uint2*>(qtab + (((ch >> (8 * k)) & 0xffu) << 3));
+}
+template <int K = 4>
+__device__ __forceinline__ void key_row_fma(const KeyRowWord& r, const uint2 (&q)[4], float (&s)[4])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const h16x2 v = __builtin_bit_cast(h16x2, k < 2 ? r.v0 : r.v1);
+        const h16x2 q01 = __builtin_bit_cast(h16x2, q[k].x), q23 = __builtin_bit_cast(h16x2, q[k].y);
+        const float x = (float)v[k & 1];
+        s[0] = __builtin_fmaf(x, (float)q01[0], s[0]);
+        s[1] = __builtin_fmaf(x, (float)q01[1], s[1]);
+        s[2] = __builtin_fmaf(x, (float)q23[0], s[2]);
+        s[3] = __builtin_fmaf(x, (float)q23[1], s[3]);
+    }
+}
+// the words of blocks A and B at one position: eight table reads, then 32 products
+__device__ __forceinline__ void key_row_step(const KeyRowWord& ra, const KeyRowWord& rb, const unsigned char* qtab, float (&sA)[4], float (&sB)[4])
+{
+    uint2 qa[4], qb[4];
+    key_row_q(ra.ch, qtab, qa);
+    key_row_q(rb.ch, qtab, qb);
+    key_row_fma(ra, qa, sA);
+    key_row_fma(rb, qb, sB);
+}
+// A wave's share of a block: words [first, first + count) of its nword; half: the position (counted from `first`) of the block's half
+// word if it is among them, else -1.  The even wave takes the first half of the words, the odd wave the rest; a half word goes to the
+// odd wave and counts as nothing when the words are halved, so that the two shares differ by half a word at most.
+struct KeyRowShare {
+    int nword, first, count, half;
+};
+__device__ __forceinline__ KeyRowShare key_row_share(uint32_t ent, int odd, bool active)
+{
+    const int w = ent & 0xffu, nword = (w + 3) >> 2;
+    const bool tail = (w & 3) != 0;   // (w is even: w % 4 == 2)
+    const int h = nword == 1 ? 1 : tail ? nword >> 1 : (nword + 1) >> 1;
+    KeyRowShare s;
+    s.nword = nword;
+    s.first = odd ? h : 0;
+    s.count = active ? (odd ? nword - h : h) : 0;
+    s.half = tail && s.count > 0 && s.first + s.count == nword ? s.count - 1 : -1;
+    return s;
+}
+// rows: the head's rows; entA / entB: the table entries of the two blocks (first row << 8 | w); mid: called behind the first requests
+template <class MID>
+__device__ __forceinline__ void key_rows_phase(const unsigned char* __restrict__ rows, uint32_t entA, uint32_t entB, bool actB, int odd, int lane,
+                                               const unsigned char* qtab, float (&sA)[4], float (&sB)[4], const MID& mid)
+{
+    const int lane4 = lane * 4;
+    const KeyRowShare A = key_row_share(entA, odd, true), B = key_row_share(entB, odd, actB);
+    const __amdgpu_buffer_rsrc_t blkA = key_row_block(rows, entA), blkB = key_row_block(rows, entB);
+    auto request = [&](__amdgpu_buffer_rsrc_t blk, const KeyRowShare& S, int i) {   // word i of the share, or nothing beyond it
+        KeyRowWord r{0u, 0u, 0u};
+        if (i < S.count) {
+            if (i == S.half) r = key_row_word<true>(blk, S.nword, S.first + i, lane4);
+            else             r = key_row_word(blk, S.nword, S.first + i, lane4);
+        }
+        return r;
+    };
+    KeyRowWord ra = request(blkA, A, 0), rb = request(blkB, B, 0);
+    mid();
+    // whole words both blocks have: two positions per trip on two sets of registers, no condition inside
+    const int fullA = A.count - (A.half >= 0), fullB = B.count - (B.half >= 0), both = fullA < fullB ? fullA : fullB;
+    const int n = A.count > B.count ? A.count : B.count;
+    int i = 0;
+#pragma unroll 1
+    for (; i + 2 < both; i += 2) {
+        const KeyRowWord na = key_row_word(blkA, A.nword, A.first + i + 1, lane4), nb = key_row_word(blkB, B.nword, B.first + i + 1, lane4);
+        key_row_step(ra, rb, qtab, sA, sB);
+        ra = key_row_word(blkA, A.nword, A.first + i + 2, lane4);
+        rb = key_row_word(blkB, B.nword, B.first + i + 2, lane4);
+        key_row_step(na, nb, qtab, sA, sB);
+    }
+    // the last positions: a block may have a word more than the other, end in a half word, or be absent
+#pragma unroll 1
+    for (; i < n; i++) {
+        const KeyRowWord na = request(blkA, A, i + 1), nb = request(blkB, B, i + 1);
+        uint2 q[4];
+        if (i < A.count) {
+            if (i == A.half) { key_row_q<2>(ra.ch, qtab, q); key_row_fma<2>(ra, q, sA); }
+            else             { key_row_q(ra.ch, qtab, q); key_row_fma(ra, q, sA); }
+        }
+        if (i < B.count) {
+            if (i == B.half) { key_row_q<2>(rb.ch, qtab, q); key_row_fma<2>(rb, q, sB); }
+            else             { key_row_q(rb.ch, qtab, q); key_row_fma(rb, q, sB); }
+        }
+        ra = na;
+        rb = nb;
+    }
+}
+
 template <int ENG, bool EXT = false, int G = 4, bool MASK = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
                                                                      // decode_onepass_leanpair_kernel; round 5 carried an uninstantiated online form here -- removed in round 6)
 __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
@@ -2688,6 +2816,10 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         vi = v_idx + (int64_t)kvh * (v_idx_stride ? v_idx_stride : tiles + 1);
         vn = v_nz + 16ull * (v_nz_stride ? (uint64_t)kvh * v_nz_stride : (uint64_t)v_nz_off[kvh]);
     }
+    // round 7: the key base as token rows (GQA-4, vector engines; workgroup-uniform: the workgroups of an appended extent read tiles)
+    constexpr bool ROWS = G == 4 && ENG != 1;
+    const bool rows = ROWS && a.key_rows && !(EXT && tb0 >= a.nb0);
+    const uint32_t* ktab = k_idx + (int64_t)kvh * k_idx_stride;   // (rows: the head's block table)
     // ---- one body for both waves of a pair: the odd wave's half (tiles 64..127 of every block; channels 64..127 of the q rows) is a bias
     kb += odd * 64;
     ki += odd * 64;
@@ -2731,6 +2863,19 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     for (int h = 0; h < G; h++) acc[h] = 0.f;
 #pragma unroll
     for (int j = 0; j < HW; j++) { m_run[j] = -INFINITY; l_lane[j] = 0.f; }
+    // rows: the q table of the key phase, [128 channels][4 heads] fp16, behind the partial scores in the FIRST wave's stage window: a fixed
+    // address, dead until that wave's value phase, which starts behind the barriers that end every wave's key phase.  Every wave writes
+    // the whole table -- the same bytes -- before it reads it: no barrier.  Lane l holds channels 2 l, 2 l + 1 of the four heads.
+    const unsigned char* qtab = smem + 2 * 64 * G * 4;
+    if constexpr (ROWS) {
+        if (rows) {
+            const uint32_t* q32 = reinterpret_cast<const uint32_t*>(a.q + (int64_t)bh0 * kD) + lane;
+            const uint32_t q0 = q32[0], q1 = q32[64], q2 = q32[128], q3 = q32[192];
+            *reinterpret_cast<uint4*>(smem + 2 * 64 * G * 4 + lane * 16) =
+                make_uint4((q0 & 0xffffu) | (q1 << 16), (q2 & 0xffffu) | (q3 << 16), (q0 >> 16) | (q1 & 0xffff0000u), (q2 >> 16) | (q3 & 0xffff0000u));
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
     const bool late_round = (int)(blockIdx.y * gridDim.x + blockIdx.x) >= a.hi_prio_from;   // (workgroup-uniform)
     if (late_round) __builtin_amdgcn_s_setprio(3);
     else __builtin_amdgcn_s_setprio(1);
@@ -2757,7 +2902,23 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         // What a phase needs from memory before its stream -- its three chunk bounds and its metadata lines in L2 -- is requested in
         // front of the LAST chunk of the phase before it (~2-3 us ahead: sooner and the lines are gone from L2 again by the time the
         // scalar loads come for them, later and the phase starts with two dependent round trips)
+        auto reqVA = [&]() {   // the value side's bounds (both blocks: they are consumed as one pipeline) and block A's metadata lines
+            bndV = ld_at(viA, off_bnd);
+            if (actB && lanesB) bndV = ld_at(viA + kTilesPerTb, off_bnd);
+            pfVA = ld_at(vbA, off_bmp);
+        };
         if (actA) {
+          if (ROWS && rows) {   // token rows: no bounds, no metadata lines; the value side's are requested behind the first two words
+            if constexpr (ROWS) {
+                if constexpr (MASK) {
+                    mkA = mrow[tAc * 64 + lane];
+                    if (actB) mkB = mrow[tBc * 64 + lane];
+                }
+                // (readfirstlane: the entries are wave-uniform, and the phase builds buffer resources -- scalar registers -- from them)
+                const uint32_t entA = __builtin_amdgcn_readfirstlane(ktab[tAc]), entB = __builtin_amdgcn_readfirstlane(ktab[tBc]);
+                key_rows_phase(kn, entA, entB, actB, odd, lane, qtab, sA, sB, reqVA);
+            }
+          } else {
             const uint64_t* kbA = kb + (int64_t)tAc * kTilesPerTb;
             const uint32_t* kiA = ki + (int64_t)tAc * kTilesPerTb;
             uint32_t bndK = ld_at(kiA, off_bnd);
@@ -2766,11 +2927,6 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                 mkA = mrow[tAc * 64 + lane];
                 if (actB) mkB = mrow[tBc * 64 + lane];
             }
-            auto reqVA = [&]() {   // the value side's bounds (both blocks: they are consumed as one pipeline) and block A's metadata lines
-                bndV = ld_at(viA, off_bnd);
-                if (actB && lanesB) bndV = ld_at(viA + kTilesPerTb, off_bnd);
-                pfVA = ld_at(vbA, off_bmp);
-            };
             if (actB) {
                 // both blocks as one pipeline of four chunks: B's bounds are needed while A's last chunk is worked on -- they come with A's
                 // (four bytes per lane); B's metadata lines are requested in front of A's last chunk
@@ -2784,6 +2940,7 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                 lean_block_phase<ENG, kD * 2, false, 0, 2, G, const void*, 0>(lds, lds_addr, kbA, kiA, kn, qb, bndK, lane, sA, sA MUSTAFAR_PTRACE_ARG, ctab_q, reqVA);
                 prefetch_done(pfKA);
             }
+          }
             fvG oA, oB;
             if constexpr (G == 1) { oA = sA[0]; oB = sB[0]; }
             else {
@@ -3778,6 +3935,12 @@ inline bool onepass_shape(OnePassShape& s, int T, int gy, int window_capacity, b
     return true;
 }
 
+// Whether the launch of shape `s` reads a key base of token rows: the super-block kernel's GQA-4 instantiations on the two vector engines, at
+// FOUR blocks per workgroup.  With two (under 768 workgroups: Llama-3-8B 8k x batch 1) a pair of waves holds ONE block, a wave walks that
+// block's words alone -- half the independent work per step -- at two waves per SIMD, and the launch measured 3.4 % SLOWER on rows than on
+// tiles (0.549 vs 0.531 ms per step, kernel 11.8 vs 11.4 us: profiles/r07_key_rows.txt), so that shape keeps tiles.
+inline bool onepass_reads_key_rows(const OnePassShape& s, int G, int eng) { return s.form == kFormSb && s.per_wg == 4 && G == 4 && eng != 1; }
+
 // The three one-pass kernels take the same arguments.  onepass_select names every instantiation the dispatcher can reach.
 using OnePassKernel = void (*)(const uint64_t*, const unsigned char*, const uint32_t*, const uint32_t*, const uint64_t*, const unsigned char*,
                                const uint32_t*, const uint32_t*, OneArgs, int64_t, int64_t, uint32_t, int64_t, int64_t, uint32_t);
@@ -3826,7 +3989,7 @@ void launch_finish(hipStream_t st, hipEvent_t f0, hipEvent_t f1, const float* ws
 
 extern "C" {
 
-int mustafar_abi_version(void) { return 112; }   // 112: mustafar_decode_multi_query, mustafar_decode_multi_query_workspace_bytes (multi_query.hip: several query tokens of every sequence per call); 111: mustafar_decode_shared_segment, mustafar_shared_segment_workspace_bytes (shared_segment.hip: one compressed copy of a shared prefix decoded for a whole batch); 110: mustafar_decode_attention_lse_hd, mustafar_decode_attention_extents_lse_hd, mustafar_merge_attention_states (the LSE of a fused decode, window-less calls, the merge of partial attention states); 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
+int mustafar_abi_version(void) { return 113; }   // 113: mustafar_cache_view::flags, MUSTAFAR_VIEW_KEY_ROWS, mustafar_key_rows_plan / _fill / _to_tiles (key_rows.hip), mustafar_decode_reads_key_rows (token-row key blocks for the GQA-4 one-pass key phase); 112: mustafar_decode_multi_query, mustafar_decode_multi_query_workspace_bytes (multi_query.hip: several query tokens of every sequence per call); 111: mustafar_decode_shared_segment, mustafar_shared_segment_workspace_bytes (shared_segment.hip: one compressed copy of a shared prefix decoded for a whole batch); 110: mustafar_decode_attention_lse_hd, mustafar_decode_attention_extents_lse_hd, mustafar_merge_attention_states (the LSE of a fused decode, window-less calls, the merge of partial attention states); 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
 
 int Key_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const void* NZ, const uint32_t* idx,
                    const uint32_t* NZ_offset, const void* B, void* C, int M_Global, int N_Global, int K_Global,
@@ -3946,9 +4109,14 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
     // an LSE comes from the one-pass forms' row kernels, and appended extents are read by the one-pass launch only: a call that would
     // run two launches is refused before anything is launched
     if ((c.lse || no_window || extents) && !onepass) return MUSTAFAR_EINVAL;
-    if (c.T > 0 && (!c.k.bmp || !c.k.nz || !c.k.idx || !c.k.nz_offset || !c.v.bmp || !c.v.nz || !c.v.idx || !c.v.nz_offset)) return MUSTAFAR_EINVAL;
+    // a key base of token rows (MUSTAFAR_VIEW_KEY_ROWS): read by the super-block launch alone (checked where the shape is known); the value
+    // side has no such form, and no other flag exists
+    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS;
+    if ((c.k.flags && !key_rows) || c.v.flags || (key_rows && (!onepass || c.T <= 0))) return MUSTAFAR_EINVAL;
+    if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || !c.v.bmp || !c.v.nz || !c.v.idx || !c.v.nz_offset)) return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
-    if (c.T > 0 && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1) ||
+    if (key_rows && (c.k.idx_head_stride < tiles / 128 || c.k.nz_head_stride <= 0 || (c.k.nz_head_stride & 15) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    if (c.T > 0 && ((!key_rows && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1))) ||
                     (c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))
         return MUSTAFAR_EINVAL;
     hipStream_t st = c.stream;
@@ -3971,10 +4139,12 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
         const int eng = G == 4 ? fma_engine() : 0;
         OnePassShape s;
         if (!onepass_shape(s, c.T, gy, c.window_capacity, extents, eng, onepass_knobs())) return MUSTAFAR_EINVAL;
+        if (key_rows && !onepass_reads_key_rows(s, G, eng)) return MUSTAFAR_EINVAL;
         float* ws_ml = ws + (int64_t)(s.NS + s.nchunks) * c.Batch_Size * kD;
         OneArgs a{qh, sc, ws, ws_ml, kwin, vwin, knew, vnew, c.window_len_extra, mask, c.T, c.groups, c.Batch_Size, s.per_wg,
                   c.ld_scores, c.window_len, c.window_capacity, s.nchunks, s.win_rows, inv_sqrt_d, s.spw == 2};
         a.hi_prio_from = s.hi_prio_from;
+        a.key_rows = key_rows;
         if (extents) {
             a.k_ext = c.k_ext;
             a.v_ext = c.v_ext;
@@ -4271,6 +4441,20 @@ int mustafar_decode_reads_extents(int num_key_value_groups, int ld_scores, uint3
     if (!onepass_slabs_fit(ld_scores / 64, 4, 1, kMaxWindow / kOneWinChunk)) return 0;
     return num_key_value_groups >= 1 && (ld_scores & 31) == 0 && onepass_wgs() <= 0 &&   // (MUSTAFAR_ONEPASS_WGS changes the shape rule)
            (onepass_lean_tbw() == 0 || onepass_lean_tbw() == 1 || onepass_lean_tbw() == 2);
+}
+
+int mustafar_decode_reads_key_rows(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
+{
+    uint32_t f_eng, f_str;
+    if (!parse_flags(flags, &f_eng, &f_str)) return 0;
+    if (f_str == 1u || (f_str == 0u && onepass_mode() == 0)) return 0;   // two launches asked for (by the call or by the process default)
+    if (num_key_value_groups < 1 || T <= 0 || (T & 63) || gy < 1 || (ld_scores & 31)) return 0;
+    const int G = pick_g(num_key_value_groups);
+    const int eng = G == 4 ? (f_eng == 1 ? 0 : f_eng == 2 ? 1 : f_eng == 3 ? 2 : fma_engine()) : 0;   // (the call's own engine, else the default)
+    OnePassShape s;
+    // (the largest window stands in for the call's own, as in mustafar_decode_reads_extents: it only matters where slabs run short)
+    if (!onepass_shape(s, T, gy, kMaxWindow, false, eng, onepass_knobs())) return 0;
+    return onepass_reads_key_rows(s, G, eng) ? 1 : 0;
 }
 
 int mustafar_profile_begin(int max_records)

@@ -83,6 +83,10 @@ class MustafarConfig:
     # one process run what each of them asks for.
     engine: Optional[str] = None
     structure: Optional[str] = None
+    # arena, head_dim 128, GQA groups % 4 == 0, engine "valu" or "dot2": to_fused() retiles the key BASE of an arena into token rows
+    # (cache.CompressedArena.to_key_rows) where the launch of the call shape reads them (mustafar_decode_reads_key_rows: the one-pass
+    # super-block form).  Whatever needs tiles retiles back (CompressedArena.require_tiles).  MUSTAFAR_KEY_ROWS=0 turns it off everywhere
+    key_rows: bool = True
     # head_dim 64, api="fused", arena=False only: the compressed cache grows by 256-token extents (cache64.py) instead of being
     # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
     hd64_extents: bool = False
@@ -312,6 +316,19 @@ class MustafarAttention:
         window capacity)."""
         return bool(_lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, _ld_scores(columns), self._flags()))
 
+    def _reads_key_rows(self, k_c, T: int, ld: int, flags: Optional[int] = None) -> bool:
+        """Whether the launch of a fused call sized for `T` compressed tokens, with scores of pitch `ld`, reads the key base of arena
+        `k_c` as token rows."""
+        groups = self.num_key_value_groups
+        if self.head_dim != 128 or groups % 4:
+            return False
+        return bool(_lib.load().mustafar_decode_reads_key_rows(groups, T, k_c.heads * (groups // 4), ld, self._flags() if flags is None else flags))
+
+    def _wants_key_rows(self) -> bool:
+        cfg = self.cfg
+        return cfg.key_rows and os.environ.get("MUSTAFAR_KEY_ROWS", "1") != "0" and cfg.head_dim == 128 and \
+            self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
+
     def _kth(self, D: int) -> Tuple[int, int]:
         """`(kth_k, kth_v)`: the prune rule's kth (model :97) for K and V rows of D channels at the configured sparsities."""
         return compression.kth_from_sparsity(self.cfg.k_sparsity, D), compression.kth_from_sparsity(self.cfg.v_sparsity, D)
@@ -384,6 +401,12 @@ class MustafarAttention:
         if not isinstance(k_w, Window):
             cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
             k_w, v_w = Window(k_w, cap), Window(v_w, cap)
+        if isinstance(k_c, CompressedArena) and not k_c.key_rows and not k_c.keep_tiles and self._wants_key_rows() and \
+                not torch.cuda.is_current_stream_capturing():
+            # the ONE place that retiles a key base into token rows: where the launch of this cache's call shape reads them
+            T = k_c.total_tokens
+            if T and self._reads_key_rows(k_c, T, _ld_scores(T + k_w.cap)):
+                k_c.to_key_rows()
         return Past(k_c, k_w, v_c, v_w, C, L)
 
     @staticmethod
@@ -543,6 +566,8 @@ class MustafarAttention:
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()   # (T == their base tokens now: the view form)
                 k_c.ext_table, v_c.ext_table
                 past = past._replace(k_cache=k_c, v_cache=v_c)
+            if k_c.key_rows and not self._reads_key_rows(k_c, T, ops.ld, ops.flags):
+                k_c.require_tiles()   # (raises under capture: the launch form of this call reads tiles)
         _call_decode(k_c, v_c, T, ops, D, t_device, lse)
         out = ops.out
         if step_counter is not None:
@@ -734,6 +759,8 @@ class MustafarAttention:
         # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
         ops = self._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
         lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
+        if isinstance(k, CompressedArena) and k.key_rows and not self._reads_key_rows(k, tokens, ops.ld, ops.flags):
+            k.require_tiles()   # (a key base in token rows and a launch form that reads tiles)
         _call_decode(k, v, tokens, ops, D, None, lse)
         return ops.out, lse
 
