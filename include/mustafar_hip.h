@@ -526,7 +526,8 @@ int mustafar_decode_shared_segment(void* stream, const mustafar_cache_view* k_ca
  *   MUSTAFAR_EINVAL before any launch for: n_q < 1, n_q * num_key_value_groups > 64, num_key_value_groups outside 1..8, head_dim not 64 or
  *   128, Bp outside 1..65535, T < 0 or T % 64 != 0, the T_base / extent rules above, window_len < n_q, window_len > window_capacity,
  *   window_capacity > 1024, exactly one of k_new / v_new NULL, NULL or misaligned q / out / windows / new rows / workspace / lse, a base
- *   view mustafar_decode_shared_segment would refuse.  No mask, no device-side lengths (window_len_extra, T_device) in this version.
+ *   view mustafar_decode_shared_segment would refuse.  No device-side lengths (window_len_extra, T_device) in this version; the mask
+ *   comes with mustafar_decode_multi_query_masked (ABI 114, below), of which this call is the form with mask == NULL.
  *   Nothing is allocated and nothing is read back: the call can be captured in a hipGraph at fixed lengths.
  * mustafar_decode_multi_query_workspace_bytes: (ceil(T / 64 / bpw) + ceil(window_capacity / 64)) * Bp * R * (head_dim + 2) * 4, with
  *   bpw = ceil(8 R (head_dim + 2) / (88 head_dim)) blocks per run, the rule of mustafar_shared_segment_workspace_bytes.  0 for the
@@ -538,6 +539,44 @@ int mustafar_decode_multi_query(void* stream, const mustafar_cache_view* k_base,
                                 int T, int Bp, int num_key_value_groups, int n_q,
                                 const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
                                 int window_len, int window_capacity, void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
+
+/*
+ * Attention masks and draft trees in the several-token call (ABI 114; multi_query.hip).
+ *
+ * mustafar_decode_multi_query_masked: mustafar_decode_multi_query (its 22 arguments first, in the same order, same workspace) with an additive
+ *   fp16 mask.  For head b of B', query token j and column c -- c = t for compressed token t, c = T + w for window row w -- a column the
+ *   causal limit lets the token see counts as x' = max(fp16(x + m), finfo(fp16).min), m = mask[(b / heads_per_mask) * mask_batch_stride +
+ *   (mask_rows == 1 ? 0 : j) * mask_row_stride + c]: ONE fp16 addition, so m = -inf gives finfo.min -- the hook's rule, as in every fused
+ *   entry point.  The causal limit stays on top: a column beyond window_len - n_q + j is not seen whatever the mask says (and its mask value
+ *   is not read), so a mask only takes columns away; columns at or beyond T + window_len are never read.  A row whose every visible column
+ *   is masked to finfo.min returns what the clamp implies (about the mean of the visible V rows), finite.
+ *   mask                fp16, DEVICE, any 2-byte aligned address (a column slice of a wider tensor); strides in halfs.  NULL: exactly the
+ *                       launches of mustafar_decode_multi_query (the other mask arguments are not looked at)
+ *   mask_rows           1 (one row for all n_q tokens) or n_q
+ *   heads_per_mask      consecutive B' heads that share a mask plane (kv_heads for one plane per sequence); 1..Bp, a divisor of Bp
+ *   MUSTAFAR_EINVAL before any launch, beyond the cases of mustafar_decode_multi_query: mask at an odd address, mask_rows outside {1, n_q},
+ *   heads_per_mask out of range or no divisor of Bp, mask_row_stride < T + window_len with mask_rows > 1, mask_batch_stride < T + window_len
+ *   with Bp / heads_per_mask > 1, a negative stride.
+ *
+ * mustafar_window_keep_rows: for every head and both windows [Bp, window_capacity, head_dim], row row0 + i <- row row0 + keep[seq][i] for
+ *   i < n_keep, seq = head / heads_per_seq: the rows of an accepted path of a draft tree moved to the front of the n_rows rows the call
+ *   appended.  One launch, one workgroup per (head, window): every source row is read before the first is written, so any index order and
+ *   duplicates are safe; an index outside [0, n_rows) is clamped into it (a wrong row, never a wild address).  Rows outside
+ *   [row0, row0 + n_keep) are left bit for bit as they are.
+ *   keep                int32, DEVICE, [Bp / heads_per_seq][n_keep], 4-byte aligned
+ *   MUSTAFAR_EINVAL for: n_keep outside 1..n_rows, n_rows outside 1..64, row0 < 0 or row0 + n_rows > window_capacity, window_capacity > 1024,
+ *   head_dim not 64 or 128, NULL or misaligned (16 B) windows, a NULL or misaligned (4 B) keep, Bp outside 1..65535, heads_per_seq < 1 or
+ *   no divisor of Bp.
+ * Neither call allocates or reads anything back: both can be captured in a hipGraph at fixed lengths.
+ */
+int mustafar_decode_multi_query_masked(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                       const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                       int T, int Bp, int num_key_value_groups, int n_q,
+                                       const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                       int window_len, int window_capacity, void* out, float* lse, void* workspace, float sqrt_d, int head_dim,
+                                       const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask);
+int mustafar_window_keep_rows(void* stream, void* k_window, void* v_window, int Bp, int heads_per_seq, int window_capacity, int head_dim,
+                              int row0, int n_rows, const int32_t* keep, int n_keep);
 
 /*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must

@@ -1,5 +1,6 @@
 // multi_query.hip -- several query tokens of every sequence per fused decode call, head_dim 64 and 128, for gfx950.  The C ABI entry points
-// mustafar_decode_multi_query and mustafar_decode_multi_query_workspace_bytes (include/mustafar_hip.h, ABI 112).
+// mustafar_decode_multi_query, mustafar_decode_multi_query_masked, mustafar_decode_multi_query_workspace_bytes and
+// mustafar_window_keep_rows (include/mustafar_hip.h, ABI 112 and 114).
 //
 // A caller that verifies n_q drafted tokens, or feeds a short follow-up turn, would issue n_q decode steps, each re-reading the whole
 // compressed cache and paying the per-tile cost of the format -- bitmap, rank, address, select -- again.  The n_q tokens of one sequence are
@@ -20,11 +21,20 @@
 //                    is requested ahead (the next block's metadata and key stream) follows the resolution of the NEXT block
 //   window chunk     64 rows of the dense window: the key image [token][channel] is filled straight from the rows of k_window as 16-byte
 //                    pieces, the value image [channel][token] is the transpose of the rows of v_window; scores, softmax step and out as for
-//                    a compressed block.  The causal limit is the only mask: window row w is visible to query token j iff
+//                    a compressed block.  The causal limit: window row w is visible to query token j iff
 //                    w <= window_len - n_q + j.  An invisible column counts as x = -inf, e = 0; a row that sees no column of its chunk
 //                    stays at M = -inf, L = 0 (a slab of weight zero).  Image rows at or beyond window_len are written as zeros
 //                    (0 x garbage through the matrix pipe is NaN where the garbage is Inf or NaN).  Chunks at or beyond
 //                    ceil(window_len / 64) leave slabs of weight zero
+//   MASK             an additive fp16 mask, one row per query token or one for all, one plane per `heads_per_mask` consecutive heads: column
+//                    64 tb + t of a compressed block (tb the GLOBAL block number), T + w of window row w.  A softmax thread owns 16
+//                    consecutive columns of one row: it asks for their mask values early -- behind the key expand of a compressed block,
+//                    ahead of the image fill of a window chunk -- and holds them packed.  x' = max(fp16(x + m), finfo(fp16).min), ONE fp16
+//                    addition, the hook's rule; the causal limit stays on top (an invisible column is -inf whatever the mask says, and
+//                    its mask value is not read), so a mask only takes columns away.  Columns at or beyond T + window_len are never
+//                    read.  The unmasked instantiations take MqArgs alone and are the code they were
+// window_keep_kernel          rows row0 + i <- row0 + keep[seq][i] of both windows of every head (accept(keep=) after a draft tree): the source
+//                             rows go through LDS and a barrier before the first store, so any order and duplicates are safe
 // shared_merge_kernel         (expand_block.h) folds a row's slabs -- compressed runs first, then window chunks -- into out and lse
 // Products are fp16 x fp16, exact in fp32; sums are fp32.  No inline assembly.
 
@@ -99,12 +109,24 @@ __device__ __forceinline__ void expand_values(const TileMeta& vm, uint32_t v0, c
 // sum folded over the quad.  Rows of zero queries (at or beyond R) go through it like any other: x = 0, finite everywhere.
 // LIMIT: columns at or beyond `visible` (0..64, the row's own) count as x = -inf, e = 0; a row that sees no column at all, in this block and
 // before it, stays at M = -inf, L = 0 with alpha = 1 (exp(-inf - -inf) would be NaN).
-template <int RT, bool LIMIT>
-__device__ __forceinline__ void softmax_rows(h16* s_xe, float* s_alpha, float& M, float& L, int srow, int sq, int visible)
+// MASK: x' = max(fp16(x + m), finfo(fp16).min) on the thread's 16 columns first -- packed fp16 additions, each rounded once; m = -inf gives
+// finfo.min -- and the limit on top of it.
+struct MaskRegs {
+    h16x8 a, b;   // the mask values of the thread's 16 columns
+};
+template <int RT, bool LIMIT, bool MASK = false>
+__device__ __forceinline__ void softmax_rows(h16* s_xe, float* s_alpha, float& M, float& L, int srow, int sq, int visible,
+                                             const MaskRegs& mk = MaskRegs{})
 {
     if (srow < RT * 16) {
         h16x8* px = reinterpret_cast<h16x8*>(s_xe + srow * kRowPad + sq * 16);
-        const h16x8 xa = px[0], xb = px[1];
+        h16x8 xa = px[0], xb = px[1];
+        if constexpr (MASK) {
+            const h16 lowest = (h16)-65504.f;
+            const h16x8 lo = h16x8{lowest, lowest, lowest, lowest, lowest, lowest, lowest, lowest};
+            xa = __builtin_elementwise_max(xa + mk.a, lo);
+            xb = __builtin_elementwise_max(xb + mk.b, lo);
+        }
         float x[16];
 #pragma unroll
         for (int j = 0; j < 8; j++) { x[j] = (float)xa[j]; x[8 + j] = (float)xb[j]; }
@@ -218,6 +240,49 @@ struct MqArgs {
     float inv_sqrt_d;
 };
 
+// MASK: the kernel's argument is MqArgs followed by the mask (the unmasked instantiations keep MqArgs as it is).
+struct MqMaskArgs : MqArgs {
+    const h16* mask;                     // additive fp16, 2-byte aligned
+    int64_t mask_batch_stride;           // halfs between the planes of two groups of `heads_per_mask` heads
+    int64_t mask_row_stride;             // halfs between the rows of two query tokens (mask_rows == n_q)
+    int mask_rows, heads_per_mask;
+};
+template <bool MASK>
+struct MqKernelArgs { typedef MqArgs type; };
+template <>
+struct MqKernelArgs<true> { typedef MqMaskArgs type; };
+
+// The mask values of a thread's 16 columns, packed as they lie in memory.  The base and the strides of a mask are 2-byte aligned only:
+// these are loads of 4 and 16 bytes at 2-byte alignment, which global memory serves (no 2-byte loads, which would take a register each
+// until they are packed).
+struct __attribute__((packed, aligned(2))) MaskPair { uint32_t v; };
+struct __attribute__((packed, aligned(2))) MaskOctet { uint32_t v[4]; };
+__device__ __forceinline__ MaskRegs load_mask16(const h16* p)
+{
+    const MaskOctet lo = *reinterpret_cast<const MaskOctet*>(p), hi = *reinterpret_cast<const MaskOctet*>(p + 8);
+    MaskRegs mk;
+    mk.a = __builtin_bit_cast(h16x8, lo);
+    mk.b = __builtin_bit_cast(h16x8, hi);
+    return mk;
+}
+// The first `n` (0..16) of them; the others are 0, belong to columns the row does not see, and are not read: whole pairs as 4 bytes, the
+// last value of an odd n as 2 bytes.
+__device__ __forceinline__ MaskRegs load_mask(const h16* p, int n)
+{
+    if (n == 16) return load_mask16(p);
+    const uint32_t last = (n & 1) ? (uint32_t)reinterpret_cast<const uint16_t*>(p)[n - 1] : 0u;
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        w[k] = 2 * k == n - 1 ? last : 0u;
+        if (2 * k + 1 < n) w[k] = reinterpret_cast<const MaskPair*>(p + 2 * k)->v;
+    }
+    MaskRegs mk;
+    mk.a = __builtin_bit_cast(h16x8, MaskOctet{{w[0], w[1], w[2], w[3]}});
+    mk.b = __builtin_bit_cast(h16x8, MaskOctet{{w[4], w[5], w[6], w[7]}});
+    return mk;
+}
+
 // Block tb of one side: from the head's rows of the base view, or (EXT) from the table behind them.
 template <int TILES, bool EXT>
 __device__ __forceinline__ BlockRef block_of(const uint64_t* bmp_h, const uint32_t* idx_h, const uint4* nz_h, const mustafar_cache_view* ext,
@@ -232,8 +297,8 @@ __device__ __forceinline__ BlockRef block_of(const uint64_t* bmp_h, const uint32
     return BlockRef{bmp_h + (int64_t)tb * TILES, idx_h + (int64_t)tb * TILES, nz_h};
 }
 
-template <int D, int RT, bool EXT>
-__global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
+template <int D, int RT, bool EXT, bool MASK>
+__global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename MqKernelArgs<MASK>::type a)
 {
     constexpr int TILES = D;                 // tiles of a 64-token block on either side (D / 64 per token)
     constexpr int KS = D / 32;               // k-steps of the score product
@@ -274,6 +339,13 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
     // softmax state of row tid >> 2 (the four lanes of a quad hold the same values; rows at or beyond 16 RT do not exist)
     const int srow = tid >> 2, sq = tid & 3;
     float M = -INFINITY, L = 0.f;
+    // MASK: the row of this thread's softmax row (query token srow % n_q; rows at or beyond R read the row of a token that exists), and
+    // whether the thread has a softmax row at all
+    const h16* mrow = nullptr;
+    const bool m_on = srow < RT * 16;
+    if constexpr (MASK)
+        mrow = a.mask + (int64_t)(bkv / a.heads_per_mask) * a.mask_batch_stride +
+               (a.mask_rows == 1 ? 0 : (int64_t)(srow % a.n_q) * a.mask_row_stride) + sq * 16;
 
     if (x < a.runs) {
         // ---- compressed blocks [tb0, tb1) of this head
@@ -299,6 +371,7 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
         __syncthreads();
         for (int tb = tb0; tb < tb1; tb++) {
             // requested now, used later: this block's value stream, the next block's bitmaps and offsets -- of the next block as resolved
+            MaskRegs mk{};
             load_block<TILES>(vc.nz, (cu32_p)vc.idx, tid, vg);
             const int tn = min(tb + 1, tb1 - 1);
             const BlockRef kn = block_of<TILES, EXT>(kb_h, ki_h, kz, a.k_ext, a.ntb_base, bkv, tn);
@@ -306,13 +379,17 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
             const TileMeta km_next = load_meta(kn.bmp, kn.idx, k_tile, meta_on);
             const TileMeta vm_next = load_meta(vn.bmp, vn.idx, v_tile, meta_on);
             expand_keys<D>(km, k0, sb, s_img, lane, wave);
+            // MASK: the 16 mask values of the softmax step, requested here: behind them lie two barriers, the scores and the value expand.
+            // (Requested in front of the key expand they are live across its 16 packing registers: 7 VGPRs more, and D = 128 at two row
+            // tiles drops from three waves per SIMD to two: 104 -> 130 us at n_q = 8)  tb: the global block number
+            if constexpr (MASK) { if (m_on) mk = load_mask16(mrow + (int64_t)tb * 64); }
             __syncthreads();   // the key image is whole, the key stream is read
             store_block<TILES>(vg, s_stream, tid);
             score_tiles<D, RT>(qf, s_img, s_xe, a.inv_sqrt_d, wave, l15, l4);
             __syncthreads();   // x is whole, the key image is read, the value stream is staged
             if (tb + 1 < tb1) load_block<TILES>(kn.nz, (cu32_p)kn.idx, tid, kg);   // (requested now, stored behind the softmax)
             expand_values<D>(vm, vg.i0, sb, s_img, lane, wave);
-            softmax_rows<RT, false>(s_xe, s_alpha, M, L, srow, sq, 64);
+            softmax_rows<RT, false, MASK>(s_xe, s_alpha, M, L, srow, sq, 64, mk);
             __syncthreads();   // e, alpha and the value image are whole, the value stream is read
             if (tb + 1 < tb1) {
                 store_block<TILES>(kg, s_stream, tid);
@@ -329,6 +406,10 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
         // ---- window chunk: rows [w0, w0 + 64) of this head's dense window (a chunk beyond the window leaves its slabs at weight zero)
         const int w0 = (x - a.runs) * 64, w_len = a.w_len;
         if (w0 < w_len) {
+            MaskRegs mk{};
+            if constexpr (MASK)   // the causally visible ones of the thread's 16 columns (below): none at or beyond T + w_len
+                mk = load_mask(mrow + (int64_t)a.ntb * 64 + w0,
+                               m_on ? min(16, max(0, w_len - a.n_q + srow % a.n_q + 1 - w0 - sq * 16)) : 0);
             const h16* kw = a.k_win + (int64_t)bkv * a.w_cap * D;
             const h16* vw = a.v_win + (int64_t)bkv * a.w_cap * D;
             // value rows, requested first and held: item = (token pair u, 8-channel piece pc), 32 x D / 8 items over 256 threads
@@ -367,7 +448,7 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(MqArgs a)
                 put(va[k].w, vb[k].w, 6);
             }
             // the causal limit: query token j = row % n_q sees window rows [0, w_len - n_q + j], `visible` of them in this chunk
-            softmax_rows<RT, true>(s_xe, s_alpha, M, L, srow, sq, w_len - a.n_q + srow % a.n_q + 1 - w0);
+            softmax_rows<RT, true, MASK>(s_xe, s_alpha, M, L, srow, sq, w_len - a.n_q + srow % a.n_q + 1 - w0, mk);
             __syncthreads();   // e, alpha and the value image are whole
             accumulate_out<D, RT>(o, s_img, s_xe, s_alpha, wave, l15, l4);
         }
@@ -388,6 +469,28 @@ __global__ __launch_bounds__(kThreads) void multi_query_append_kernel(const uint
     dst[((int64_t)b * w_cap + row0 + j) * D8 + pc] = src[i];
 }
 
+// Rows [row0, row0 + n_keep) of one head's K or V window <- rows row0 + keep[seq][i], keep clamped to [0, n_rows): grid (B', 2), thread =
+// 16-byte pieces.  Every source row is in LDS before the first store (the barrier), so the index order and duplicates do not matter.
+template <int D>
+__global__ __launch_bounds__(kThreads) void window_keep_kernel(uint4* __restrict__ k_win, uint4* __restrict__ v_win,
+                                                               const int32_t* __restrict__ keep, int heads_per_seq, int w_cap, int row0,
+                                                               int n_rows, int n_keep)
+{
+    constexpr int D8 = D / 8;
+    __shared__ uint4 s_rows[64 * D8];
+    const int b = blockIdx.x;
+    uint4* win = (blockIdx.y ? v_win : k_win) + (int64_t)b * w_cap * D8;
+    const int32_t* idx = keep + (int64_t)(b / heads_per_seq) * n_keep;
+    const int total = n_keep * D8;   // at most 64 D8
+    for (int p = threadIdx.x; p < total; p += kThreads) {
+        const int i = p / D8, pc = p % D8;
+        const int src = min(max(idx[i], 0), n_rows - 1);
+        s_rows[p] = win[(int64_t)(row0 + src) * D8 + pc];
+    }
+    __syncthreads();   // every source row is read
+    for (int p = threadIdx.x; p < total; p += kThreads) win[(int64_t)row0 * D8 + p] = s_rows[p];
+}
+
 bool mq_shape_ok(int T, int window_capacity, int Bp, int groups, int n_q, int head_dim)
 {
     if (n_q < 1 || groups < 1 || groups > 8 || (int64_t)n_q * groups > kMaxRows || Bp < 1 || Bp > 65535 || T < 0 || (T & 63)) return false;
@@ -395,15 +498,21 @@ bool mq_shape_ok(int T, int window_capacity, int Bp, int groups, int n_q, int he
     return head_dim == 64 || head_dim == 128;
 }
 
-template <int D, bool EXT>
-void mq_launch(hipStream_t st, const MqArgs& a, const dim3 grid)
+template <int D, bool EXT, bool MASK>
+void mq_launch(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid)
 {
     switch ((a.R + 15) / 16) {
-        case 1: multi_query_decode_kernel<D, 1, EXT><<<grid, kThreads, 0, st>>>(a); break;
-        case 2: multi_query_decode_kernel<D, 2, EXT><<<grid, kThreads, 0, st>>>(a); break;
-        case 3: multi_query_decode_kernel<D, 3, EXT><<<grid, kThreads, 0, st>>>(a); break;
-        default: multi_query_decode_kernel<D, 4, EXT><<<grid, kThreads, 0, st>>>(a); break;
+        case 1: multi_query_decode_kernel<D, 1, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        case 2: multi_query_decode_kernel<D, 2, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        case 3: multi_query_decode_kernel<D, 3, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        default: multi_query_decode_kernel<D, 4, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
     }
+}
+template <bool MASK>
+void mq_launch_any(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid, int head_dim, bool ext)
+{
+    if (head_dim == 64) { if (ext) mq_launch<64, true, MASK>(st, a, grid); else mq_launch<64, false, MASK>(st, a, grid); }
+    else { if (ext) mq_launch<128, true, MASK>(st, a, grid); else mq_launch<128, false, MASK>(st, a, grid); }
 }
 
 }  // namespace
@@ -423,6 +532,18 @@ extern "C" int mustafar_decode_multi_query(void* stream, const mustafar_cache_vi
                                            const void* v_new, int window_len, int window_capacity, void* out, float* lse, void* workspace,
                                            float sqrt_d, int head_dim)
 {
+    return mustafar_decode_multi_query_masked(stream, k_base, v_base, T_base, k_extents, v_extents, T, Bp, num_key_value_groups, n_q, q, k_window,
+                                              v_window, k_new, v_new, window_len, window_capacity, out, lse, workspace, sqrt_d, head_dim, nullptr,
+                                              0, 0, 1, 1);
+}
+
+extern "C" int mustafar_decode_multi_query_masked(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                                  const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, int T, int Bp,
+                                                  int num_key_value_groups, int n_q, const void* q, void* k_window, void* v_window,
+                                                  const void* k_new, const void* v_new, int window_len, int window_capacity, void* out,
+                                                  float* lse, void* workspace, float sqrt_d, int head_dim, const void* mask,
+                                                  int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask)
+{
     using namespace mustafar_shared;
     if (!mq_shape_ok(T, window_capacity, Bp, num_key_value_groups, n_q, head_dim) || !(sqrt_d > 0.f)) return MUSTAFAR_EINVAL;
     if (window_len < n_q || window_len > window_capacity || (k_new == nullptr) != (v_new == nullptr)) return MUSTAFAR_EINVAL;
@@ -432,7 +553,15 @@ extern "C" int mustafar_decode_multi_query(void* stream, const mustafar_cache_vi
     if (!q || !out || !k_window || !v_window || !workspace || !lse || !aligned16(q) || !aligned16(out) || !aligned16(k_window) ||
         !aligned16(v_window) || !aligned16(workspace) || !aligned16(k_new) || !aligned16(v_new) || ((uintptr_t)lse & 3))
         return MUSTAFAR_EINVAL;
-    MqArgs a{};
+    if (mask) {   // (a NULL mask: the other four arguments are not looked at)
+        const int64_t columns = (int64_t)T + window_len;
+        if (((uintptr_t)mask & 1) || (mask_rows != 1 && mask_rows != n_q) || heads_per_mask < 1 || heads_per_mask > Bp || Bp % heads_per_mask)
+            return MUSTAFAR_EINVAL;
+        if (mask_batch_stride < 0 || mask_row_stride < 0 || (mask_rows > 1 && mask_row_stride < columns) ||
+            (Bp / heads_per_mask > 1 && mask_batch_stride < columns))
+            return MUSTAFAR_EINVAL;
+    }
+    MqMaskArgs a{};
     if (T_base && (!side_of(k_base, T_base, Bp, head_dim, &a.k) || !side_of(v_base, T_base, Bp, head_dim, &a.v))) return MUSTAFAR_EINVAL;
     const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R, head_dim);
     const int runs = (ntb + bpw - 1) / bpw, slabs = runs + (window_capacity + 63) / 64;
@@ -454,10 +583,38 @@ extern "C" int mustafar_decode_multi_query(void* stream, const mustafar_cache_vi
             window_len - n_q, window_capacity, D8, total);
     }
     const dim3 grid(slabs, Bp);
-    if (head_dim == 64) { if (ext) mq_launch<64, true>(st, a, grid); else mq_launch<64, false>(st, a, grid); }
-    else { if (ext) mq_launch<128, true>(st, a, grid); else mq_launch<128, false>(st, a, grid); }
+    if (mask) {
+        a.mask = static_cast<const h16*>(mask);
+        a.mask_batch_stride = mask_batch_stride;
+        a.mask_row_stride = mask_row_stride;
+        a.mask_rows = mask_rows;
+        a.heads_per_mask = heads_per_mask;
+        mq_launch_any<true>(st, a, grid, head_dim, ext);
+    } else {
+        mq_launch_any<false>(st, a, grid, head_dim, ext);   // (MqArgs alone: the launch of ABI 112)
+    }
     // the fold of every row's slabs: (kv_heads, G, R) = (B', R, R) addresses row bkv * R + r of out / lse and of every slab
     if (head_dim == 64) shared_merge_kernel<64><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);
     else shared_merge_kernel<128><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mustafar_window_keep_rows(void* stream, void* k_window, void* v_window, int Bp, int heads_per_seq, int window_capacity,
+                                         int head_dim, int row0, int n_rows, const int32_t* keep, int n_keep)
+{
+    using namespace mustafar_shared;
+    if ((head_dim != 64 && head_dim != 128) || Bp < 1 || Bp > 65535 || heads_per_seq < 1 || Bp % heads_per_seq) return MUSTAFAR_EINVAL;
+    if (n_rows < 1 || n_rows > 64 || n_keep < 1 || n_keep > n_rows || window_capacity > kMaxWindow || row0 < 0 ||
+        (int64_t)row0 + n_rows > window_capacity)
+        return MUSTAFAR_EINVAL;
+    if (!k_window || !v_window || !aligned16(k_window) || !aligned16(v_window) || !keep || ((uintptr_t)keep & 3)) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(Bp, 2);
+    if (head_dim == 64)
+        window_keep_kernel<64><<<grid, kThreads, 0, st>>>(static_cast<uint4*>(k_window), static_cast<uint4*>(v_window), keep, heads_per_seq,
+                                                          window_capacity, row0, n_rows, n_keep);
+    else
+        window_keep_kernel<128><<<grid, kThreads, 0, st>>>(static_cast<uint4*>(k_window), static_cast<uint4*>(v_window), keep, heads_per_seq,
+                                                           window_capacity, row0, n_rows, n_keep);
     return (int)hipGetLastError();
 }

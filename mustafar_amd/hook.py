@@ -617,7 +617,24 @@ class MustafarAttention:
                 return j + 1
         return n_q
 
-    def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False):
+    @staticmethod
+    def _multi_mask(attention_mask, bsz: int, n_q: int, columns: int, dev):
+        """The additive fp16 mask of a decode_multi call, checked: [bsz, 1, 1 or n_q, columns] on `dev`, rows and planes at least
+        `columns` halfs apart and unit stride along a row (made contiguous otherwise); or None."""
+        if attention_mask is None:
+            return None
+        if attention_mask.dim() != 4 or attention_mask.shape[:2] != (bsz, 1) or attention_mask.shape[2] not in (1, n_q) or \
+                attention_mask.shape[3] != columns:
+            raise ValueError(f"Attention mask should be of size {(bsz, 1, n_q, columns)} or {(bsz, 1, 1, columns)}, but is "
+                             f"{tuple(attention_mask.size())}")
+        if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
+            raise RuntimeError("attention_mask must be a float16 tensor on the device of the query")
+        if attention_mask.stride(3) != 1 or (bsz > 1 and attention_mask.stride(0) < columns) or \
+                (attention_mask.shape[2] > 1 and attention_mask.stride(2) < columns):
+            attention_mask = attention_mask.contiguous()
+        return attention_mask
+
+    def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False, attention_mask=None):
         """n_q consecutive tokens of every sequence in one call: q [bsz, H, n_q, D], their new k / v [bsz, Hkv, n_q, D] -> (out
         [bsz, H, n_q, D], past'), or (out, lse fp32 [bsz, H, n_q], past') with `return_lse`.  Token j attends to the cache, the window
         and the new rows 0 .. j: what n_q decode_fused steps compute, with the compressed cache read once (speculative decoding, a short
@@ -627,7 +644,13 @@ class MustafarAttention:
 
         The call appends the rows and never compresses: close it with `accept()`, which drops the rejected rows and runs the 256-token
         trigger when it is due.  A trigger point may only be the LAST row of a call -- a call that would step over one raises ValueError
-        naming the largest n_q that fits.  No attention_mask in this version: left-padded batches keep using decode_fused."""
+        naming the largest n_q that fits.
+
+        attention_mask: additive fp16 on the query's device, [bsz, 1, 1 or n_q, kv_seq_len + n_q] (one plane per sequence).  Row j of an
+        [.., n_q, ..] mask is what a decode_fused step for token j would get as mask[:, :, j:j+1, :kv_seq_len + j + 1] -- HF's 4-D form
+        with its finfo.min upper triangle among the new tokens works unchanged; the causal limit holds whatever the mask says, so a mask
+        only takes columns away: left padding, the holes of a batch whose sequences accepted different numbers of drafts, or a draft
+        tree (0 on a node's ancestors and itself, finfo.min on the other new tokens; close with accept(keep=path)).  INTEGRATION.md 5."""
         cfg = self.cfg
         if cfg.api != "fused":
             raise ValueError("decode_multi needs MustafarConfig(api='fused')")
@@ -643,12 +666,17 @@ class MustafarAttention:
         if fits < n_q:
             raise ValueError(f"decode_multi: {n_q} tokens would step over a 256-token trigger point; at most {fits} fit in this call "
                              "(the trigger point may only be the last row: accept() then runs the trigger)")
+        kv_seq_len = Past(*past).kv_seq_len
+        mask = self._multi_mask(attention_mask, bsz, n_q, kv_seq_len + n_q, query_states.device)
         past = self.to_fused(past)
         per = 64 // groups
         outs, lses = [], []
         for s0 in range(0, n_q, per):
             s1 = min(n_q, s0 + per)
-            o, l, past = self._decode_multi_call(query_states[:, :, s0:s1], key_states[:, :, s0:s1], value_states[:, :, s0:s1], past)
+            m = None
+            if mask is not None:   # the sub-call's rows, and the columns up to its last new row
+                m = mask[:, :, (s0 if mask.shape[2] > 1 else 0):(s1 if mask.shape[2] > 1 else 1), :kv_seq_len + s1]
+            o, l, past = self._decode_multi_call(query_states[:, :, s0:s1], key_states[:, :, s0:s1], value_states[:, :, s0:s1], past, m)
             outs.append(o)
             lses.append(l)
         out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
@@ -656,8 +684,9 @@ class MustafarAttention:
             return out, past
         return out, (lses[0] if len(lses) == 1 else torch.cat(lses, dim=2)), past
 
-    def _decode_multi_call(self, q, k_rows, v_rows, past):
-        """One mustafar_decode_multi_query call: at most 64 // groups tokens, appended to the windows and counted in the returned past."""
+    def _decode_multi_call(self, q, k_rows, v_rows, past, mask=None):
+        """One mustafar_decode_multi_query(_masked) call: at most 64 // groups tokens, appended to the windows and counted in the returned
+        past.  mask: None, or a checked view [bsz, 1, 1 or n, kv_seq_len + n] (`_multi_mask`) whose address and strides the call takes."""
         past = Past(*past)
         k_c, k_w, v_c, v_w, C = past[:5]
         bsz, H, n, D = q.shape
@@ -679,23 +708,55 @@ class MustafarAttention:
         _, ws = self._scratch(dev, 0, 0, ws_bytes)
         out = torch.empty((bsz, H, n, D), dtype=torch.float16, device=dev)
         lse = torch.empty((bsz, H, n), dtype=torch.float32, device=dev)
+        args = (kv, vv, t_base, kt, vt, C, Bkv, groups, n, q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(),
+                w_len, k_w.cap, out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D)
         with torch.cuda.device(dev):
-            err = L.mustafar_decode_multi_query(torch.cuda.current_stream(dev).cuda_stream, kv, vv, t_base, kt, vt, C, Bkv, groups, n,
-                                                q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(), w_len,
-                                                k_w.cap, out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if mask is None:
+                err = L.mustafar_decode_multi_query(st, *args)
+            else:   # one plane per sequence: its kv heads share it
+                err = L.mustafar_decode_multi_query_masked(st, *args, mask.data_ptr(), mask.stride(0), mask.stride(2), mask.shape[2],
+                                                           self.num_key_value_heads)
         _lib.check(err, "mustafar_decode_multi_query")
         del keep   # (alive until here: the call has been issued)
         k_w.len = v_w.len = w_len
         return out, lse, past._replace(kv_seq_len=past.kv_seq_len + n)
 
-    def accept(self, past, rejected: int = 0, defer_trigger: bool = False):
+    def accept(self, past, rejected: int = 0, defer_trigger: bool = False, keep=None, n_q: Optional[int] = None):
         """Close a decode_multi call: drop the `rejected` newest rows (0 <= rejected < the rows the window holds) -- only the host lengths
         change, the rows stay in the buffer and the next append overwrites them -- then run the 256-token trigger exactly as a decode_fused
-        step does when it is due.  `defer_trigger`: return with the trigger not run, for run_triggers() over all layers."""
+        step does when it is due.  `defer_trigger`: return with the trigger not run, for run_triggers() over all layers.
+
+        keep (with n_q, the tokens of the last call; not with `rejected`): an integer tensor [bsz, n_keep] of indices into those n_q rows,
+        per sequence -- the accepted path of a draft tree, or the accepted prefix padded with any rejected node where a sequence accepted
+        less than the longest.  The rows are gathered to the front of the n_q rows of both windows (mustafar_window_keep_rows: one launch,
+        any order, duplicates allowed, indices clamped to [0, n_q)), the lengths become len - n_q + n_keep, then the trigger as above."""
         past = Past(*past)
         k_w, v_w = past.k_window, past.v_window
         if not isinstance(k_w, Window) or not isinstance(v_w, Window):
             raise ValueError("accept() closes a decode_multi call: the past it returned (windows in appendable buffers)")
+        if keep is not None:
+            if rejected != 0:
+                raise ValueError("accept: keep= says which rows stay; it does not go with rejected != 0")
+            if n_q is None:
+                raise ValueError("accept: keep= needs n_q, the number of tokens of the decode_multi call it closes")
+            if not 1 <= n_q <= min(k_w.len, v_w.len, 64) or k_w.len != v_w.len or k_w.buf.shape != v_w.buf.shape:
+                raise ValueError(f"accept: n_q must be in [1, {min(k_w.len, v_w.len, 64)}] -- the rows of one call, in windows of equal "
+                                 f"length and capacity (got {n_q}; the windows hold {k_w.len} / {v_w.len} rows)")
+            bsz = k_w.buf.shape[0]
+            if not isinstance(keep, torch.Tensor) or keep.dtype.is_floating_point or keep.dtype == torch.bool or keep.dim() != 2 or \
+                    keep.shape[0] != bsz or not 1 <= keep.shape[1] <= n_q:
+                raise ValueError(f"accept: keep must be an integer tensor [{bsz}, 1..{n_q}] of indices into the {n_q} rows of the last call "
+                                 f"(got {tuple(keep.shape) if isinstance(keep, torch.Tensor) else type(keep).__name__})")
+            n_keep, dev = keep.shape[1], k_w.buf.device
+            idx = keep.to(device=dev, dtype=torch.int32).contiguous()
+            B, Hkv, cap, D = k_w.buf.shape
+            with torch.cuda.device(dev):
+                err = _lib.load().mustafar_window_keep_rows(torch.cuda.current_stream(dev).cuda_stream, k_w.buf.data_ptr(), v_w.buf.data_ptr(),
+                                                            B * Hkv, Hkv, cap, D, k_w.len - n_q, n_q, idx.data_ptr(), n_keep)
+            _lib.check(err, "mustafar_window_keep_rows")
+            del idx   # (alive until here: the call has been issued)
+            rejected = n_q - n_keep
         if not 0 <= rejected < min(k_w.len, v_w.len):
             raise ValueError(f"accept: rejected must be in [0, {min(k_w.len, v_w.len)}) -- the window holds {k_w.len} rows (got {rejected})")
         k_w.len -= rejected

@@ -7,7 +7,11 @@ Each way is a captured graph of --launches repetitions back to back (the window 
 the graph holds fixed lengths), timed with device events around --replays replays behind warm-up replays, the two alternated A B A B
 in one process; the outputs are compared before anything is timed.  Prints ONE JSON line: per geometry and n_q the microseconds per call
 of `multi` and per n_q steps of `stepwise` (mean of the rounds, and every round).
+--mask pad | tree: both ways carry an additive fp16 mask -- `pad`: one row for all tokens, sequence b left-padded by 17 b
+columns; `tree`: a row per token, the binary tree parent(j) = (j - 1) // 2 among the new tokens (a decode_fused step takes row j cut to
+its columns) -- and a third graph times the UNMASKED multi call on the same operands, alternated with the other two: `multi_unmasked_us`.
 Needs an MI355X; it does not fall back to anything.  Usage: python tools/bench_multi_query.py [--launches 20] [--replays 20] [--rounds 4]
+[--mask none|pad|tree]
 """
 from __future__ import annotations
 
@@ -65,16 +69,29 @@ def run(D, n_q, a, dev):
     ks = [kn[:, :, j:j + 1].contiguous() for j in range(n_q)]
     vs = [vn[:, :, j:j + 1].contiguous() for j in range(n_q)]
     del K, V
+    mask = None
+    if a.mask != "none":
+        lowest = torch.finfo(torch.float16).min
+        mask = torch.zeros((BSZ, 1, 1 if a.mask == "pad" else n_q, L0 + n_q), dtype=torch.float16, device=dev)
+        for b in range(BSZ if a.mask == "pad" else 0):
+            mask[b, :, :, :17 * b] = lowest
+        for j in range(n_q if a.mask == "tree" else 0):
+            seen, i = set(), j
+            while i >= 0:
+                seen.add(i)
+                i = (i - 1) // 2 if i else -1
+            mask[:, :, j, [L0 + i for i in range(n_q) if i not in seen]] = lowest
+    step_masks = [None if mask is None else mask[:, :, min(j, mask.shape[2] - 1):min(j, mask.shape[2] - 1) + 1, :L0 + j + 1] for j in range(n_q)]
 
-    def multi():
+    def multi(m=mask):
         k_w.len = v_w.len = W0
-        return attn._decode_multi_call(q, kn, vn, (k_c, k_w, v_c, v_w, C, L0))[0]
+        return attn._decode_multi_call(q, kn, vn, (k_c, k_w, v_c, v_w, C, L0), m)[0]
 
     def stepwise():
         outs = []
         for j in range(n_q):
             k_w.len = v_w.len = W0 + j
-            outs.append(attn.decode_fused(qs[j], ks[j], vs[j], (k_c, k_w, v_c, v_w, C, L0 + j))[0])
+            outs.append(attn.decode_fused(qs[j], ks[j], vs[j], (k_c, k_w, v_c, v_w, C, L0 + j), attention_mask=step_masks[j])[0])
         return outs
 
     o1, o2 = multi(), torch.cat(stepwise(), dim=2)
@@ -88,14 +105,19 @@ def run(D, n_q, a, dev):
         return f
 
     ga, gb = graph_of(many(multi)), graph_of(many(stepwise))
+    gu = graph_of(many(lambda: multi(None))) if mask is not None else None
     replay_us(ga, 5)
     replay_us(gb, 5)
-    ta, tb = [], []
+    ta, tb, tu = [], [], []
     for _ in range(a.rounds):
         ta.append(replay_us(ga, a.replays) / a.launches)
         tb.append(replay_us(gb, a.replays) / a.launches)
+        if gu is not None:
+            tu.append(replay_us(gu, a.replays) / a.launches)
     res["multi_us"], res["stepwise_us"] = round(sum(ta) / len(ta), 2), round(sum(tb) / len(tb), 2)
     res["multi_us_rounds"], res["stepwise_us_rounds"] = [round(x, 2) for x in ta], [round(x, 2) for x in tb]
+    if tu:
+        res["multi_unmasked_us"], res["multi_unmasked_us_rounds"] = round(sum(tu) / len(tu), 2), [round(x, 2) for x in tu]
     return res
 
 
@@ -106,11 +128,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--head-dims", default="128,64")
     ap.add_argument("--n-q", default="1,2,4,8")
+    ap.add_argument("--mask", choices=["none", "pad", "tree"], default="none")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "tools/bench_multi_query.py needs a GPU"
     dev = torch.device("cuda:0")
     res = {"tool": "bench_multi_query", "device": torch.cuda.get_device_name(0), "q_heads": HQ, "kv_heads": HKV, "batch": BSZ, "tokens": T,
-           "window": W0}
+           "window": W0, "mask": a.mask}
     for D in (int(x) for x in a.head_dims.split(",")):
         for n in (int(x) for x in a.n_q.split(",")):
             res[f"d{D}_nq{n}"] = run(D, n, a, dev)

@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
-"""Compare the kernels of two device builds of a .hip file: isa_diff.py OLD.elf NEW.elf [OLD.s NEW.s]
+r"""Compare the kernels of two device builds of a .hip file: isa_diff.py [--key REGEX] OLD.elf NEW.elf [OLD.s NEW.s]
 
 The ELFs come from build.sh's flags plus `--cuda-device-only --no-gpu-bundle-output -c` (one sized FUNC symbol per kernel,
 no relocations: a symbol's bytes are position-independent), the optional .s files from the same flags with -S.  Per kernel
 present in both it compares the raw instruction bytes of the symbol's range in .text and, with the .s files, its
 .amdhsa_* directive block (registers, LDS, scratch, kernarg size, preload).  Bytes, not -S text: .LBB<n>_<m> labels carry
 the function's ordinal and shift when a kernel is removed.  Exit status 1 if any common kernel differs.
+
+--key REGEX: a kernel whose mangled name matches is known by the regex's groups instead (a group that did not take part counts as 0),
+so that a template that gained a parameter is still compared with what it was: with
+--key 'multi_query_decode_kernelILi(\d+)ELi(\d+)ELb([01])E(?:Lb([01])E)?' the instantiation <128, 2, true> of the old build meets
+<128, 2, true, false> of the new one, and <.., true> is reported as added.
 """
 import os
 import re
@@ -15,6 +20,14 @@ import sys
 
 _ROCM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf")
 READELF = shutil.which("llvm-readelf") or (_ROCM if os.path.exists(_ROCM) else "readelf")
+
+
+KEY = None
+
+
+def known_as(name):
+    m = KEY.search(name) if KEY else None
+    return name if not m else name[m.start():m.start(1)] + " <" + ", ".join(g or "0" for g in m.groups()) + ">"
 
 
 def kernels(elf):
@@ -31,7 +44,7 @@ def kernels(elf):
         f = line.split()
         if len(f) == 8 and f[3] == "FUNC" and f[6] == idx:
             a, n = int(f[1], 16) - addr, int(f[2])
-            out[f[7]] = text[a:a + n]
+            out[known_as(f[7])] = text[a:a + n]
     return out
 
 
@@ -41,7 +54,7 @@ def directives(asm):
     for line in open(asm):
         s = line.split()
         if len(s) == 2 and s[0] == ".amdhsa_kernel":
-            cur = out.setdefault(s[1], [])
+            cur = out.setdefault(known_as(s[1]), [])
         elif s and s[0] == ".end_amdhsa_kernel":
             cur = None
         elif cur is not None and s and s[0].startswith(".amdhsa_"):
@@ -50,6 +63,10 @@ def directives(asm):
 
 
 def main():
+    global KEY
+    if len(sys.argv) > 2 and sys.argv[1] == "--key":
+        KEY = re.compile(sys.argv[2])
+        del sys.argv[1:3]
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     dold, dnew = (directives(sys.argv[3]), directives(sys.argv[4])) if len(sys.argv) > 4 else ({}, {})
     common = sorted(set(old) & set(new))
