@@ -526,9 +526,9 @@ int mustafar_decode_shared_segment(void* stream, const mustafar_cache_view* k_ca
  *   MUSTAFAR_EINVAL before any launch for: n_q < 1, n_q * num_key_value_groups > 64, num_key_value_groups outside 1..8, head_dim not 64 or
  *   128, Bp outside 1..65535, T < 0 or T % 64 != 0, the T_base / extent rules above, window_len < n_q, window_len > window_capacity,
  *   window_capacity > 1024, exactly one of k_new / v_new NULL, NULL or misaligned q / out / windows / new rows / workspace / lse, a base
- *   view mustafar_decode_shared_segment would refuse.  No device-side lengths (window_len_extra, T_device) in this version; the mask
- *   comes with mustafar_decode_multi_query_masked (ABI 114, below), of which this call is the form with mask == NULL.
- *   Nothing is allocated and nothing is read back: the call can be captured in a hipGraph at fixed lengths.
+ *   view mustafar_decode_shared_segment would refuse.  The mask comes with mustafar_decode_multi_query_masked (ABI 114, below), device-side
+ *   lengths (window_len_extra, T_device) with mustafar_decode_multi_query_lengths (ABI 115, below); this call is their form with all
+ *   three NULL.  Nothing is allocated and nothing is read back: the call can be captured in a hipGraph, which replays these lengths.
  * mustafar_decode_multi_query_workspace_bytes: (ceil(T / 64 / bpw) + ceil(window_capacity / 64)) * Bp * R * (head_dim + 2) * 4, with
  *   bpw = ceil(8 R (head_dim + 2) / (88 head_dim)) blocks per run, the rule of mustafar_shared_segment_workspace_bytes.  0 for the
  *   shapes the call refuses.
@@ -567,7 +567,8 @@ int mustafar_decode_multi_query(void* stream, const mustafar_cache_view* k_base,
  *   MUSTAFAR_EINVAL for: n_keep outside 1..n_rows, n_rows outside 1..64, row0 < 0 or row0 + n_rows > window_capacity, window_capacity > 1024,
  *   head_dim not 64 or 128, NULL or misaligned (16 B) windows, a NULL or misaligned (4 B) keep, Bp outside 1..65535, heads_per_seq < 1 or
  *   no divisor of Bp.
- * Neither call allocates or reads anything back: both can be captured in a hipGraph at fixed lengths.
+ * Neither call allocates or reads anything back: both can be captured in a hipGraph (these lengths; mustafar_decode_multi_query_lengths
+ * below takes them from the device).
  */
 int mustafar_decode_multi_query_masked(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
                                        const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
@@ -577,6 +578,41 @@ int mustafar_decode_multi_query_masked(void* stream, const mustafar_cache_view* 
                                        const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask);
 int mustafar_window_keep_rows(void* stream, void* k_window, void* v_window, int Bp, int heads_per_seq, int window_capacity, int head_dim,
                               int row0, int n_rows, const int32_t* keep, int n_keep);
+
+/*
+ * Device-side lengths in the several-token call (ABI 115; multi_query.hip): ONE captured graph of the call replayed while
+ * the window and the compressed cache grow.
+ *
+ * mustafar_decode_multi_query_lengths: mustafar_decode_multi_query_masked (its 27 arguments first, in the same order, same workspace)
+ *   with two DEVICE ints, either of which may be NULL, read once per workgroup when the kernels start -- the conventions of
+ *   mustafar_decode_attention_extents_hd.  Both NULL: exactly the launches and bits of mustafar_decode_multi_query_masked, which is this
+ *   call with two NULLs.
+ *   window_len_extra    the window length in effect is w = window_len + *window_len_extra, clamped by the kernels into
+ *                       [n_q, window_capacity] (a bad counter gives a wrong row, never an address outside the window buffers): the new
+ *                       rows are copied to rows [w - n_q, w), query token j sees window rows [0, w - n_q + j], image rows at or beyond w
+ *                       are zero.  window_len itself keeps the host rules, n_q <= window_len <= window_capacity.  The caller advances
+ *                       the int between replays (mustafar_counter_add) by the rows that stayed
+ *   T_device            T becomes the CAPACITY the launch is sized for -- grid, slabs, workspace -- and *T_device the compressed tokens IN
+ *                       USE: T_base plus a multiple of 256, clamped by the kernels into [T_base, T].  Needs T > T_base and both tables.
+ *                       Blocks at or beyond *T_device / 64 are skipped: a run that straddles the limit ends at it, and so does what it
+ *                       requests ahead; a run with no block in use touches no byte of the cache (no base loads, no nz_offset load, no
+ *                       table entry) and leaves slabs of weight zero.  Table entries at or beyond (*T_device - T_base) / 256 are never
+ *                       read, so the caller fills them as the cache grows; it adds 256 to *T_device when a trigger has listed an extent
+ *                       and takes 256 off *window_len_extra, the windows having slid
+ *   mask columns        compressed token t reads column t, window row w reads column *T_device + w -- the tokens IN USE, not the
+ *                       capacity --, so a mask row is the model's own; columns at or beyond *T_device + w are never read.  With either
+ *                       pointer not NULL the stride rules of the mask take T + window_capacity in place of T + window_len: a row reaches as
+ *                       far as the lengths can
+ *   MUSTAFAR_EINVAL before any launch, beyond the cases of mustafar_decode_multi_query_masked: T_device with T == T_base or a NULL table,
+ *   either pointer not 4-byte aligned, the mask strides above.  Nothing is allocated and nothing is read back.
+ */
+int mustafar_decode_multi_query_lengths(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                        const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                        int T, int Bp, int num_key_value_groups, int n_q,
+                                        const void* q, void* k_window, void* v_window, const void* k_new, const void* v_new,
+                                        int window_len, int window_capacity, void* out, float* lse, void* workspace, float sqrt_d, int head_dim,
+                                        const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask,
+                                        const int32_t* window_len_extra, const int32_t* T_device);
 
 /*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must

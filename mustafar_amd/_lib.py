@@ -63,6 +63,8 @@ SIGNATURES = {
                                            _vp, _vp, _vp, ctypes.c_float, _i32]),
     "mustafar_decode_multi_query_masked": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                                   _i32, _vp, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i32, _i32]),
+    "mustafar_decode_multi_query_lengths": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                   _i32, _vp, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "mustafar_window_keep_rows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "mustafar_trigger_compress_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "mustafar_trigger_finish_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32]),

@@ -1,6 +1,6 @@
 // multi_query.hip -- several query tokens of every sequence per fused decode call, head_dim 64 and 128, for gfx950.  The C ABI entry points
-// mustafar_decode_multi_query, mustafar_decode_multi_query_masked, mustafar_decode_multi_query_workspace_bytes and
-// mustafar_window_keep_rows (include/mustafar_hip.h, ABI 112 and 114).
+// mustafar_decode_multi_query, mustafar_decode_multi_query_masked, mustafar_decode_multi_query_lengths,
+// mustafar_decode_multi_query_workspace_bytes and mustafar_window_keep_rows (include/mustafar_hip.h, ABI 112, 114 and 115).
 //
 // A caller that verifies n_q drafted tokens, or feeds a short follow-up turn, would issue n_q decode steps, each re-reading the whole
 // compressed cache and paying the per-tile cost of the format -- bitmap, rank, address, select -- again.  The n_q tokens of one sequence are
@@ -33,6 +33,11 @@
 //                    addition, the hook's rule; the causal limit stays on top (an invisible column is -inf whatever the mask says, and
 //                    its mask value is not read), so a mask only takes columns away.  Columns at or beyond T + window_len are never
 //                    read.  The unmasked instantiations take MqArgs alone and are the code they were
+//   LEN              the window length and the compressed tokens in use come from two device ints (either may be NULL), read once per
+//                    workgroup with scalar loads at the top: w_len = clamp(w_len + *w_extra, n_q, w_cap); EXT: the blocks in use ntb =
+//                    clamp(*t_dev / 64, T_base / 64, T / 64), T being the capacity the grid and the slabs are sized for.  A run ends at
+//                    ntb, one beyond it reads nothing and leaves slabs of weight zero, and the window's mask columns start at 64 ntb.
+//                    The instantiations without LEN are the code they were (multi_query_append_lengths_kernel: the append with the same w_len)
 // window_keep_kernel          rows row0 + i <- row0 + keep[seq][i] of both windows of every head (accept(keep=) after a draft tree): the source
 //                             rows go through LDS and a barrier before the first store, so any order and duplicates are safe
 // shared_merge_kernel         (expand_block.h) folds a row's slabs -- compressed runs first, then window chunks -- into out and lse
@@ -251,6 +256,23 @@ template <bool MASK>
 struct MqKernelArgs { typedef MqArgs type; };
 template <>
 struct MqKernelArgs<true> { typedef MqMaskArgs type; };
+// LEN: the two device lengths follow whatever the instantiation took before (either may be NULL; t_dev is read by EXT alone).
+template <bool MASK>
+struct MqLenArgs : MqKernelArgs<MASK>::type {
+    const int32_t* w_extra;              // added to w_len, the sum clamped into [n_q, w_cap]
+    const int32_t* t_dev;                // compressed tokens in use, clamped into [64 ntb_base, 64 ntb]
+};
+template <bool MASK, bool LEN>
+struct MqKernelArgsOf { typedef typename MqKernelArgs<MASK>::type type; };
+template <bool MASK>
+struct MqKernelArgsOf<MASK, true> { typedef MqLenArgs<MASK> type; };
+// w_len + *w_extra in [n_q, w_cap]: a bad counter gives a wrong row, never an address outside the window buffers
+__device__ __forceinline__ int device_window_len(int w_len, const int32_t* w_extra, int n_q, int w_cap)
+{
+    if (!w_extra) return w_len;
+    const int extra = min(max((int)*(cu32_p)reinterpret_cast<const uint32_t*>(w_extra), -kMaxWindow), kMaxWindow);   // (no overflow below)
+    return min(max(w_len + extra, n_q), w_cap);
+}
 
 // The mask values of a thread's 16 columns, packed as they lie in memory.  The base and the strides of a mask are 2-byte aligned only:
 // these are loads of 4 and 16 bytes at 2-byte alignment, which global memory serves (no 2-byte loads, which would take a register each
@@ -297,8 +319,8 @@ __device__ __forceinline__ BlockRef block_of(const uint64_t* bmp_h, const uint32
     return BlockRef{bmp_h + (int64_t)tb * TILES, idx_h + (int64_t)tb * TILES, nz_h};
 }
 
-template <int D, int RT, bool EXT, bool MASK>
-__global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename MqKernelArgs<MASK>::type a)
+template <int D, int RT, bool EXT, bool MASK, bool LEN>
+__global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename MqKernelArgsOf<MASK, LEN>::type a)
 {
     constexpr int TILES = D;                 // tiles of a 64-token block on either side (D / 64 per token)
     constexpr int KS = D / 32;               // k-steps of the score product
@@ -316,6 +338,16 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename M
     const int R = a.R;
     const int l15 = lane & 15, l4 = lane >> 4;
     const uint16_t* sb = reinterpret_cast<const uint16_t*>(s_stream);
+
+    // LEN: the two device lengths, one wave-uniform load each, asked for here with the q fragments (used behind them: nothing waits for a
+    // cold scalar load inside a step).  ntb: the blocks IN USE, which is also the column base of the mask's window part
+    int w_len = a.w_len, ntb = a.ntb;
+    if constexpr (LEN) {
+        w_len = device_window_len(a.w_len, a.w_extra, a.n_q, a.w_cap);
+        if constexpr (EXT) {
+            if (a.t_dev) ntb = min(max((int)*(cu32_p)reinterpret_cast<const uint32_t*>(a.t_dev) >> 6, a.ntb_base), a.ntb);
+        }
+    }
 
     // q fragments (A operand): lane holds q[row 16 rt + (l & 15)][32 s + 8 (l >> 4) ..+8); rows at or beyond R are zero
     h16x8 qf[RT][KS];
@@ -347,9 +379,16 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename M
         mrow = a.mask + (int64_t)(bkv / a.heads_per_mask) * a.mask_batch_stride +
                (a.mask_rows == 1 ? 0 : (int64_t)(srow % a.n_q) * a.mask_row_stride) + sq * 16;
 
-    if (x < a.runs) {
-        // ---- compressed blocks [tb0, tb1) of this head
-        const int tb0 = x * a.bpw, tb1 = min(a.ntb, tb0 + a.bpw);
+    // LEN: a run with no block in use takes neither branch: it touches no byte of the cache -- no base loads, no nz_offset load, no table
+    // resolution -- and leaves slabs of weight zero (M = -inf, L = 0, o = 0).  KEEP the `x * bpw < ntb` test: without it the loop below
+    // still does not run and the slabs are the same, so no test on valid tables can tell (the surviving mutant), but the
+    // prologue would resolve block tb0 through a table entry beyond the tokens in use -- which callers leave unwritten (the hook's tables
+    // are zero there: a NULL view).  Only the hook's graph tests, whose unlisted entries are NULL, stand behind it
+    const bool is_run = x < a.runs;
+    if (is_run && (!LEN || x * a.bpw < ntb)) {
+        // ---- compressed blocks [tb0, tb1) of this head (LEN: a run that straddles the blocks in use ends at them, and so does what it
+        // requests ahead: tn below is bounded by tb1)
+        const int tb0 = x * a.bpw, tb1 = min(ntb, tb0 + a.bpw);
         const uint4* kz = a.k.nz + (a.k.nz_stride ? (int64_t)bkv * a.k.nz_stride : (int64_t)a.k.nz_offset[bkv]);
         const uint4* vz = a.v.nz + (a.v.nz_stride ? (int64_t)bkv * a.v.nz_stride : (int64_t)a.v.nz_offset[bkv]);
         const uint64_t* kb_h = a.k.bmp + bkv * a.k.bmp_stride;
@@ -402,13 +441,13 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename M
             kc = kn;
             vc = vn;
         }
-    } else {
+    } else if (!is_run) {
         // ---- window chunk: rows [w0, w0 + 64) of this head's dense window (a chunk beyond the window leaves its slabs at weight zero)
-        const int w0 = (x - a.runs) * 64, w_len = a.w_len;
+        const int w0 = (x - a.runs) * 64;
         if (w0 < w_len) {
             MaskRegs mk{};
             if constexpr (MASK)   // the causally visible ones of the thread's 16 columns (below): none at or beyond T + w_len
-                mk = load_mask(mrow + (int64_t)a.ntb * 64 + w0,
+                mk = load_mask(mrow + (int64_t)ntb * 64 + w0,
                                m_on ? min(16, max(0, w_len - a.n_q + srow % a.n_q + 1 - w0 - sq * 16)) : 0);
             const h16* kw = a.k_win + (int64_t)bkv * a.w_cap * D;
             const h16* vw = a.v_win + (int64_t)bkv * a.w_cap * D;
@@ -469,6 +508,21 @@ __global__ __launch_bounds__(kThreads) void multi_query_append_kernel(const uint
     dst[((int64_t)b * w_cap + row0 + j) * D8 + pc] = src[i];
 }
 
+// The same with the window length on the device: row0 = clamp(w_len + *w_extra, n_q, w_cap) - n_q, inside the buffer whatever the counter holds.
+__global__ __launch_bounds__(kThreads) void multi_query_append_lengths_kernel(const uint4* __restrict__ k_new, const uint4* __restrict__ v_new,
+                                                                              uint4* __restrict__ k_win, uint4* __restrict__ v_win, int n_q,
+                                                                              int w_len, const int32_t* __restrict__ w_extra, int w_cap, int D8,
+                                                                              int total)
+{
+    const int row0 = device_window_len(w_len, w_extra, n_q, w_cap) - n_q;
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const int pc = i % D8, j = (i / D8) % n_q, b = i / (D8 * n_q);
+    const uint4* src = blockIdx.y ? v_new : k_new;
+    uint4* dst = blockIdx.y ? v_win : k_win;
+    dst[((int64_t)b * w_cap + row0 + j) * D8 + pc] = src[i];
+}
+
 // Rows [row0, row0 + n_keep) of one head's K or V window <- rows row0 + keep[seq][i], keep clamped to [0, n_rows): grid (B', 2), thread =
 // 16-byte pieces.  Every source row is in LDS before the first store (the barrier), so the index order and duplicates do not matter.
 template <int D>
@@ -498,21 +552,38 @@ bool mq_shape_ok(int T, int window_capacity, int Bp, int groups, int n_q, int he
     return head_dim == 64 || head_dim == 128;
 }
 
-template <int D, bool EXT, bool MASK>
-void mq_launch(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid)
+template <int D, bool EXT, bool MASK, bool LEN>
+void mq_launch(hipStream_t st, const typename MqKernelArgsOf<MASK, LEN>::type& a, const dim3 grid)
 {
     switch ((a.R + 15) / 16) {
-        case 1: multi_query_decode_kernel<D, 1, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
-        case 2: multi_query_decode_kernel<D, 2, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
-        case 3: multi_query_decode_kernel<D, 3, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
-        default: multi_query_decode_kernel<D, 4, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        case 1: multi_query_decode_kernel<D, 1, EXT, MASK, LEN><<<grid, kThreads, 0, st>>>(a); break;
+        case 2: multi_query_decode_kernel<D, 2, EXT, MASK, LEN><<<grid, kThreads, 0, st>>>(a); break;
+        case 3: multi_query_decode_kernel<D, 3, EXT, MASK, LEN><<<grid, kThreads, 0, st>>>(a); break;
+        default: multi_query_decode_kernel<D, 4, EXT, MASK, LEN><<<grid, kThreads, 0, st>>>(a); break;
     }
 }
-template <bool MASK>
-void mq_launch_any(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid, int head_dim, bool ext)
+template <bool MASK, bool LEN>
+void mq_launch_any(hipStream_t st, const typename MqKernelArgsOf<MASK, LEN>::type& a, const dim3 grid, int head_dim, bool ext)
 {
-    if (head_dim == 64) { if (ext) mq_launch<64, true, MASK>(st, a, grid); else mq_launch<64, false, MASK>(st, a, grid); }
-    else { if (ext) mq_launch<128, true, MASK>(st, a, grid); else mq_launch<128, false, MASK>(st, a, grid); }
+    if (head_dim == 64) { if (ext) mq_launch<64, true, MASK, LEN>(st, a, grid); else mq_launch<64, false, MASK, LEN>(st, a, grid); }
+    else { if (ext) mq_launch<128, true, MASK, LEN>(st, a, grid); else mq_launch<128, false, MASK, LEN>(st, a, grid); }
+}
+// The instantiation a call takes: MqArgs alone (the launch of ABI 112), + the mask (ABI 114), + the device lengths (ABI 115)
+void mq_launch_call(hipStream_t st, const MqLenArgs<true>& a, const dim3 grid, int head_dim, bool ext)
+{
+    const bool len = a.w_extra || a.t_dev;
+    if (a.mask) {
+        if (len) mq_launch_any<true, true>(st, a, grid, head_dim, ext);
+        else mq_launch_any<true, false>(st, a, grid, head_dim, ext);
+    } else if (len) {
+        MqLenArgs<false> u{};
+        static_cast<MqArgs&>(u) = a;
+        u.w_extra = a.w_extra;
+        u.t_dev = a.t_dev;
+        mq_launch_any<false, true>(st, u, grid, head_dim, ext);
+    } else {
+        mq_launch_any<false, false>(st, a, grid, head_dim, ext);
+    }
 }
 
 }  // namespace
@@ -544,6 +615,19 @@ extern "C" int mustafar_decode_multi_query_masked(void* stream, const mustafar_c
                                                   float* lse, void* workspace, float sqrt_d, int head_dim, const void* mask,
                                                   int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask)
 {
+    return mustafar_decode_multi_query_lengths(stream, k_base, v_base, T_base, k_extents, v_extents, T, Bp, num_key_value_groups, n_q, q, k_window,
+                                               v_window, k_new, v_new, window_len, window_capacity, out, lse, workspace, sqrt_d, head_dim, mask,
+                                               mask_batch_stride, mask_row_stride, mask_rows, heads_per_mask, nullptr, nullptr);
+}
+
+extern "C" int mustafar_decode_multi_query_lengths(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                                   const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, int T, int Bp,
+                                                   int num_key_value_groups, int n_q, const void* q, void* k_window, void* v_window,
+                                                   const void* k_new, const void* v_new, int window_len, int window_capacity, void* out,
+                                                   float* lse, void* workspace, float sqrt_d, int head_dim, const void* mask,
+                                                   int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask,
+                                                   const int32_t* window_len_extra, const int32_t* T_device)
+{
     using namespace mustafar_shared;
     if (!mq_shape_ok(T, window_capacity, Bp, num_key_value_groups, n_q, head_dim) || !(sqrt_d > 0.f)) return MUSTAFAR_EINVAL;
     if (window_len < n_q || window_len > window_capacity || (k_new == nullptr) != (v_new == nullptr)) return MUSTAFAR_EINVAL;
@@ -553,15 +637,19 @@ extern "C" int mustafar_decode_multi_query_masked(void* stream, const mustafar_c
     if (!q || !out || !k_window || !v_window || !workspace || !lse || !aligned16(q) || !aligned16(out) || !aligned16(k_window) ||
         !aligned16(v_window) || !aligned16(workspace) || !aligned16(k_new) || !aligned16(v_new) || ((uintptr_t)lse & 3))
         return MUSTAFAR_EINVAL;
+    // device lengths: T is a capacity to grow into (T_device), and a mask row reaches as far as the lengths can (either pointer)
+    const bool len = window_len_extra || T_device;
+    if (((uintptr_t)window_len_extra & 3) || ((uintptr_t)T_device & 3) || (T_device && (T == T_base || !k_extents || !v_extents)))
+        return MUSTAFAR_EINVAL;
     if (mask) {   // (a NULL mask: the other four arguments are not looked at)
-        const int64_t columns = (int64_t)T + window_len;
+        const int64_t columns = (int64_t)T + (len ? window_capacity : window_len);
         if (((uintptr_t)mask & 1) || (mask_rows != 1 && mask_rows != n_q) || heads_per_mask < 1 || heads_per_mask > Bp || Bp % heads_per_mask)
             return MUSTAFAR_EINVAL;
         if (mask_batch_stride < 0 || mask_row_stride < 0 || (mask_rows > 1 && mask_row_stride < columns) ||
             (Bp / heads_per_mask > 1 && mask_batch_stride < columns))
             return MUSTAFAR_EINVAL;
     }
-    MqMaskArgs a{};
+    MqLenArgs<true> a{};
     if (T_base && (!side_of(k_base, T_base, Bp, head_dim, &a.k) || !side_of(v_base, T_base, Bp, head_dim, &a.v))) return MUSTAFAR_EINVAL;
     const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R, head_dim);
     const int runs = (ntb + bpw - 1) / bpw, slabs = runs + (window_capacity + 63) / 64;
@@ -578,9 +666,15 @@ extern "C" int mustafar_decode_multi_query_masked(void* stream, const mustafar_c
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (k_new) {
         const int D8 = head_dim / 8, total = Bp * n_q * D8;
-        multi_query_append_kernel<<<dim3((total + kThreads - 1) / kThreads, 2), kThreads, 0, st>>>(
-            static_cast<const uint4*>(k_new), static_cast<const uint4*>(v_new), static_cast<uint4*>(k_window), static_cast<uint4*>(v_window), n_q,
-            window_len - n_q, window_capacity, D8, total);
+        const dim3 agrid((total + kThreads - 1) / kThreads, 2);
+        if (window_len_extra)
+            multi_query_append_lengths_kernel<<<agrid, kThreads, 0, st>>>(
+                static_cast<const uint4*>(k_new), static_cast<const uint4*>(v_new), static_cast<uint4*>(k_window), static_cast<uint4*>(v_window),
+                n_q, window_len, window_len_extra, window_capacity, D8, total);
+        else
+            multi_query_append_kernel<<<agrid, kThreads, 0, st>>>(
+                static_cast<const uint4*>(k_new), static_cast<const uint4*>(v_new), static_cast<uint4*>(k_window), static_cast<uint4*>(v_window),
+                n_q, window_len - n_q, window_capacity, D8, total);
     }
     const dim3 grid(slabs, Bp);
     if (mask) {
@@ -589,10 +683,10 @@ extern "C" int mustafar_decode_multi_query_masked(void* stream, const mustafar_c
         a.mask_row_stride = mask_row_stride;
         a.mask_rows = mask_rows;
         a.heads_per_mask = heads_per_mask;
-        mq_launch_any<true>(st, a, grid, head_dim, ext);
-    } else {
-        mq_launch_any<false>(st, a, grid, head_dim, ext);   // (MqArgs alone: the launch of ABI 112)
     }
+    a.w_extra = window_len_extra;
+    a.t_dev = T_device;
+    mq_launch_call(st, a, grid, head_dim, ext);
     // the fold of every row's slabs: (kv_heads, G, R) = (B', R, R) addresses row bkv * R + r of out / lse and of every slab
     if (head_dim == 64) shared_merge_kernel<64><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);
     else shared_merge_kernel<128><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, slabs, Bp, R, R, static_cast<h16*>(out), lse);

@@ -3989,7 +3989,7 @@ void launch_finish(hipStream_t st, hipEvent_t f0, hipEvent_t f1, const float* ws
 
 extern "C" {
 
-int mustafar_abi_version(void) { return 114; }   // 114: mustafar_decode_multi_query_masked, mustafar_window_keep_rows (multi_query.hip: attention masks and draft trees in the several-token call); 113: mustafar_cache_view::flags, MUSTAFAR_VIEW_KEY_ROWS, mustafar_key_rows_plan / _fill / _to_tiles (key_rows.hip), mustafar_decode_reads_key_rows (token-row key blocks for the GQA-4 one-pass key phase); 112: mustafar_decode_multi_query, mustafar_decode_multi_query_workspace_bytes (multi_query.hip: several query tokens of every sequence per call); 111: mustafar_decode_shared_segment, mustafar_shared_segment_workspace_bytes (shared_segment.hip: one compressed copy of a shared prefix decoded for a whole batch); 110: mustafar_decode_attention_lse_hd, mustafar_decode_attention_extents_lse_hd, mustafar_merge_attention_states (the LSE of a fused decode, window-less calls, the merge of partial attention states); 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
+int mustafar_abi_version(void) { return 115; }   // 115: mustafar_decode_multi_query_lengths (multi_query.hip: device-side window and compressed lengths, one graph of the several-token call replayed while the cache grows); 114: mustafar_decode_multi_query_masked, mustafar_window_keep_rows (multi_query.hip: attention masks and draft trees in the several-token call); 113: mustafar_cache_view::flags, MUSTAFAR_VIEW_KEY_ROWS, mustafar_key_rows_plan / _fill / _to_tiles (key_rows.hip), mustafar_decode_reads_key_rows (token-row key blocks for the GQA-4 one-pass key phase); 112: mustafar_decode_multi_query, mustafar_decode_multi_query_workspace_bytes (multi_query.hip: several query tokens of every sequence per call); 111: mustafar_decode_shared_segment, mustafar_shared_segment_workspace_bytes (shared_segment.hip: one compressed copy of a shared prefix decoded for a whole batch); 110: mustafar_decode_attention_lse_hd, mustafar_decode_attention_extents_lse_hd, mustafar_merge_attention_states (the LSE of a fused decode, window-less calls, the merge of partial attention states); 109: mustafar_prefill_compress_hd, mustafar_cache_gather_hd (head_dim 64: the prefill from raw rows, consolidate() on the device); 108: mustafar_decode_attention_extents_hd, mustafar_trigger_compress_batch_hd, mustafar_trigger_finish_batch_hd (head_dim 64 grows by extents); 107: mustafar_decode_attention_hd, mustafar_decode_workspace_bytes_hd (head_dim 64); 106 (round 6): mustafar_compress_get_form; the compression form and the test hook are per host thread; 105 (round 5): mustafar_profile_end2, mustafar_convert_*, mustafar_cache_consolidate_extents, mustafar_compress_set_form
 
 int Key_SplitK_API(void* stream, const void* /*A*/, const uint64_t* bmp, const void* NZ, const uint32_t* idx,
                    const uint32_t* NZ_offset, const void* B, void* C, int M_Global, int N_Global, int K_Global,

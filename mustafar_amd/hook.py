@@ -608,8 +608,9 @@ class MustafarAttention:
         return new._replace(k_cache=k_c, v_cache=v_c, compressed_length=C + 256)
 
     # ---- several query tokens per call (multi_query.hip) ------------------------------------------------------------
-    def _fits_before_trigger(self, past, n_q: int) -> int:
-        """The largest n <= n_q such that no row but the last of an n-token call reaches a trigger point (`trigger_due`)."""
+    def fits_before_trigger(self, past, n_q: int) -> int:
+        """The largest n <= n_q such that no row but the last of an n-token call reaches a trigger point (`trigger_due`).  A caller that
+        replays a graph of a fixed n_q asks before every replay: below n_q, it issues an eager call of that many tokens instead."""
         _, k_w, _, _, C, L = past
         w_len = k_w.len if isinstance(k_w, Window) else k_w.shape[2]
         for j in range(n_q - 1):
@@ -617,14 +618,24 @@ class MustafarAttention:
                 return j + 1
         return n_q
 
+    _fits_before_trigger = fits_before_trigger   # compatibility alias only (the name before it was public): not a second API
+
     @staticmethod
-    def _multi_mask(attention_mask, bsz: int, n_q: int, columns: int, dev):
-        """The additive fp16 mask of a decode_multi call, checked: [bsz, 1, 1 or n_q, columns] on `dev`, rows and planes at least
-        `columns` halfs apart and unit stride along a row (made contiguous otherwise); or None."""
+    def _device_int(t, name: str, dev) -> None:
+        """A device-side length as the kernels load it: ONE int32 on the query's device (its address goes to the library as it is)."""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != 1 or t.device != dev:
+            raise ValueError(f"decode_multi: {name} must be an int32 tensor of one element on the device of the query ({dev}); got "
+                             f"{(t.dtype, tuple(t.shape), str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+    @staticmethod
+    def _multi_mask(attention_mask, bsz: int, n_q: int, columns: int, dev, exact: bool = True):
+        """The additive fp16 mask of a decode_multi call, checked: [bsz, 1, 1 or n_q, columns] on `dev` (not `exact`, a replayed graph:
+        at least `columns`), rows and planes at least `columns` halfs apart and unit stride along a row (made contiguous otherwise); or
+        None."""
         if attention_mask is None:
             return None
         if attention_mask.dim() != 4 or attention_mask.shape[:2] != (bsz, 1) or attention_mask.shape[2] not in (1, n_q) or \
-                attention_mask.shape[3] != columns:
+                attention_mask.shape[3] < columns or (exact and attention_mask.shape[3] != columns):
             raise ValueError(f"Attention mask should be of size {(bsz, 1, n_q, columns)} or {(bsz, 1, 1, columns)}, but is "
                              f"{tuple(attention_mask.size())}")
         if attention_mask.dtype != torch.float16 or attention_mask.device != dev:
@@ -634,7 +645,9 @@ class MustafarAttention:
             attention_mask = attention_mask.contiguous()
         return attention_mask
 
-    def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False, attention_mask=None):
+    def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False, attention_mask=None,
+                     step_counter: Optional[torch.Tensor] = None, t_device: Optional[torch.Tensor] = None,
+                     t_capacity: Optional[int] = None):
         """n_q consecutive tokens of every sequence in one call: q [bsz, H, n_q, D], their new k / v [bsz, Hkv, n_q, D] -> (out
         [bsz, H, n_q, D], past'), or (out, lse fp32 [bsz, H, n_q], past') with `return_lse`.  Token j attends to the cache, the window
         and the new rows 0 .. j: what n_q decode_fused steps compute, with the compressed cache read once (speculative decoding, a short
@@ -650,7 +663,17 @@ class MustafarAttention:
         [.., n_q, ..] mask is what a decode_fused step for token j would get as mask[:, :, j:j+1, :kv_seq_len + j + 1] -- HF's 4-D form
         with its finfo.min upper triangle among the new tokens works unchanged; the causal limit holds whatever the mask says, so a mask
         only takes columns away: left padding, the holes of a batch whose sequences accepted different numbers of drafts, or a draft
-        tree (0 on a node's ancestors and itself, finfo.min on the other new tokens; close with accept(keep=path)).  INTEGRATION.md 5."""
+        tree (0 on a node's ancestors and itself, finfo.min on the other new tokens; close with accept(keep=path)).  INTEGRATION.md 5.
+
+        `step_counter`, `t_device`, `t_capacity`: as in decode_fused, for ONE captured graph of the call replayed while the cache grows.
+        `step_counter` (int32 device tensor) is added to the window length inside the kernels; the returned past keeps the host lengths
+        of the FIRST replay, and the caller accounts with `advance(past, n_q)` before `accept()` and adds the rows that stayed to the
+        counter (mustafar_counter_add).  The windows must already have their full capacity (a past from `to_fused()` has), n_q must fit
+        one library call (n_q <= 64 // groups), and a mask is [bsz, 1, 1 or n_q, >= compressed capacity + window capacity], refilled by
+        the caller between replays: window row w sits at column compressed-tokens-in-use + w.  `t_device` (int32 device tensor, with
+        `step_counter`) holds the compressed tokens in use and `t_capacity` the tokens the launch is sized for (an arena that grows by
+        extents, or an ExtentCache64): after a trigger, run eagerly, the caller adds 256 to `t_device` and takes 256 off the counter.
+        `fits_before_trigger(past, n_q)` says when a replay would step over a trigger point."""
         cfg = self.cfg
         if cfg.api != "fused":
             raise ValueError("decode_multi needs MustafarConfig(api='fused')")
@@ -662,14 +685,26 @@ class MustafarAttention:
                 value_states.shape != key_states.shape:
             raise ValueError(f"decode_multi: q [bsz, {self.num_heads}, n_q, {self.head_dim}] with k / v [bsz, {self.num_key_value_heads}, n_q, "
                              f"{self.head_dim}] (got {tuple(query_states.shape)}, {tuple(key_states.shape)}, {tuple(value_states.shape)})")
-        fits = self._fits_before_trigger(past, n_q)
+        per = 64 // groups
+        if t_device is not None and step_counter is None:
+            raise ValueError("decode_multi: t_device is for captured graphs and needs step_counter (an eager call passes neither)")
+        if step_counter is not None:
+            self._device_int(step_counter, "step_counter", query_states.device)
+        if t_device is not None:
+            self._device_int(t_device, "t_device", query_states.device)
+        if step_counter is not None and n_q > per:
+            raise ValueError(f"decode_multi: a replayed call (step_counter) is one library call: at most {per} tokens at {groups} q heads "
+                             f"per kv head (got {n_q})")
+        fits = self.fits_before_trigger(past, n_q)
         if fits < n_q:
             raise ValueError(f"decode_multi: {n_q} tokens would step over a 256-token trigger point; at most {fits} fit in this call "
                              "(the trigger point may only be the last row: accept() then runs the trigger)")
+        if step_counter is not None:
+            return self._decode_multi_replayed(query_states, key_states, value_states, past, return_lse, attention_mask, step_counter,
+                                               t_device, t_capacity)
         kv_seq_len = Past(*past).kv_seq_len
         mask = self._multi_mask(attention_mask, bsz, n_q, kv_seq_len + n_q, query_states.device)
         past = self.to_fused(past)
-        per = 64 // groups
         outs, lses = [], []
         for s0 in range(0, n_q, per):
             s1 = min(n_q, s0 + per)
@@ -684,41 +719,84 @@ class MustafarAttention:
             return out, past
         return out, (lses[0] if len(lses) == 1 else torch.cat(lses, dim=2)), past
 
-    def _decode_multi_call(self, q, k_rows, v_rows, past, mask=None):
-        """One mustafar_decode_multi_query(_masked) call: at most 64 // groups tokens, appended to the windows and counted in the returned
-        past.  mask: None, or a checked view [bsz, 1, 1 or n, kv_seq_len + n] (`_multi_mask`) whose address and strides the call takes."""
+    def _decode_multi_replayed(self, query_states, key_states, value_states, past, return_lse, attention_mask, step_counter, t_device,
+                               t_capacity):
+        """decode_multi with `step_counter`: the checks a graph that outlives this call needs, then ONE library call whose lengths come
+        from the device.  The returned past is the one that came in (as a fused past): the host lengths of the first replay."""
+        cfg = self.cfg
+        bsz, _, n_q, _ = query_states.shape
+        past = self.to_fused(past)
+        k_c, k_w, v_c, v_w, C, _ = past
+        full = cfg.residual_length + 256   # the longest window: the step that fires the trigger holds R + 256 rows (to_fused)
+        if k_w.cap < full or v_w.cap != k_w.cap or k_w.len + n_q > k_w.cap:
+            raise ValueError(f"decode_multi: under graph replay (step_counter) the windows must already have their full capacity of "
+                             f"{full} rows and room for this call -- a graph keeps their addresses, nothing may be reallocated (got "
+                             f"{k_w.cap} / {v_w.cap} rows of capacity, {k_w.len} in use, {n_q} new)")
+        T = C   # the compressed tokens the launch is sized for
+        if t_device is not None:
+            if cfg.hd64_extents:
+                if t_capacity is None or not isinstance(k_c, ExtentCache64) or t_capacity <= k_c.tokens or t_capacity < C or \
+                        (t_capacity - k_c.tokens) % 256 or (t_capacity - k_c.tokens) // 256 > k_c.MAX_EXTENTS:
+                    raise ValueError("decode_multi: t_device needs an extent cache and t_capacity = base tokens + a multiple of 256 (at most the "
+                                     "table's entries), not below the compressed length")
+            elif t_capacity is None or t_capacity < C or (t_capacity - C) % 256 or not isinstance(k_c, CompressedArena) or \
+                    not cfg.extents or t_capacity <= k_c.tokens or (t_capacity - k_c.tokens) // 256 > k_c.MAX_EXTENTS:
+                raise ValueError("decode_multi: t_device needs an arena cache that grows by extents and t_capacity = compressed length + a "
+                                 "multiple of 256, beyond the base tokens")
+            T = t_capacity
+        elif t_capacity is not None:
+            raise ValueError("decode_multi: t_capacity goes with t_device (the compressed tokens in use, on the device)")
+        # a replayed graph reads more columns as the cache and the window grow: up to the two capacities
+        mask = self._multi_mask(attention_mask, bsz, n_q, T + k_w.cap, query_states.device, exact=False)
+        out, lse, past = self._decode_multi_call(query_states, key_states, value_states, past, mask, step_counter, t_device, T)
+        return (out, lse, past) if return_lse else (out, past)
+
+    def _decode_multi_call(self, q, k_rows, v_rows, past, mask=None, step_counter=None, t_device=None, T=None):
+        """One mustafar_decode_multi_query(_masked, _lengths) call: at most 64 // groups tokens, appended to the windows and counted in the
+        returned past.  mask: None, or a checked view [bsz, 1, 1 or n, kv_seq_len + n] (`_multi_mask`) whose address and strides the call
+        takes.  step_counter / t_device (`_decode_multi_replayed`): the lengths come from the device, the launch is sized for `T`
+        compressed tokens and the window capacity, nothing is reallocated and the past comes back with the host lengths it had."""
         past = Past(*past)
         k_c, k_w, v_c, v_w, C = past[:5]
+        T = C if T is None else T
         bsz, H, n, D = q.shape
         Bkv, groups, dev = bsz * self.num_key_value_heads, self.num_key_value_groups, q.device
         w_len = k_w.len + n
-        k_w.reserve(w_len)
-        v_w.reserve(w_len)
+        if step_counter is None:
+            k_w.reserve(w_len)
+            v_w.reserve(w_len)
         if k_w.cap != v_w.cap or k_w.len != v_w.len:
             raise RuntimeError("key/value windows must have the same length and capacity")
         q = q.contiguous()
         kn, vn = k_rows.contiguous(), v_rows.contiguous()
         k = as_cache(k_c, C)   # (an arena is poll()ed by view_args; an ExtentCache64 always names its tables here)
-        (kv, vv, t_base, kt, vt), keep = k.view_args(as_cache(v_c, C), tables=C > k.tokens or k.lse_reads_tables)
+        (kv, vv, t_base, kt, vt), keep = k.view_args(as_cache(v_c, C), tables=T > k.tokens or k.lse_reads_tables)
         L = _lib.load()
-        ws_bytes = L.mustafar_decode_multi_query_workspace_bytes(C, k_w.cap, Bkv, groups, n, D)
+        ws_bytes = L.mustafar_decode_multi_query_workspace_bytes(T, k_w.cap, Bkv, groups, n, D)
         if ws_bytes <= 0:
-            raise ValueError(f"decode_multi: the library serves no call of {n} tokens x {groups} q heads per kv head, {C} compressed tokens, "
+            raise ValueError(f"decode_multi: the library serves no call of {n} tokens x {groups} q heads per kv head, {T} compressed tokens, "
                              f"a window of {k_w.cap} rows, head_dim {D}")
         _, ws = self._scratch(dev, 0, 0, ws_bytes)
         out = torch.empty((bsz, H, n, D), dtype=torch.float16, device=dev)
         lse = torch.empty((bsz, H, n), dtype=torch.float32, device=dev)
-        args = (kv, vv, t_base, kt, vt, C, Bkv, groups, n, q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(),
+        args = (kv, vv, t_base, kt, vt, T, Bkv, groups, n, q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(),
                 w_len, k_w.cap, out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            if mask is None:
+            margs = (None, 0, 0, 1, 1)
+            if mask is not None:   # one plane per sequence: its kv heads share it
+                margs = (mask.data_ptr(), mask.stride(0), mask.stride(2), mask.shape[2], self.num_key_value_heads)
+            if step_counter is not None:
+                err = L.mustafar_decode_multi_query_lengths(st, *args, *margs, step_counter.data_ptr(),
+                                                            t_device.data_ptr() if t_device is not None else None)
+            elif mask is None:
                 err = L.mustafar_decode_multi_query(st, *args)
-            else:   # one plane per sequence: its kv heads share it
-                err = L.mustafar_decode_multi_query_masked(st, *args, mask.data_ptr(), mask.stride(0), mask.stride(2), mask.shape[2],
-                                                           self.num_key_value_heads)
+            else:
+                err = L.mustafar_decode_multi_query_masked(st, *args, *margs)
         _lib.check(err, "mustafar_decode_multi_query")
         del keep   # (alive until here: the call has been issued)
+        if step_counter is not None:
+            return out, lse, past   # lengths advance with the device counter
         k_w.len = v_w.len = w_len
         return out, lse, past._replace(kv_seq_len=past.kv_seq_len + n)
 
