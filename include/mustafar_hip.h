@@ -615,6 +615,56 @@ int mustafar_decode_multi_query_lengths(void* stream, const mustafar_cache_view*
                                         const int32_t* window_len_extra, const int32_t* T_device);
 
 /*
+ * Several query tokens per call over frozen and shared segments (shared_segment.hip, multi_query.hip).  These four symbols
+ * were added WITHOUT a change of mustafar_abi_version(), which stays 115: nothing that existed changed its behaviour or its bits, and a
+ * caller detects the new entry points by symbol (dlsym), not by version.
+ *
+ * mustafar_decode_shared_segment_multi: mustafar_decode_shared_segment for n_q query tokens of each of n_seqs sequences: one cache of
+ *   `kv_heads` heads is read for n_seqs * n_q query tokens, every row sees all T tokens (a frozen segment has no causal limit among them).
+ *   q, out              fp16 [n_seqs, kv_heads * num_key_value_groups, n_q, head_dim] -- the hook's [bsz, heads, n_q, head_dim] --, contiguous,
+ *                       16-byte aligned;  lse fp32 [n_seqs, kv_heads * num_key_value_groups, n_q], REQUIRED
+ *   rows                local row of kv head h: r = s * (groups * n_q) + g * n_q + j for sequence s, q head g of the kv head, query token j;
+ *                       R = n_seqs * groups * n_q in 1..1024, groups in 1..8 (groups * n_q is not limited to 8)
+ *   launches            two, whatever R: the rows of a kv head are cut into chunks of 64 consecutive local rows (the last one shorter; a
+ *                       boundary may fall inside a sequence's rows), the chunks are blockIdx.z of ONE decode launch -- a workgroup serves
+ *                       (run, kv head, chunk) and expands its blocks for its own chunk --, and one row-kernel launch merges all rows.  Row
+ *                       tiles: those of 64 rows with more than one chunk, else those of R; rows at or beyond R are zero query rows
+ *   run length          ceil(8 min(R, 64) (head_dim + 2) / (88 head_dim)) blocks, the rule of mustafar_shared_segment_workspace_bytes
+ *   bits                with R <= 64 the launches ARE those of mustafar_decode_shared_segment with groups * n_q in place of groups (the same
+ *                       kernel instantiations): bit for bit its result on the same rows.  A chunk of 64 rows gives the bits of a 64-row call
+ *                       on those rows
+ *   MUSTAFAR_EINVAL before any launch for n_q < 1, R outside 1..1024, and everything mustafar_decode_shared_segment refuses.  Nothing is
+ *   read back and nothing is allocated: the call can be captured in a hipGraph.
+ * mustafar_shared_segment_multi_workspace_bytes: ceil(T / 64 / run length) * kv_heads * R * (head_dim + 2) * 4; 0 for the shapes the call refuses.
+ *
+ * mustafar_decode_multi_segment: mustafar_decode_multi_query_masked over compressed tokens ONLY -- the several-token call over a frozen
+ *   per-sequence segment: no window, no new rows, no append launch, no window workgroups, no causal limit (query token j sees all T tokens),
+ *   no device-side lengths.  Two launches.
+ *   k_base .. T         Bp caches as in mustafar_decode_multi_query: base views, T_base, the DEVICE tables of 256-token extents, the same
+ *                       T_base / extent rules; T > 0 (and so T_base > 0) is required
+ *   q, out, lse         as in mustafar_decode_multi_query: fp16 [B', groups, n_q, head_dim], fp32 [B', groups, n_q]
+ *   rows                R = n_q * groups in 1..1024 (a 256-token follow-up turn at GQA-4 is one launch pair), cut into 64-row chunks in
+ *                       blockIdx.z exactly as above; run length and workspace by the same rule with Bp for kv_heads
+ *   mask                as in mustafar_decode_multi_query_masked with the columns [0, T): mask_rows 1 or n_q, the clamp rule, strides in
+ *                       halfs, mask_row_stride >= T with mask_rows > 1, mask_batch_stride >= T with Bp / heads_per_mask > 1.  A row masked
+ *                       entirely returns what the clamp implies, finite.  NULL: no mask (the other four arguments are not looked at)
+ *   MUSTAFAR_EINVAL before any launch for T <= 0 or T % 64 != 0, n_q < 1, n_q * groups > 1024, groups outside 1..8, head_dim not 64 or 128,
+ *   Bp outside 1..65535, the T_base / extent rules, NULL or misaligned q / out / lse / workspace, a base view mustafar_decode_shared_segment
+ *   would refuse, the mask rules.  Nothing is allocated and nothing is read back: the call can be captured in a hipGraph.
+ * mustafar_decode_multi_segment_workspace_bytes: ceil(T / 64 / run length) * Bp * R * (head_dim + 2) * 4; 0 for the shapes the call refuses.
+ */
+int64_t mustafar_shared_segment_multi_workspace_bytes(int T, int kv_heads, int num_key_value_groups, int n_seqs, int n_q, int head_dim);
+int mustafar_decode_shared_segment_multi(void* stream, const mustafar_cache_view* k_cache, const mustafar_cache_view* v_cache,
+                                         int T, int kv_heads, int num_key_value_groups, int n_seqs, int n_q,
+                                         const void* q, void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
+int64_t mustafar_decode_multi_segment_workspace_bytes(int T, int Bp, int num_key_value_groups, int n_q, int head_dim);
+int mustafar_decode_multi_segment(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                  const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents,
+                                  int T, int Bp, int num_key_value_groups, int n_q,
+                                  const void* q, void* out, float* lse, void* workspace, float sqrt_d, int head_dim,
+                                  const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask);
+
+/*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
  * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
  *

@@ -65,7 +65,14 @@ SIGNATURES = {
                                                   _i32, _vp, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i32, _i32]),
     "mustafar_decode_multi_query_lengths": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32,
                                                    _i32, _vp, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
-    "mustafar_window_keep_rows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    # several query tokens over frozen and shared segments: added at ABI 115 without a version change, detected by symbol
+    "mustafar_shared_segment_multi_workspace_bytes": (_i64, [_i32] * 6),
+    "mustafar_decode_shared_segment_multi": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                                    _i32]),
+    "mustafar_decode_multi_segment_workspace_bytes": (_i64, [_i32] * 5),
+    "mustafar_decode_multi_segment": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                             _i32, _vp, _i64, _i64, _i32, _i32]),
+    "mustafar_window_keep_rows":(_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "mustafar_trigger_compress_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "mustafar_trigger_finish_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32]),
     "mustafar_prefill_compress_hd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _view_p, _view_p, _i64, _i64, _vp, _vp, _vp, _vp,

@@ -20,7 +20,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) uint32_t* cu32_p;   // read-only, wave-uniform: scalar loads
 
 constexpr int kThreads = 256;
-constexpr int kMaxRows = 64;     // rows of a kv head per launch
+constexpr int kMaxRows = 64;     // rows of a kv head per workgroup (and per launch of the single-token entry points)
+constexpr int kMaxRowsMulti = 1024;   // rows of a kv head per launch of the several-token segment forms: up to 16 chunks of kMaxRows in blockIdx.z
 constexpr int kRowPad = 72;      // halfs of a 64-half LDS row: 144 bytes, so the 16 rows of a 16-byte fragment read hit 16 different slots
 // Run length.  A workgroup writes one slab of R (D + 2) floats and the row kernel reads it once: 8 R (D + 2) bytes per run.  A block's
 // compressed K + V at 70 % sparsity is about 88 D bytes (0.3 x 2 x 64 D halfs of stream, D bitmaps and D offsets per side: 11 KB at

@@ -1,6 +1,7 @@
 // multi_query.hip -- several query tokens of every sequence per fused decode call, head_dim 64 and 128, for gfx950.  The C ABI entry points
 // mustafar_decode_multi_query, mustafar_decode_multi_query_masked, mustafar_decode_multi_query_lengths,
-// mustafar_decode_multi_query_workspace_bytes and mustafar_window_keep_rows (include/mustafar_hip.h, ABI 112, 114 and 115).
+// mustafar_decode_multi_query_workspace_bytes and mustafar_window_keep_rows (include/mustafar_hip.h, ABI 112, 114 and 115),
+// and the call over a frozen per-sequence segment, mustafar_decode_multi_segment with its workspace size.
 //
 // A caller that verifies n_q drafted tokens, or feeds a short follow-up turn, would issue n_q decode steps, each re-reading the whole
 // compressed cache and paying the per-tile cost of the format -- bitmap, rank, address, select -- again.  The n_q tokens of one sequence are
@@ -38,6 +39,7 @@
 //                    clamp(*t_dev / 64, T_base / 64, T / 64), T being the capacity the grid and the slabs are sized for.  A run ends at
 //                    ntb, one beyond it reads nothing and leaves slabs of weight zero, and the window's mask columns start at 64 ntb.
 //                    The instantiations without LEN are the code they were (multi_query_append_lengths_kernel: the append with the same w_len)
+// multi_segment_decode_kernel the compressed runs alone, for up to 1024 rows in chunks of 64 (blockIdx.z): no window, no causal limit, no LEN
 // window_keep_kernel          rows row0 + i <- row0 + keep[seq][i] of both windows of every head (accept(keep=) after a draft tree): the source
 //                             rows go through LDS and a barrier before the first store, so any order and duplicates are safe
 // shared_merge_kernel         (expand_block.h) folds a row's slabs -- compressed runs first, then window chunks -- into out and lse
@@ -319,6 +321,71 @@ __device__ __forceinline__ BlockRef block_of(const uint64_t* bmp_h, const uint32
     return BlockRef{bmp_h + (int64_t)tb * TILES, idx_h + (int64_t)tb * TILES, nz_h};
 }
 
+// A run of compressed blocks [tb0, tb1) of head bkv for the workgroup's row tiles: the compressed branch of multi_query_decode_kernel
+// below, statement for statement, as a function for multi_segment_decode_kernel.  (That kernel keeps its own copy: called from there, this
+// function changed 64 of its 70 instantiations by a few instructions each -- DESIGN.md 4.14 -- and they are to stay the code they were.)
+// mrow (MASK): the mask row of the thread's softmax row at the thread's 16 columns of block 0; m_on: whether the thread has a softmax row.
+template <int D, int RT, bool EXT, bool MASK>
+__device__ __forceinline__ void compressed_run(const MqArgs& a, int bkv, int tb0, int tb1, const h16x8 (&qf)[RT][D / 32], f32x4 (&o)[RT][D / 64],
+                                               float& M, float& L, const h16* mrow, bool m_on, uint4* s_stream, h16* s_img, h16* s_xe,
+                                               float* s_alpha, int tid, int lane, int wave, int l15, int l4, int srow, int sq)
+{
+    constexpr int TILES = D;
+    const uint16_t* sb = reinterpret_cast<const uint16_t*>(s_stream);
+    const uint4* kz = a.k.nz + (a.k.nz_stride ? (int64_t)bkv * a.k.nz_stride : (int64_t)a.k.nz_offset[bkv]);
+    const uint4* vz = a.v.nz + (a.v.nz_stride ? (int64_t)bkv * a.v.nz_stride : (int64_t)a.v.nz_offset[bkv]);
+    const uint64_t* kb_h = a.k.bmp + bkv * a.k.bmp_stride;
+    const uint32_t* ki_h = a.k.idx + bkv * a.k.idx_stride;
+    const uint64_t* vb_h = a.v.bmp + bkv * a.v.bmp_stride;
+    const uint32_t* vi_h = a.v.idx + bkv * a.v.idx_stride;
+
+    // the tiles this wave expands: K tile wave D / 4 + lane (lanes below D / 4), V tile 64 (lane >> 4) + 16 wave + (lane & 15) (lanes below D / 4)
+    const bool meta_on = lane < D / 4;
+    const int k_tile = wave * (D / 4) + lane, v_tile = (lane >> 4) * 64 + wave * 16 + l15;
+    BlockRef kc = block_of<TILES, EXT>(kb_h, ki_h, kz, a.k_ext, a.ntb_base, bkv, tb0);
+    BlockRef vc = block_of<TILES, EXT>(vb_h, vi_h, vz, a.v_ext, a.ntb_base, bkv, tb0);
+    TileMeta km = load_meta(kc.bmp, kc.idx, k_tile, meta_on);
+    TileMeta vm = load_meta(vc.bmp, vc.idx, v_tile, meta_on);
+    StreamRegs<TILES> kg{}, vg{};
+    load_block<TILES>(kc.nz, (cu32_p)kc.idx, tid, kg);
+    store_block<TILES>(kg, s_stream, tid);
+    uint32_t k0 = kg.i0;
+    __syncthreads();
+    for (int tb = tb0; tb < tb1; tb++) {
+        // requested now, used later: this block's value stream, the next block's bitmaps and offsets -- of the next block as resolved
+        MaskRegs mk{};
+        load_block<TILES>(vc.nz, (cu32_p)vc.idx, tid, vg);
+        const int tn = min(tb + 1, tb1 - 1);
+        const BlockRef kn = block_of<TILES, EXT>(kb_h, ki_h, kz, a.k_ext, a.ntb_base, bkv, tn);
+        const BlockRef vn = block_of<TILES, EXT>(vb_h, vi_h, vz, a.v_ext, a.ntb_base, bkv, tn);
+        const TileMeta km_next = load_meta(kn.bmp, kn.idx, k_tile, meta_on);
+        const TileMeta vm_next = load_meta(vn.bmp, vn.idx, v_tile, meta_on);
+        expand_keys<D>(km, k0, sb, s_img, lane, wave);
+        // MASK: the 16 mask values of the softmax step, requested here: behind them lie two barriers, the scores and the value expand.
+        // (Requested in front of the key expand they are live across its 16 packing registers: 7 VGPRs more, and D = 128 at two row
+        // tiles drops from three waves per SIMD to two: 104 -> 130 us at n_q = 8)  tb: the global block number
+        if constexpr (MASK) { if (m_on) mk = load_mask16(mrow + (int64_t)tb * 64); }
+        __syncthreads();   // the key image is whole, the key stream is read
+        store_block<TILES>(vg, s_stream, tid);
+        score_tiles<D, RT>(qf, s_img, s_xe, a.inv_sqrt_d, wave, l15, l4);
+        __syncthreads();   // x is whole, the key image is read, the value stream is staged
+        if (tb + 1 < tb1) load_block<TILES>(kn.nz, (cu32_p)kn.idx, tid, kg);   // (requested now, stored behind the softmax)
+        expand_values<D>(vm, vg.i0, sb, s_img, lane, wave);
+        softmax_rows<RT, false, MASK>(s_xe, s_alpha, M, L, srow, sq, 64, mk);
+        __syncthreads();   // e, alpha and the value image are whole, the value stream is read
+        if (tb + 1 < tb1) {
+            store_block<TILES>(kg, s_stream, tid);
+            k0 = kg.i0;
+        }
+        accumulate_out<D, RT>(o, s_img, s_xe, s_alpha, wave, l15, l4);
+        __syncthreads();   // the value image, e and alpha are read; the next key stream is staged
+        km = km_next;
+        vm = vm_next;
+        kc = kn;
+        vc = vn;
+    }
+}
+
 template <int D, int RT, bool EXT, bool MASK, bool LEN>
 __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename MqKernelArgsOf<MASK, LEN>::type a)
 {
@@ -495,6 +562,59 @@ __global__ __launch_bounds__(kThreads) void multi_query_decode_kernel(typename M
     write_slabs<D, RT>(o, M, L, a.ws_o, a.ws_ml, ((int64_t)x * gridDim.y + bkv) * R, R, wave, l15, l4, srow, sq);
 }
 
+// The several-token call over compressed tokens ONLY (mustafar_decode_multi_segment): a frozen per-sequence segment has
+// no window, no new rows and no causal limit among the query tokens, and no device-side lengths.  Grid (runs, B', row chunks): a workgroup
+// serves local rows [64 z, 64 z + 64) of one (sequence, kv head) -- up to 1024 rows, one expansion of a block per chunk -- over one run
+// of blocks.  The window fields of MqArgs are unused; MASK: columns [0, T), the row of query token (row % n_q).
+template <int D, int RT, bool EXT, bool MASK>
+__global__ __launch_bounds__(kThreads) void multi_segment_decode_kernel(typename MqKernelArgs<MASK>::type a)
+{
+    constexpr int KS = D / 32, CT = D / 64, KROW = D + 8;
+    constexpr int IMG = (64 * KROW > D * kRowPad) ? 64 * KROW : D * kRowPad;
+    __shared__ uint4 s_stream[8 * D];        // a block's key or value stream
+    __shared__ __attribute__((aligned(16))) h16 s_img[IMG];                 // key image [token][channel], then value image [channel][token]
+    __shared__ __attribute__((aligned(16))) h16 s_xe[RT * 16 * kRowPad];    // x, then e: [row][token]
+    __shared__ __attribute__((aligned(16))) float s_alpha[RT * 16];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bkv = blockIdx.y, x = blockIdx.x, row0 = 64 * (int)blockIdx.z;
+    const int R = a.R;
+    const int l15 = lane & 15, l4 = lane >> 4;
+
+    // q fragments (A operand) of the chunk's rows; rows at or beyond R are zero
+    h16x8 qf[RT][KS];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) {
+        const int r = row0 + rt * 16 + l15;
+        const bool live = r < R;
+        const h16* qrow = a.q + ((int64_t)bkv * R + (live ? r : 0)) * D;
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            h16x8 v = *reinterpret_cast<const h16x8*>(qrow + 32 * s + 8 * l4);
+            if (!live) v = h16x8{};
+            qf[rt][s] = v;
+        }
+    }
+    f32x4 o[RT][CT];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int c = 0; c < CT; c++) o[rt][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int srow = tid >> 2, sq = tid & 3;
+    float M = -INFINITY, L = 0.f;
+    const h16* mrow = nullptr;
+    const bool m_on = srow < RT * 16;
+    if constexpr (MASK)
+        mrow = a.mask + (int64_t)(bkv / a.heads_per_mask) * a.mask_batch_stride +
+               (a.mask_rows == 1 ? 0 : (int64_t)((row0 + srow) % a.n_q) * a.mask_row_stride) + sq * 16;
+
+    compressed_run<D, RT, EXT, MASK>(a, bkv, x * a.bpw, min(a.ntb, x * a.bpw + a.bpw), qf, o, M, L, mrow, m_on, s_stream, s_img, s_xe, s_alpha, tid,
+                                     lane, wave, l15, l4, srow, sq);
+    // (write_slabs counts rows from the chunk's first: the slab index and the row limit move by row0)
+    write_slabs<D, RT>(o, M, L, a.ws_o, a.ws_ml, ((int64_t)x * gridDim.y + bkv) * R + row0, R - row0, wave, l15, l4, srow, sq);
+}
+
 // Rows [row0, row0 + n_q) of every head's K and V window <- k_new / v_new [B', n_q, D]; thread = one 16-byte piece, blockIdx.y = side.
 __global__ __launch_bounds__(kThreads) void multi_query_append_kernel(const uint4* __restrict__ k_new, const uint4* __restrict__ v_new,
                                                                       uint4* __restrict__ k_win, uint4* __restrict__ v_win, int n_q, int row0,
@@ -586,8 +706,90 @@ void mq_launch_call(hipStream_t st, const MqLenArgs<true>& a, const dim3 grid, i
     }
 }
 
+// ---- the several-token call over a frozen per-sequence segment (mustafar_decode_multi_segment)
+bool ms_shape_ok(int T, int Bp, int groups, int n_q, int head_dim)
+{
+    if (n_q < 1 || n_q > kMaxRowsMulti || groups < 1 || groups > 8 || n_q * groups > kMaxRowsMulti || Bp < 1 || Bp > 65535) return false;
+    if (T <= 0 || (T & 63)) return false;
+    return head_dim == 64 || head_dim == 128;
+}
+template <int D, bool EXT, bool MASK>
+void ms_launch(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid)
+{
+    switch (grid.z > 1 ? 4 : (a.R + 15) / 16) {   // several chunks: every chunk at four row tiles, the last one's spare rows are zero queries
+        case 1: multi_segment_decode_kernel<D, 1, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        case 2: multi_segment_decode_kernel<D, 2, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        case 3: multi_segment_decode_kernel<D, 3, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+        default: multi_segment_decode_kernel<D, 4, EXT, MASK><<<grid, kThreads, 0, st>>>(a); break;
+    }
+}
+template <bool MASK>
+void ms_launch_any(hipStream_t st, const typename MqKernelArgs<MASK>::type& a, const dim3 grid, int head_dim, bool ext)
+{
+    if (head_dim == 64) { if (ext) ms_launch<64, true, MASK>(st, a, grid); else ms_launch<64, false, MASK>(st, a, grid); }
+    else { if (ext) ms_launch<128, true, MASK>(st, a, grid); else ms_launch<128, false, MASK>(st, a, grid); }
+}
+
 }  // namespace
 }  // namespace mustafar_shared
+
+extern "C" int64_t mustafar_decode_multi_segment_workspace_bytes(int T, int Bp, int num_key_value_groups, int n_q, int head_dim)
+{
+    using namespace mustafar_shared;
+    if (!ms_shape_ok(T, Bp, num_key_value_groups, n_q, head_dim)) return 0;
+    const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R < kMaxRows ? R : kMaxRows, head_dim);
+    return (int64_t)((ntb + bpw - 1) / bpw) * Bp * R * (head_dim + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int mustafar_decode_multi_segment(void* stream, const mustafar_cache_view* k_base, const mustafar_cache_view* v_base, int T_base,
+                                             const mustafar_cache_view* k_extents, const mustafar_cache_view* v_extents, int T, int Bp,
+                                             int num_key_value_groups, int n_q, const void* q, void* out, float* lse, void* workspace,
+                                             float sqrt_d, int head_dim, const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride,
+                                             int mask_rows, int heads_per_mask)
+{
+    using namespace mustafar_shared;
+    if (!ms_shape_ok(T, Bp, num_key_value_groups, n_q, head_dim) || !(sqrt_d > 0.f)) return MUSTAFAR_EINVAL;
+    if (T_base <= 0 || T_base > T || (T_base & 63)) return MUSTAFAR_EINVAL;
+    if (T > T_base && ((T_base & 255) || ((T - T_base) & 255) || (T - T_base) / 256 > kMaxExtents || !k_extents || !v_extents))
+        return MUSTAFAR_EINVAL;
+    if (!q || !out || !workspace || !lse || !aligned16(q) || !aligned16(out) || !aligned16(workspace) || ((uintptr_t)lse & 3))
+        return MUSTAFAR_EINVAL;
+    if (mask) {   // (a NULL mask: the other four arguments are not looked at)
+        if (((uintptr_t)mask & 1) || (mask_rows != 1 && mask_rows != n_q) || heads_per_mask < 1 || heads_per_mask > Bp || Bp % heads_per_mask)
+            return MUSTAFAR_EINVAL;
+        if (mask_batch_stride < 0 || mask_row_stride < 0 || (mask_rows > 1 && mask_row_stride < T) ||
+            (Bp / heads_per_mask > 1 && mask_batch_stride < T))
+            return MUSTAFAR_EINVAL;
+    }
+    MqMaskArgs a{};
+    if (!side_of(k_base, T_base, Bp, head_dim, &a.k) || !side_of(v_base, T_base, Bp, head_dim, &a.v)) return MUSTAFAR_EINVAL;
+    const int R = n_q * num_key_value_groups, ntb = T / 64, bpw = blocks_per_run(R < kMaxRows ? R : kMaxRows, head_dim);
+    const int runs = (ntb + bpw - 1) / bpw;
+    const bool ext = T > T_base;
+    a.k_ext = ext ? k_extents : nullptr;
+    a.v_ext = ext ? v_extents : nullptr;
+    a.q = static_cast<const h16*>(q);
+    a.ws_o = static_cast<float*>(workspace);
+    a.ws_ml = a.ws_o + (int64_t)runs * Bp * R * head_dim;
+    a.ntb = ntb; a.ntb_base = T_base / 64; a.bpw = bpw; a.runs = runs; a.n_q = n_q; a.R = R;
+    a.inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(runs, Bp, (R + kMaxRows - 1) / kMaxRows);
+    if (mask) {
+        a.mask = static_cast<const h16*>(mask);
+        a.mask_batch_stride = mask_batch_stride;
+        a.mask_row_stride = mask_row_stride;
+        a.mask_rows = mask_rows;
+        a.heads_per_mask = heads_per_mask;
+        ms_launch_any<true>(st, a, grid, head_dim, ext);
+    } else {
+        ms_launch_any<false>(st, a, grid, head_dim, ext);
+    }
+    // the fold of every row's slabs: (kv_heads, G, R) = (B', R, R) addresses row bkv * R + r of out / lse and of every slab
+    if (head_dim == 64) shared_merge_kernel<64><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, runs, Bp, R, R, static_cast<h16*>(out), lse);
+    else shared_merge_kernel<128><<<Bp * R, kThreads, 0, st>>>(a.ws_o, a.ws_ml, runs, Bp, R, R, static_cast<h16*>(out), lse);
+    return (int)hipGetLastError();
+}
 
 extern "C" int64_t mustafar_decode_multi_query_workspace_bytes(int T, int window_capacity, int Bp, int num_key_value_groups, int n_q, int head_dim)
 {

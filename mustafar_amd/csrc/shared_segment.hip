@@ -1,6 +1,7 @@
 // shared_segment.hip -- decode over ONE compressed copy of a segment that every sequence of a batch shares (a system prompt, a document,
 // n samples of one prompt), head_dim 64 and 128, for gfx950.  The C ABI entry points mustafar_decode_shared_segment and
-// mustafar_shared_segment_workspace_bytes (include/mustafar_hip.h, ABI 111).
+// mustafar_shared_segment_workspace_bytes (include/mustafar_hip.h, ABI 111), and their several-token forms
+// mustafar_decode_shared_segment_multi and mustafar_shared_segment_multi_workspace_bytes.
 //
 // The cache holds kv_heads heads in the reference format.  With n_seqs sequences and G q heads per kv head, a kv head serves
 // R = n_seqs * G query rows (local row r = s * G + g), and the per-tile cost of this format -- bitmap, rank, address, select -- is paid
@@ -39,7 +40,10 @@ struct SegArgs {
     float inv_sqrt_d;
 };
 
-template <int D, int RT>
+// CHUNKS (mustafar_decode_shared_segment_multi with more than 64 rows per kv head): grid (runs, kv heads, row chunks), the
+// workgroup serves local rows [64 z, 64 z + 64) of its kv head -- the same phases on its own rows, one expansion of the block per chunk.
+// Without it row0 is the constant 0 and the instantiations are the code they were.
+template <int D, int RT, bool CHUNKS = false>
 __global__ __launch_bounds__(kThreads) void shared_segment_decode_kernel(SegArgs a)
 {
     constexpr int TILES = D;                 // tiles of a 64-token block on either side (D / 64 per token)
@@ -56,6 +60,7 @@ __global__ __launch_bounds__(kThreads) void shared_segment_decode_kernel(SegArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kvh = blockIdx.y, run = blockIdx.x;
     const int G = a.groups, R = a.R, H = gridDim.y * G;
+    const int row0 = CHUNKS ? 64 * (int)blockIdx.z : 0;
     const int l15 = lane & 15, l4 = lane >> 4;
     const uint16_t* sb = reinterpret_cast<const uint16_t*>(s_stream);
 
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void shared_segment_decode_kernel(SegArgs
     h16x8 qf[RT][KS];
 #pragma unroll
     for (int rt = 0; rt < RT; rt++) {
-        const int r = rt * 16 + l15;
+        const int r = row0 + rt * 16 + l15;
         const bool live = r < R;
         const int rr = live ? r : 0;
         const h16* qrow = a.q + ((int64_t)(rr / G) * H + kvh * G + rr % G) * D;
@@ -224,10 +229,10 @@ __global__ __launch_bounds__(kThreads) void shared_segment_decode_kernel(SegArgs
         for (int c = 0; c < CT; c++)
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const int r = rt * 16 + 4 * l4 + i;
+                const int r = row0 + rt * 16 + 4 * l4 + i;
                 if (r < R) a.ws_o[(slab + r) * D + (wave * CT + c) * 16 + l15] = o[rt][c][i];
             }
-    if (srow < R && sq == 0) { a.ws_ml[2 * (slab + srow)] = M; a.ws_ml[2 * (slab + srow) + 1] = L; }
+    if (row0 + srow < R && sq == 0) { a.ws_ml[2 * (slab + row0 + srow)] = M; a.ws_ml[2 * (slab + row0 + srow) + 1] = L; }
 }
 
 bool shape_ok(int T, int kv_heads, int groups, int n_seqs, int head_dim)
@@ -237,11 +242,20 @@ bool shape_ok(int T, int kv_heads, int groups, int n_seqs, int head_dim)
     return head_dim == 64 || head_dim == 128;
 }
 
+// The several-token form: R = n_seqs * groups * n_q rows per kv head, up to 16 chunks of 64
+bool multi_shape_ok(int T, int kv_heads, int groups, int n_seqs, int n_q, int head_dim)
+{
+    if (T <= 0 || (T & 63) || kv_heads < 1 || kv_heads > 65535 || groups < 1 || groups > 8) return false;
+    if (n_seqs < 1 || n_seqs > kMaxRowsMulti || n_q < 1 || n_q > kMaxRowsMulti || (int64_t)n_seqs * groups * n_q > kMaxRowsMulti) return false;
+    return head_dim == 64 || head_dim == 128;
+}
+
 template <int D>
 void launch(hipStream_t st, const SegArgs& a, int runs, int kv_heads, h16* out, float* lse)
 {
-    const dim3 grid(runs, kv_heads);
-    switch ((a.R + 15) / 16) {
+    const dim3 grid(runs, kv_heads, (a.R + kMaxRows - 1) / kMaxRows);
+    if (grid.z > 1) shared_segment_decode_kernel<D, 4, true><<<grid, kThreads, 0, st>>>(a);
+    else switch ((a.R + 15) / 16) {
         case 1: shared_segment_decode_kernel<D, 1><<<grid, kThreads, 0, st>>>(a); break;
         case 2: shared_segment_decode_kernel<D, 2><<<grid, kThreads, 0, st>>>(a); break;
         case 3: shared_segment_decode_kernel<D, 3><<<grid, kThreads, 0, st>>>(a); break;
@@ -277,6 +291,40 @@ extern "C" int mustafar_decode_shared_segment(void* stream, const mustafar_cache
     a.ws_o = static_cast<float*>(workspace);
     a.ws_ml = a.ws_o + (int64_t)runs * kv_heads * R * head_dim;
     a.ntb = ntb; a.bpw = bpw; a.n_seqs = n_seqs; a.groups = num_key_value_groups; a.R = R;
+    a.inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (head_dim == 64) launch<64>(st, a, runs, kv_heads, static_cast<h16*>(out), lse);
+    else launch<128>(st, a, runs, kv_heads, static_cast<h16*>(out), lse);
+    return (int)hipGetLastError();
+}
+
+// ---- several query tokens of every sequence over the one copy: the rows of a (sequence, kv head) are consecutive in
+// [n_seqs, kv_heads * G, n_q, D], so the kernel's row addressing holds with G' = G * n_q q rows per (sequence, kv head)
+
+extern "C" int64_t mustafar_shared_segment_multi_workspace_bytes(int T, int kv_heads, int num_key_value_groups, int n_seqs, int n_q, int head_dim)
+{
+    using namespace mustafar_shared;
+    if (!multi_shape_ok(T, kv_heads, num_key_value_groups, n_seqs, n_q, head_dim)) return 0;
+    const int R = n_seqs * num_key_value_groups * n_q, ntb = T / 64, bpw = blocks_per_run(R < kMaxRows ? R : kMaxRows, head_dim);
+    return (int64_t)((ntb + bpw - 1) / bpw) * kv_heads * R * (head_dim + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int mustafar_decode_shared_segment_multi(void* stream, const mustafar_cache_view* k_cache, const mustafar_cache_view* v_cache, int T,
+                                                    int kv_heads, int num_key_value_groups, int n_seqs, int n_q, const void* q, void* out,
+                                                    float* lse, void* workspace, float sqrt_d, int head_dim)
+{
+    using namespace mustafar_shared;
+    if (!multi_shape_ok(T, kv_heads, num_key_value_groups, n_seqs, n_q, head_dim) || !(sqrt_d > 0.f)) return MUSTAFAR_EINVAL;
+    if (!q || !out || !lse || !workspace || !aligned16(q) || !aligned16(out) || ((uintptr_t)lse & 3) || !aligned16(workspace))
+        return MUSTAFAR_EINVAL;
+    SegArgs a{};
+    if (!side_of(k_cache, T, kv_heads, head_dim, &a.k) || !side_of(v_cache, T, kv_heads, head_dim, &a.v)) return MUSTAFAR_EINVAL;
+    const int Gq = num_key_value_groups * n_q, R = n_seqs * Gq, ntb = T / 64, bpw = blocks_per_run(R < kMaxRows ? R : kMaxRows, head_dim);
+    const int runs = (ntb + bpw - 1) / bpw;
+    a.q = static_cast<const h16*>(q);
+    a.ws_o = static_cast<float*>(workspace);
+    a.ws_ml = a.ws_o + (int64_t)runs * kv_heads * R * head_dim;
+    a.ntb = ntb; a.bpw = bpw; a.n_seqs = n_seqs; a.groups = Gq; a.R = R;
     a.inv_sqrt_d = (float)(1.0 / (double)sqrt_d);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (head_dim == 64) launch<64>(st, a, runs, kv_heads, static_cast<h16*>(out), lse);

@@ -645,6 +645,29 @@ class MustafarAttention:
             attention_mask = attention_mask.contiguous()
         return attention_mask
 
+    def _multi_shapes(self, what: str, query_states, key_states, value_states) -> int:
+        """The configuration and the shapes a several-token call over the live cache takes (`what`: the method the errors name) -> n_q."""
+        if self.cfg.api != "fused":
+            raise ValueError(f"{what} needs MustafarConfig(api='fused')")
+        groups = self.num_key_value_groups
+        if groups > 8:
+            raise ValueError(f"{what} serves 1 to 8 q heads per kv head (got {groups})")
+        if query_states.dim() != 4:
+            raise ValueError(f"{what}: q [bsz, {self.num_heads}, n_q, {self.head_dim}] (got {tuple(query_states.shape)})")
+        bsz, H, n_q, D = query_states.shape
+        if H != self.num_heads or D != self.head_dim or n_q < 1 or key_states.shape != (bsz, self.num_key_value_heads, n_q, D) or \
+                value_states.shape != key_states.shape:
+            raise ValueError(f"{what}: q [bsz, {self.num_heads}, n_q, {self.head_dim}] with k / v [bsz, {self.num_key_value_heads}, n_q, "
+                             f"{self.head_dim}] (got {tuple(query_states.shape)}, {tuple(key_states.shape)}, {tuple(value_states.shape)})")
+        return n_q
+
+    def _multi_fits(self, what: str, past, n_q: int) -> None:
+        """The trigger-point rule of a several-token call: a trigger point may only be its last row."""
+        fits = self.fits_before_trigger(past, n_q)
+        if fits < n_q:
+            raise ValueError(f"{what}: {n_q} tokens would step over a 256-token trigger point; at most {fits} fit in this call "
+                             "(the trigger point may only be the last row: accept() then runs the trigger)")
+
     def decode_multi(self, query_states, key_states, value_states, past, return_lse: bool = False, attention_mask=None,
                      step_counter: Optional[torch.Tensor] = None, t_device: Optional[torch.Tensor] = None,
                      t_capacity: Optional[int] = None):
@@ -674,17 +697,8 @@ class MustafarAttention:
         `step_counter`) holds the compressed tokens in use and `t_capacity` the tokens the launch is sized for (an arena that grows by
         extents, or an ExtentCache64): after a trigger, run eagerly, the caller adds 256 to `t_device` and takes 256 off the counter.
         `fits_before_trigger(past, n_q)` says when a replay would step over a trigger point."""
-        cfg = self.cfg
-        if cfg.api != "fused":
-            raise ValueError("decode_multi needs MustafarConfig(api='fused')")
         groups = self.num_key_value_groups
-        if groups > 8:
-            raise ValueError(f"decode_multi serves 1 to 8 q heads per kv head (got {groups})")
-        bsz, H, n_q, D = query_states.shape
-        if H != self.num_heads or D != self.head_dim or n_q < 1 or key_states.shape != (bsz, self.num_key_value_heads, n_q, D) or \
-                value_states.shape != key_states.shape:
-            raise ValueError(f"decode_multi: q [bsz, {self.num_heads}, n_q, {self.head_dim}] with k / v [bsz, {self.num_key_value_heads}, n_q, "
-                             f"{self.head_dim}] (got {tuple(query_states.shape)}, {tuple(key_states.shape)}, {tuple(value_states.shape)})")
+        n_q = self._multi_shapes("decode_multi", query_states, key_states, value_states)
         per = 64 // groups
         if t_device is not None and step_counter is None:
             raise ValueError("decode_multi: t_device is for captured graphs and needs step_counter (an eager call passes neither)")
@@ -695,16 +709,24 @@ class MustafarAttention:
         if step_counter is not None and n_q > per:
             raise ValueError(f"decode_multi: a replayed call (step_counter) is one library call: at most {per} tokens at {groups} q heads "
                              f"per kv head (got {n_q})")
-        fits = self.fits_before_trigger(past, n_q)
-        if fits < n_q:
-            raise ValueError(f"decode_multi: {n_q} tokens would step over a 256-token trigger point; at most {fits} fit in this call "
-                             "(the trigger point may only be the last row: accept() then runs the trigger)")
+        self._multi_fits("decode_multi", past, n_q)
         if step_counter is not None:
             return self._decode_multi_replayed(query_states, key_states, value_states, past, return_lse, attention_mask, step_counter,
                                                t_device, t_capacity)
+        out, lse, past = self._decode_multi_eager(query_states, key_states, value_states, past, attention_mask)
+        return (out, lse, past) if return_lse else (out, past)
+
+    def _decode_multi_eager(self, query_states, key_states, value_states, past, attention_mask, out=None, lse=None):
+        """The eager body of decode_multi behind its checks: consecutive library calls of at most 64 // groups tokens -> (out, lse, past').
+        out / lse (decode_multi_split): contiguous [bsz, H, n_q, D] fp16 / [bsz, H, n_q] fp32 that take the result -- a single library
+        call writes them itself, the pieces of several are copied in."""
+        bsz, _, n_q, _ = query_states.shape
+        per = 64 // self.num_key_value_groups
         kv_seq_len = Past(*past).kv_seq_len
         mask = self._multi_mask(attention_mask, bsz, n_q, kv_seq_len + n_q, query_states.device)
         past = self.to_fused(past)
+        if n_q <= per:
+            return self._decode_multi_call(query_states, key_states, value_states, past, mask, out=out, lse=lse)
         outs, lses = [], []
         for s0 in range(0, n_q, per):
             s1 = min(n_q, s0 + per)
@@ -714,10 +736,11 @@ class MustafarAttention:
             o, l, past = self._decode_multi_call(query_states[:, :, s0:s1], key_states[:, :, s0:s1], value_states[:, :, s0:s1], past, m)
             outs.append(o)
             lses.append(l)
-        out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
-        if not return_lse:
-            return out, past
-        return out, (lses[0] if len(lses) == 1 else torch.cat(lses, dim=2)), past
+        if out is None:
+            return torch.cat(outs, dim=2), torch.cat(lses, dim=2), past
+        torch.cat(outs, dim=2, out=out)
+        torch.cat(lses, dim=2, out=lse)
+        return out, lse, past
 
     def _decode_multi_replayed(self, query_states, key_states, value_states, past, return_lse, attention_mask, step_counter, t_device,
                                t_capacity):
@@ -751,11 +774,12 @@ class MustafarAttention:
         out, lse, past = self._decode_multi_call(query_states, key_states, value_states, past, mask, step_counter, t_device, T)
         return (out, lse, past) if return_lse else (out, past)
 
-    def _decode_multi_call(self, q, k_rows, v_rows, past, mask=None, step_counter=None, t_device=None, T=None):
+    def _decode_multi_call(self, q, k_rows, v_rows, past, mask=None, step_counter=None, t_device=None, T=None, out=None, lse=None):
         """One mustafar_decode_multi_query(_masked, _lengths) call: at most 64 // groups tokens, appended to the windows and counted in the
         returned past.  mask: None, or a checked view [bsz, 1, 1 or n, kv_seq_len + n] (`_multi_mask`) whose address and strides the call
         takes.  step_counter / t_device (`_decode_multi_replayed`): the lengths come from the device, the launch is sized for `T`
-        compressed tokens and the window capacity, nothing is reallocated and the past comes back with the host lengths it had."""
+        compressed tokens and the window capacity, nothing is reallocated and the past comes back with the host lengths it had.
+        out / lse: the contiguous tensors the call writes (decode_multi_split's slices), or None: allocated here."""
         past = Past(*past)
         k_c, k_w, v_c, v_w, C = past[:5]
         T = C if T is None else T
@@ -777,8 +801,9 @@ class MustafarAttention:
             raise ValueError(f"decode_multi: the library serves no call of {n} tokens x {groups} q heads per kv head, {T} compressed tokens, "
                              f"a window of {k_w.cap} rows, head_dim {D}")
         _, ws = self._scratch(dev, 0, 0, ws_bytes)
-        out = torch.empty((bsz, H, n, D), dtype=torch.float16, device=dev)
-        lse = torch.empty((bsz, H, n), dtype=torch.float32, device=dev)
+        if out is None:
+            out = torch.empty((bsz, H, n, D), dtype=torch.float16, device=dev)
+            lse = torch.empty((bsz, H, n), dtype=torch.float32, device=dev)
         args = (kv, vv, t_base, kt, vt, T, Bkv, groups, n, q.data_ptr(), k_w.buf.data_ptr(), v_w.buf.data_ptr(), kn.data_ptr(), vn.data_ptr(),
                 w_len, k_w.cap, out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D)
         with torch.cuda.device(dev):
@@ -902,6 +927,125 @@ class MustafarAttention:
             k.require_tiles()   # (a key base in token rows and a launch form that reads tiles)
         _call_decode(k, v, tokens, ops, D, None, lse)
         return ops.out, lse
+
+    # ---- several query tokens over frozen and shared segments -----------------------------------------------------------
+    def _segment_query_multi(self, what: str, query_states) -> int:
+        """What every several-token segment call checks first (`what`: the method the errors name) -> n_q."""
+        if self.cfg.api != "fused":
+            raise ValueError(f"{what} needs MustafarConfig(api='fused')")
+        if self.num_key_value_groups > 8:
+            raise ValueError(f"{what} serves 1 to 8 q heads per kv head (got {self.num_key_value_groups})")
+        if query_states.dim() != 4 or query_states.shape[1] != self.num_heads or query_states.shape[3] != self.head_dim or \
+                query_states.shape[2] < 1:
+            raise ValueError(f"{what}: query of shape {tuple(query_states.shape)} for {self.num_heads} heads of {self.head_dim} "
+                             f"([bsz, {self.num_heads}, n_q, {self.head_dim}], n_q >= 1)")
+        return query_states.shape[2]
+
+    def decode_segment_multi(self, query_states, k_cache, v_cache=None, tokens=None, attention_mask=None):
+        """partial.decode_segment_multi (documented there): n_q query tokens of every sequence over ONE frozen segment."""
+        return self._decode_segment_multi(query_states, k_cache, v_cache, tokens, attention_mask)
+
+    def _decode_segment_multi(self, query_states, k_cache, v_cache, tokens, attention_mask, out=None, lse=None):
+        """decode_segment_multi; out / lse (decode_multi_split): the contiguous [bsz, H, n_q, D] fp16 / [bsz, H, n_q] fp32 the call writes."""
+        what = "decode_segment_multi"
+        n_q = self._segment_query_multi(what, query_states)
+        if hasattr(k_cache, "_decode_multi"):   # a partial.SharedSegment: one copy for the whole batch
+            if v_cache is not None or tokens is not None:
+                raise ValueError(f"{what}: a SharedSegment carries both caches and its token count")
+            if attention_mask is not None:
+                raise ValueError(f"{what}: a shared segment takes no attention mask: its one copy is visible to every row (decode_multi_split "
+                                 "skips its columns)")
+            return k_cache._decode_multi(self, query_states, out, lse)
+        bsz, H, _, D = query_states.shape
+        groups, Bkv = self.num_key_value_groups, bsz * self.num_key_value_heads
+        if v_cache is None or tokens is None:
+            raise ValueError(f"{what}: a per-sequence segment is (k_cache, v_cache, tokens)")
+        if tokens <= 0 or tokens % 64:
+            raise ValueError(f"{what}: a segment holds a positive multiple of 64 tokens (got {tokens})")
+        if n_q * groups > 1024:
+            raise ValueError(f"{what}: at most {1024 // groups} tokens per call at {groups} q heads per kv head (got {n_q})")
+        dev = query_states.device
+        mask = self._multi_mask(attention_mask, bsz, n_q, tokens, dev, exact=False)
+        k, v = as_cache(k_cache, tokens), as_cache(v_cache, tokens)
+        if type(k) is not type(v) or k.total_tokens != tokens or v.total_tokens != tokens:
+            raise ValueError(f"{what}: the caches hold {k.total_tokens} / {v.total_tokens} tokens, not {tokens}")
+        if query_states.dtype != torch.float16 or not query_states.is_cuda:
+            raise ValueError(f"{what}: the query is a float16 tensor on the GPU (got {query_states.dtype} on {query_states.device})")
+        q = query_states.contiguous()
+        (kv, vv, t_base, kt, vt), keep = k.view_args(v, tables=tokens > k.tokens)   # (an arena is poll()ed, a key base in rows retiled)
+        L = _lib.load()
+        ws_bytes = L.mustafar_decode_multi_segment_workspace_bytes(tokens, Bkv, groups, n_q, D)
+        if ws_bytes <= 0:
+            raise ValueError(f"{what}: the library serves no call of {n_q} tokens x {groups} q heads per kv head over {tokens} tokens, head_dim {D}")
+        _, ws = self._scratch(dev, 0, 0, ws_bytes)
+        if out is None:
+            out = torch.empty((bsz, H, n_q, D), dtype=torch.float16, device=dev)
+            lse = torch.empty((bsz, H, n_q), dtype=torch.float32, device=dev)
+        margs = (None, 0, 0, 1, 1)
+        if mask is not None:   # one plane per sequence: its kv heads share it
+            margs = (mask.data_ptr(), mask.stride(0), mask.stride(2), mask.shape[2], self.num_key_value_heads)
+        with torch.cuda.device(dev):
+            err = L.mustafar_decode_multi_segment(torch.cuda.current_stream(dev).cuda_stream, kv, vv, t_base, kt, vt, tokens, Bkv, groups, n_q,
+                                                  q.data_ptr(), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), math.sqrt(D), D, *margs)
+        _lib.check(err, "mustafar_decode_multi_segment")
+        del keep, q, mask   # (alive until here: the call has been issued)
+        return out, lse
+
+    def decode_multi_split(self, query_states, key_states, value_states, past, frozen, attention_mask=None, return_lse: bool = False):
+        """decode_multi over frozen compressed segments + the live cache: n_q tokens of every sequence, q [bsz, H, n_q, D] with their new
+        k / v [bsz, Hkv, n_q, D] -> (out [bsz, H, n_q, D], past'), or (out, lse fp32 [bsz, H, n_q], past') with `return_lse`.  `frozen` is
+        what decode_split takes: `(k_cache, v_cache, tokens)` tuples that precede the live cache in sequence order and / or
+        `partial.SharedSegment`s.  Every query token sees ALL tokens of every frozen entry (they precede the new tokens: no causal limit
+        there) and the live cache as in decode_multi.  One call per frozen entry over all n_q tokens at once
+        (mustafar_decode_shared_segment_multi / mustafar_decode_multi_segment), decode_multi(return_lse=True) on `past` -- its trigger-point
+        rule and its chunking by 64 // groups tokens apply to the live call as they do there --, then ONE mustafar_merge_attention_states
+        over the flat bsz * H * n_q rows.  The stacked outputs and LSEs of the parts are allocated once and every call writes its own slice.
+
+        past': exactly what decode_multi returns for the live cache alone -- rows appended, nothing compressed: close it with `accept()`
+        (rejected=, keep=, the trigger).
+
+        attention_mask: additive fp16 [bsz, 1, 1 or n_q, frozen tokens + kv_seq_len + n_q], the frozen entries' columns first, in order
+        (those of SharedSegments included).  Each per-sequence entry and the live call read their own column slice; the columns of a
+        shared entry are NEVER read -- one copy is visible to every row --, so a draft tree or left padding in the live part works next
+        to a shared prefix (decode_split refuses that combination and keeps doing so: there the mask has no columns for a shared entry).
+        Device-side lengths (step_counter / t_device) are not taken: one captured graph serves fixed lengths."""
+        what = "decode_multi_split"
+        n_q = self._multi_shapes(what, query_states, key_states, value_states)
+        bsz, H, _, D = query_states.shape
+        past = Past(*past)
+        frozen = list(frozen)
+        if len(frozen) > 63:
+            raise ValueError(f"{what}: at most 63 frozen entries (one merge of 64 parts; got {len(frozen)})")
+        shared = [not isinstance(f, (tuple, list)) for f in frozen]
+        tokens = [int(f.tokens) if sh else int(f[2]) for f, sh in zip(frozen, shared)]
+        total = sum(tokens) + past.kv_seq_len + n_q
+        if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[:2] != (bsz, 1) or
+                                           attention_mask.shape[2] not in (1, n_q) or attention_mask.shape[3] != total):
+            raise ValueError(f"Attention mask should be of size {(bsz, 1, n_q, total)} or {(bsz, 1, 1, total)}, but is "
+                             f"{tuple(attention_mask.size())}")
+        self._multi_fits(what, past, n_q)
+        dev, parts = query_states.device, len(frozen) + 1
+        o_all = torch.empty((parts, bsz, H, n_q, D), dtype=torch.float16, device=dev)
+        l_all = torch.empty((parts, bsz, H, n_q), dtype=torch.float32, device=dev)
+        col = 0
+        for i, (f, sh, t) in enumerate(zip(frozen, shared, tokens)):
+            if sh:   # one copy for the whole batch; its mask columns are skipped
+                f._decode_multi(self, query_states, o_all[i], l_all[i])
+            else:
+                m = attention_mask[..., col:col + t] if attention_mask is not None else None
+                self._decode_segment_multi(query_states, f[0], f[1], t, m, o_all[i], l_all[i])
+            col += t
+        m = attention_mask[..., col:] if attention_mask is not None else None
+        _, _, new = self._decode_multi_eager(query_states, key_states, value_states, past, m, o_all[-1], l_all[-1])
+        out = torch.empty((bsz, H, n_q, D), dtype=torch.float16, device=dev)
+        lse = torch.empty((bsz, H, n_q), dtype=torch.float32, device=dev) if return_lse else None
+        rows = bsz * H * n_q
+        with torch.cuda.device(dev):
+            err = _lib.load().mustafar_merge_attention_states(torch.cuda.current_stream(dev).cuda_stream, o_all.data_ptr(), rows * D,
+                                                              l_all.data_ptr(), rows, parts, rows, D, out.data_ptr(),
+                                                              lse.data_ptr() if return_lse else None)
+        _lib.check(err, "mustafar_merge_attention_states")
+        return (out, lse, new) if return_lse else (out, new)
 
     # ---- head_dim 64 over a cache that grows by extents (MustafarConfig(hd64_extents=True); cache64.py) ---------------------------------
     def _run_triggers_ext64(self, pasts):

@@ -11,7 +11,9 @@ such states over disjoint token sets combine exactly into the attention over the
 every sequence of the batch (a system prompt, a document several requests ask about, n samples of one prompt): `decode_segment` reads
 it through `mustafar_decode_shared_segment`, which expands each block once and serves all rows of a kv head on the matrix pipe
 (DESIGN.md 4.10).  `MustafarAttention.decode_split` strings them together with the
-live cache.  No CPU fallback: both are calls into libmustafar_hip.so.  This is the top layer: it imports hook.py, nothing imports it.
+live cache.  `decode_segment_multi` / `SharedSegment.decode_multi` are the same calls for n_q query tokens of every sequence at once
+(mustafar_decode_multi_segment, mustafar_decode_shared_segment_multi), strung together with `decode_multi` by
+`MustafarAttention.decode_multi_split`.  No CPU fallback: all are calls into libmustafar_hip.so.  This is the top layer: it imports hook.py, nothing imports it.
 """
 from __future__ import annotations
 
@@ -72,6 +74,17 @@ class SharedSegment:
         attn._segment_query(query_states)
         return _decode_shared(attn, query_states, self)
 
+    def decode_multi(self, attn, query_states: torch.Tensor):
+        """decode_segment_multi(attn, query_states, self): n_q query tokens of every sequence, q [bsz, H, n_q, D] (n_q >= 1) -> (out
+        [bsz, H, n_q, D], lse fp32 [bsz, H, n_q]); every row sees the whole segment.  One mustafar_decode_shared_segment_multi call serves
+        up to 1024 rows per kv head (bsz x groups x n_q); more run as consecutive calls over whole sequences."""
+        attn._segment_query_multi("decode_segment_multi", query_states)
+        return _decode_shared_multi(attn, query_states, self)
+
+    def _decode_multi(self, attn, query_states: torch.Tensor, out=None, lse=None):
+        """What MustafarAttention.decode_multi_split calls for an entry that is no tuple: `decode_multi` into the caller's tensors."""
+        return _decode_shared_multi(attn, query_states, self, out, lse)
+
     @classmethod
     def from_dense(cls, attn, key_states: torch.Tensor, value_states: torch.Tensor) -> "SharedSegment":
         """key_states / value_states [1, kv_heads, t, D] (t % 64 == 0): pruned at the hook's sparsities and converted."""
@@ -119,6 +132,56 @@ def _decode_shared(attn, query_states: torch.Tensor, seg: SharedSegment):
                                                    lse.data_ptr() + s0 * H * 4, ws.data_ptr(), math.sqrt(D), D)
             _lib.check(err, "mustafar_decode_shared_segment")
     return out, lse
+
+
+def _decode_shared_multi(attn, query_states: torch.Tensor, seg: SharedSegment, out=None, lse=None):
+    """decode_segment_multi over a SharedSegment: one launch pair per 1024 // (groups x n_q) sequences.  out / lse: contiguous
+    [bsz, H, n_q, D] fp16 / [bsz, H, n_q] fp32 to write, or None: allocated here."""
+    bsz, H, n_q, D = query_states.shape
+    groups = attn.num_key_value_groups
+    what = "decode_segment_multi"
+    if seg.kv_heads != attn.num_key_value_heads:
+        raise ValueError(f"{what}: the shared segment holds {seg.kv_heads} heads, the attention has {attn.num_key_value_heads} kv heads")
+    if groups * n_q > 1024:
+        raise ValueError(f"{what}: at most {1024 // groups} tokens per call at {groups} q heads per kv head (got {n_q})")
+    if query_states.dtype != torch.float16 or not query_states.is_cuda:
+        raise ValueError(f"{what}: the query is a float16 tensor on the GPU (got {query_states.dtype} on {query_states.device})")
+    dev = query_states.device
+    L = _lib.load()
+    q = query_states if query_states.is_contiguous() else query_states.contiguous()
+    if out is None:
+        out = torch.empty((bsz, H, n_q, D), dtype=torch.float16, device=dev)
+        lse = torch.empty((bsz, H, n_q), dtype=torch.float32, device=dev)
+    per = 1024 // (groups * n_q)
+    kv, vv = seg.view_ptrs()
+    # (the slab count is not monotonic in the rows: a short last call may run shorter runs and leave more slabs than a full one)
+    ws_bytes = max(L.mustafar_shared_segment_multi_workspace_bytes(seg.tokens, seg.kv_heads, groups, n, n_q, D)
+                   for n in {min(bsz, per), bsz % per or min(bsz, per)})
+    _, ws = attn._scratch(dev, 0, 0, ws_bytes)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for s0 in range(0, bsz, per):   # (launches on one stream run in order: the calls share the workspace)
+            n, row = min(per, bsz - s0), s0 * H * n_q
+            err = L.mustafar_decode_shared_segment_multi(st, kv, vv, seg.tokens, seg.kv_heads, groups, n, n_q, q.data_ptr() + row * D * 2,
+                                                         out.data_ptr() + row * D * 2, lse.data_ptr() + row * 4, ws.data_ptr(),
+                                                         math.sqrt(D), D)
+            _lib.check(err, "mustafar_decode_shared_segment_multi")
+    return out, lse
+
+
+def decode_segment_multi(attn, query_states: torch.Tensor, k_cache, v_cache=None, tokens: Optional[int] = None,
+                         attention_mask: Optional[torch.Tensor] = None):
+    """decode_segment for n_q query tokens of every sequence at once (drafted tokens to verify, a short follow-up turn): attention over
+    ONE frozen compressed segment and nothing else; query_states [bsz, num_heads, n_q, D], n_q >= 1.  Every query token sees every token
+    of the segment: the segment precedes them all, there is no causal limit.
+
+    `decode_segment_multi(attn, q, segment)` with a SharedSegment: the one copy serves every row, whatever bsz (no mask).  Otherwise
+    k_cache / v_cache / tokens are what decode_segment takes -- a reference-layout list, a CompressedArena (its extents read through its
+    tables) or an ExtentCache64, of bsz * kv_heads heads -- and n_q x groups may be up to 1024 (mustafar_decode_multi_segment).
+    attention_mask: None or additive fp16 [bsz, 1, 1 or n_q, >= tokens], column 0 = the segment's first token, one row for all query
+    tokens or one each.  Returns (out fp16 [bsz, num_heads, n_q, D], lse fp32 [bsz, num_heads, n_q]): what merge_attention_states
+    combines with other parts row by row (MustafarAttention.decode_multi_split does)."""
+    return attn.decode_segment_multi(query_states, k_cache, v_cache, tokens, attention_mask)
 
 
 def decode_segment(attn, query_states: torch.Tensor, k_cache, v_cache=None, tokens: Optional[int] = None,
