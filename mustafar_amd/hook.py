@@ -914,6 +914,11 @@ class MustafarAttention:
             raise ValueError("decode_segment: a per-sequence segment is (k_cache, v_cache, tokens)")
         if tokens <= 0 or tokens % 64:
             raise ValueError(f"decode_segment: a segment holds a positive multiple of 64 tokens (got {tokens})")
+        if isinstance(k_cache, CompressedArena) and tokens % 256:
+            # the extents entry points take an arena's base in whole 256-token blocks (mustafar_hip.h); the several-token segment call reads
+            # any multiple of 64, so a shorter tail goes there as one token
+            out, lse = self._decode_segment_multi(query_states, k_cache, v_cache, tokens, attention_mask)
+            return out, lse.reshape(bsz, H)
         if D == 128:   # the LSE comes from the one-pass forms (mustafar_hip.h)
             self._lse_served(tokens)
         k, v = as_cache(k_cache, tokens), as_cache(v_cache, tokens)
