@@ -193,7 +193,8 @@ typedef struct mustafar_cache_view {
     int64_t   idx_head_stride;
     int64_t   nz_head_stride;   /* != 0: nz_offset[h] == h * nz_head_stride (uint4 units, < 2^32): the SpMV kernels then compute
                                    the head's stream start instead of loading it (one memory latency less per wave) */
-    uint32_t  flags;            /* 0: the tile format above.  MUSTAFAR_VIEW_KEY_ROWS (ABI 113): a KEY cache held as token rows, see below */
+    uint32_t  flags;            /* 0: the tile format above.  MUSTAFAR_VIEW_KEY_ROWS (ABI 113): a KEY cache held as token rows;
+                                   MUSTAFAR_VIEW_VALUE_LISTS: a VALUE cache held as sorted channel lists, see below */
 } mustafar_cache_view;
 
 /*
@@ -227,6 +228,39 @@ int mustafar_key_rows_to_tiles(void* stream, const mustafar_cache_view* src, con
  * compressed tokens the launch is sized for; gy: B' * num_key_value_groups / 4, the head groups of its grid.  Answered from the shape
  * rule of the launch itself, with the largest window standing in for the call's own (as mustafar_decode_reads_extents does). */
 int mustafar_decode_reads_key_rows(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
+
+/*
+ * Sorted channel lists: the form the GQA-4 one-pass super-block launch reads a value BASE in.  The ABI version stays 115:
+ * callers find these symbols by name.  Made from a tile-format value cache by mustafar_value_lists_plan + mustafar_value_lists_fill and
+ * turned back, bit for bit, by mustafar_value_lists_to_tiles.  Per kv head, 64-token block and 64-channel half (channels 0..63, 64..127):
+ *   cnt[c]    the number of the block's tokens whose bitmap has channel c set (0..64; a kept +-0 is an entry)
+ *   perm[i]   the half's channels sorted by cnt descending, ties by channel ascending: lane i owns channel perm[i]; its list is that
+ *             channel's (token in block u8, value fp16) entries, tokens ascending
+ *   value row r   slots 2r, 2r + 1 of the first m_r = #{c : cnt[c] > 2r} lanes, one half2 each; the rows end at the first m_r == 0
+ *   token row j   slots 4j .. 4j + 3 of the first m_{2j} lanes, four token bytes each
+ *   word j        token row j, value row 2j, value row 2j + 1, back to back in dwords; lane i of a row at the row's start + 4 i bytes
+ * Slots behind a lane's last entry, inside a row it takes part in, hold value +0 / token 0 (tokens ascend: recognisable on the way back).
+ * A block is a 256-byte header, half 0's words, half 1's words, and zeros up to the next multiple of 16 bytes (blocks are 16-byte aligned
+ * from the head's start).  Header: bytes 0..127 perm of half 0, of half 1 (channels counted inside the half); bytes 128..191 m_0..m_31 of
+ * half 0, of half 1; bytes 192..195 u32, the dword offset of half 1 from the block's start; the rest zero.
+ * A view with MUSTAFAR_VIEW_VALUE_LISTS in `flags` names such a cache:
+ *   nz               the blocks; head h starts at h * nz_head_stride uint4 units (nz_head_stride != 0)
+ *   idx              u32 [B', idx_head_stride] block table: entry b = the dword offset of block b from the head's start, entry
+ *                    tokens / 64 the head's dwords (idx_head_stride >= tokens / 64 + 1)
+ *   bmp, nz_offset   unused (may be NULL)
+ * Only mustafar_decode_attention_view / _extents / _extents_lse_hd read such a view, and only as the value BASE of a launch for which
+ * mustafar_decode_reads_value_lists() is 1; every other entry point, and every other use, returns MUSTAFAR_EINVAL.
+ */
+#define MUSTAFAR_VIEW_VALUE_LISTS 2u
+/* Pass 1: block sizes and the block table.  src: a tile-format VALUE view of `tokens` tokens (tokens % 64 == 0) and Bp heads.
+ * table u32 [Bp][tokens / 64 + 1] and head_dwords i64 [Bp] (each head's size in dwords) are written; the caller reads head_dwords to size `nz`. */
+int mustafar_value_lists_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_dwords);
+/* Pass 2: every block.  dst: a MUSTAFAR_VIEW_VALUE_LISTS view whose idx is the table of pass 1 (idx_head_stride == tokens / 64 + 1). */
+int mustafar_value_lists_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens);
+/* Back to tiles, as mustafar_key_rows_to_tiles: bitmaps, offsets, streams (padding included) and head_total i64 [Bp], bit for bit. */
+int mustafar_value_lists_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total);
+/* Whether the launch that a fused call of this shape runs reads a value base of lists: the rule of mustafar_decode_reads_key_rows. */
+int mustafar_decode_reads_value_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
 
 /*
  * mustafar_decode_attention over a cache that GROWS BY EXTENTS (the 256-token trigger of models/llama_mustafar_kernel.py:324-398

@@ -20,7 +20,8 @@ class CacheView(ctypes.Structure):
                 ("bmp_head_stride", _i64), ("idx_head_stride", _i64), ("nz_head_stride", _i64), ("flags", ctypes.c_uint32)]
 
 
-VIEW_KEY_ROWS = 1   # MUSTAFAR_VIEW_KEY_ROWS: a key base held as token rows (cache.CompressedArena.to_key_rows)
+VIEW_KEY_ROWS = 1      # MUSTAFAR_VIEW_KEY_ROWS: a key base held as token rows (cache.CompressedArena.to_key_rows)
+VIEW_VALUE_LISTS = 2   # MUSTAFAR_VIEW_VALUE_LISTS: a value base held as sorted channel lists (cache.CompressedArena.to_value_lists)
 
 
 _view_p = ctypes.POINTER(CacheView)
@@ -83,6 +84,11 @@ SIGNATURES = {
     "mustafar_key_rows_plan": (_i32, [_vp, _view_p, _i32, _i32, _vp, _vp]),
     "mustafar_key_rows_fill": (_i32, [_vp, _view_p, _view_p, _i32, _i32]),
     "mustafar_key_rows_to_tiles": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _vp]),
+    # sorted channel lists of a value base: added at ABI 115 without a version change, detected by symbol
+    "mustafar_decode_reads_value_lists": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_uint32]),
+    "mustafar_value_lists_plan": (_i32, [_vp, _view_p, _i32, _i32, _vp, _vp]),
+    "mustafar_value_lists_fill": (_i32, [_vp, _view_p, _view_p, _i32, _i32]),
+    "mustafar_value_lists_to_tiles": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _vp]),
     "mustafar_cache_append_bitmap_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_bitmap_value": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_pack_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32]),

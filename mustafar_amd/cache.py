@@ -158,9 +158,34 @@ class CompressedArena:
         self._host_totals = None                           # pinned landing area of an asynchronous append's lengths
         self._pending = None                               # (event, tokens appended) behind an asynchronous append
         self._host_flag = None
-        self._view = _lib.CacheView(self.bmp.data_ptr(), self.nz.data_ptr(), self.idx.data_ptr(), self.nz_offset.data_ptr(),
+        self._view = _lib.CacheView(self._bmp.data_ptr(), self._nz.data_ptr(), self._idx.data_ptr(), self.nz_offset.data_ptr(),
                                     tiles, tiles + 1,
                                     nz_cap // 8 if (H * (nz_cap // 8) < 2 ** 32 and os.environ.get("MUSTAFAR_NZ_STRIDE", "1") != "0") else 0)
+
+    # ---- the arrays of the format --------------------------------------------------------------------------------------------
+    # `bmp`, `idx`, `nz` of a VALUE arena are always the tile arrays: reading them while the base is held as channel lists retiles it back
+    # first (require_tiles(): sticky, and an error under capture), as every other use of tiles does.  The lists themselves are
+    # `lists_table` / `lists_blocks`.  (A key arena in token rows shows its block table and rows under `idx` / `nz`: see key_rows.)
+    def _tile_array(self, name: str) -> torch.Tensor:
+        if self._view.flags & _lib.VIEW_VALUE_LISTS:
+            self.require_tiles()
+        return getattr(self, name)
+
+    bmp = property(lambda self: self._tile_array("_bmp"), lambda self, x: setattr(self, "_bmp", x))
+    idx = property(lambda self: self._tile_array("_idx"), lambda self, x: setattr(self, "_idx", x))
+    nz = property(lambda self: self._tile_array("_nz"), lambda self, x: setattr(self, "_nz", x))
+
+    @property
+    def lists_table(self) -> torch.Tensor:
+        """The block table of a value base held as channel lists: int32 [H, tokens / 64 + 1], dword offsets."""
+        assert self.value_lists
+        return self._idx
+
+    @property
+    def lists_blocks(self) -> torch.Tensor:
+        """The blocks of a value base held as channel lists: fp16 [H, 2 x dwords per head]."""
+        assert self.value_lists
+        return self._nz
 
     # ---- token-row key blocks (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS) -------------------------------------
     @property
@@ -205,6 +230,47 @@ class CompressedArena:
         self._used = used
         return True
 
+    # ---- sorted channel lists of a value base (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS) -----------------------------
+    @property
+    def value_lists(self) -> bool:
+        """True while the base of this VALUE arena is held as sorted channel lists (`lists_table`, `lists_blocks`; the tile arrays are
+        released); only the GQA-4 one-pass super-block launch reads it.  Everything else calls `require_tiles()` first -- reading
+        `bmp` / `idx` / `nz` included."""
+        return bool(self._view.flags & _lib.VIEW_VALUE_LISTS)
+
+    def to_value_lists(self) -> bool:
+        """`to_key_rows()` for a value arena: the base from tiles to sorted channel lists on the device, in place of the tile arrays.
+        One small host read (the heads' sizes).  False, and nothing changed, where this arena cannot take the form."""
+        if self.value_lists:
+            return True
+        if self.which != "value" or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
+            return False
+        used = self.used   # (resolves an asynchronous append still in flight)
+        H, nb, dev = self.heads, self.tokens // 64, self.device
+        L = _lib.load()
+        table = torch.empty((H, nb + 1), dtype=torch.int32, device=dev)
+        head_dwords = torch.empty(H, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(L.mustafar_value_lists_plan(st, ctypes.byref(self._view), H, self.tokens, table.data_ptr(), head_dwords.data_ptr()),
+                       "mustafar_value_lists_plan")
+            counts = head_dwords.cpu()
+            stride_dwords = _round_up(int(counts.max()), 4)
+            blocks = torch.empty((H, stride_dwords * 2), dtype=torch.float16, device=dev)
+            view = _lib.CacheView(None, blocks.data_ptr(), table.data_ptr(), None, 0, nb + 1, stride_dwords // 4, _lib.VIEW_VALUE_LISTS)
+            _lib.check(L.mustafar_value_lists_fill(st, ctypes.byref(self._view), ctypes.byref(view), H, self.tokens), "mustafar_value_lists_fill")
+        # (the tile arrays are released behind the launch that read them: the allocator is stream-ordered)
+        self._tile_caps = (self.cap_tokens, self.nz_cap)
+        self._row_counts = counts
+        self._buf = None
+        self.bmp = torch.empty((H, 0), dtype=torch.int64, device=dev)
+        self.idx, self.nz = table, blocks
+        self.nz_offset = self.nz_offset.clone()
+        self._totals, self._overflow = self._totals.clone(), self._overflow.clone()
+        self._view = view
+        self._used = used
+        return True
+
     keep_tiles = False   # set by require_tiles(): to_fused() does not retile this arena into rows again (no ping-pong between a caller's
                          # decode_fused and decode_multi / shared-segment calls); consolidate() clears it for its result
 
@@ -212,19 +278,23 @@ class CompressedArena:
         """Back to the tile format on the device, bit for bit what `to_key_rows()` started from (same row capacity, same stream regions;
         the addresses are new).  Nothing to do for an arena in tiles.  Raises under stream capture: a captured graph holds the addresses.
         sticky: the arena then stays in tiles (`keep_tiles`) -- whoever needed tiles once will need them again."""
-        if not self.key_rows:
+        if not self.key_rows and not self.value_lists:
             return
         self.keep_tiles = sticky
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("CompressedArena.require_tiles: the key base is held as token rows and this call needs tiles; the retile cannot run "
-                               "under graph capture (call require_tiles() before the capture, or MustafarConfig(key_rows=False))")
-        used, tokens, rows_view, keep = self._used, self.tokens, self._view, (self.idx, self.nz)
+            raise RuntimeError("CompressedArena.require_tiles: the base is held as token rows / channel lists and this call needs tiles; the retile "
+                               "cannot run under graph capture (call require_tiles() before the capture, or MustafarConfig(key_rows=False, "
+                               "value_lists=False))")
+        L = _lib.load()
+        to_tiles, what = (L.mustafar_key_rows_to_tiles, "mustafar_key_rows_to_tiles") if self.key_rows else \
+            (L.mustafar_value_lists_to_tiles, "mustafar_value_lists_to_tiles")
+        used, tokens, rows_view, keep = self._used, self.tokens, self._view, (self._idx, self._nz)
         self._alloc(*self._tile_caps)
         self._init_empty()
         with torch.cuda.device(self.device):
-            err = _lib.load().mustafar_key_rows_to_tiles(torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(rows_view),
-                                                         ctypes.byref(self._view), self.heads, tokens, self._totals.data_ptr())
-        _lib.check(err, "mustafar_key_rows_to_tiles")
+            err = to_tiles(torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(rows_view),
+                           ctypes.byref(self._view), self.heads, tokens, self._totals.data_ptr())
+        _lib.check(err, what)
         del keep
         self.used, self.tokens = used, tokens
 
@@ -291,19 +361,23 @@ class CompressedArena:
         return (self.view_ptr(), v_arena.view_ptr(), self.tokens, kt, vt), ()
 
     def view_args(self, v_arena: "CompressedArena", tables: bool):
-        """`decode_args` for the calls that take views of TILES (multi-query, shared segment): a key base in token rows is retiled back."""
+        """`decode_args` for the calls that take views of TILES (multi-query, shared segment): a key base in token rows and a value base in channel
+        lists are retiled back."""
         self.require_tiles()
+        v_arena.require_tiles()
         return self.decode_args(v_arena, tables)
 
     def bytes_in_use(self) -> int:
         ext = sum(e.bytes_in_use() for e in self.extents)
         if self.key_rows:   # the block table + every head's rows of 256 bytes
             return self.heads * (self.tokens // 64) * 4 + int(self._row_counts.sum()) * 256 + ext
+        if self.value_lists:   # the block table + every head's blocks
+            return self.heads * (self.tokens // 64 + 1) * 4 + int(self._row_counts.sum()) * 4 + ext
         t = self.tokens * self.TILES_PER_TOKEN
         return self.heads * (t * 8 + (t + 1) * 4 + 4) + int(self.used.sum()) * 2 + ext
 
     def bytes_reserved(self) -> int:
-        own = sum(x.numel() * x.element_size() for x in (self.bmp, self.idx, self.nz, self.nz_offset))
+        own = sum(x.numel() * x.element_size() for x in (self._bmp, self._idx, self._nz, self.nz_offset))
         return own + sum(e.bytes_reserved() for e in self.extents) + (self._ext_table.numel() if self._ext_table is not None else 0)
 
     # ---- growth by extents (module docstring) ------------------------------------------------------------------
@@ -321,7 +395,7 @@ class CompressedArena:
 
     def signature(self) -> tuple:
         """Addresses a captured decode graph holds for this cache (extents are found through the table at run time)."""
-        return (self.bmp.data_ptr(), self.nz.data_ptr(), self.idx.data_ptr(), self.tokens, self.ext_table.data_ptr())
+        return (self._bmp.data_ptr(), self._nz.data_ptr(), self._idx.data_ptr(), self.tokens, self.ext_table.data_ptr())
 
     def _list_extent(self, ext: "CompressedArena") -> None:
         i = len(self.extents)
@@ -579,6 +653,7 @@ class CompressedArena:
         if k_arena.extents or v_arena.extents:
             raise RuntimeError("append_window_pair: the cache has grown by extents; append_extent_pair() or consolidate()")
         k_arena.require_tiles()   # (an append in place writes tiles behind tiles)
+        v_arena.require_tiles()
         for x in (k_rows, v_rows):
             if x.dtype != torch.float16 or x.dim() != 4 or x.shape[0] * x.shape[1] != heads or x.shape[3] != 128 or x.shape[2] < t \
                     or not x.is_contiguous():

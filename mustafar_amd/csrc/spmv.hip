@@ -30,6 +30,7 @@
 
 #include "../../include/mustafar_hip.h"
 #include "headdim64.h"
+#include "value_lists.h"
 
 namespace {
 
@@ -2733,7 +2734,97 @@ __device__ __forceinline__ void key_rows_phase(const unsigned char* __restrict__
     }
 }
 
-template <int ENG, bool EXT = false, int G = 4, bool MASK = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
+// ---- value phase over SORTED CHANNEL LISTS (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS; value_lists.h).  Lane i = the channel perm[i]
+// of the wave's half; a WORD is a token row (4 token bytes per lane) and the two value rows that go with it (a half2 per lane each): three
+// loads per wave at scalar word offset + lane offset, then per slot one shift of its token byte, one ds_read_b64 of the pair's e table
+// ([64 tokens][4 heads] fp16 in LDS) and four v_fma_mix.  No bitmap, no rank, no zeroing, no EXEC switch, no staging of the stream.  A half
+// block is a buffer of its own; a lane at or beyond a row's width (the rows narrow as the shorter lists end) asks for an address beyond every
+// buffer and gets zeros: token 0, value +0, which add +0.  The widths come from the block header, one dword per lane, loaded a phase ahead
+// and read with v_readlane: no scalar load inside the phase.  Blocks A and B are walked side by side on accumulators of their own (their
+// lanes own different channels), the next two words requested while the current two are multiplied.  Exact fp16 x fp16 products.
+// A half block as a buffer of its own.  lists: the head's blocks; start / end: the block's table entries (dwords); hdr: the block header,
+// dword `lane` (0: no block -- an empty buffer)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t value_list_buffer(const unsigned char* __restrict__ lists, uint32_t start, uint32_t end, uint32_t hdr, int odd)
+{
+    const uint32_t half1 = (uint32_t)__builtin_amdgcn_readlane((int)hdr, kVlHalf1Dword);
+    const uint32_t first = odd ? half1 : (uint32_t)kVlHeaderDwords, last = odd ? end - start : half1;
+    const bool any = half1 >= (uint32_t)kVlHeaderDwords && last >= first;   // (a header that is none: an empty buffer)
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(lists + 4ull * (start + first)), (short)0, any ? (int)(4u * (last - first)) : 0, 0x00020000);
+}
+// wsel: the lane of hdr that holds the widths of the half's rows 0..3 (the seven behind it: the rows up to 31)
+__device__ __forceinline__ int value_list_words(uint32_t hdr, int wsel, int lane)
+{
+    // a word exists where its token row has lanes: bytes 0 and 2 of the eight width dwords
+    const bool mine = lane >= wsel && lane < wsel + kVlMaxRows / 4;
+    return __popcll(__ballot(mine && (hdr & 0xffu))) + __popcll(__ballot(mine && (hdr & 0xff0000u)));
+}
+// word j of the half at dword `off` (advanced): lanes beyond a row's width read nothing
+__device__ __forceinline__ KeyRowWord value_list_word(__amdgpu_buffer_rsrc_t buf, uint32_t hdr, int wsel, int j, int& off, int lane, int lane4)
+{
+    constexpr int kStreamAux = 2, kNowhere = 0x40000000;
+    const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)hdr, wsel + (j >> 1));
+    const uint32_t mm = (j & 1) ? d >> 16 : d & 0xffffu;
+    const int m0 = mm & 0xffu, m1 = mm >> 8;
+    const int at0 = lane < m0 ? lane4 : kNowhere, at1 = lane < m1 ? lane4 : kNowhere;
+    KeyRowWord r;
+    r.ch = __builtin_amdgcn_raw_buffer_load_b32(buf, at0, 4 * off, kStreamAux);
+    r.v0 = __builtin_amdgcn_raw_buffer_load_b32(buf, at0, 4 * (off + m0), kStreamAux);
+    r.v1 = __builtin_amdgcn_raw_buffer_load_b32(buf, at1, 4 * (off + 2 * m0), kStreamAux);
+    off += 2 * m0 + m1;
+    return r;
+}
+// the channel lane `lane` of the half owns (hdr == 0: no block, every lane its own channel)
+__device__ __forceinline__ int value_list_channel(uint32_t hdr, bool active, int odd, int lane)
+{
+    const uint32_t d = (uint32_t)__shfl((int)hdr, kVlPermByte / 4 + odd * 16 + (lane >> 2), 64);
+    return active ? (int)((d >> (8 * (lane & 3))) & 63u) : lane;
+}
+// etab: the pair's e tables, block A's, then block B's; last: called in front of the last words
+template <class LAST>
+__device__ __forceinline__ void value_lists_phase(const unsigned char* __restrict__ lists, uint32_t startA, uint32_t endA, uint32_t hdrA, uint32_t startB,
+                                                  uint32_t endB, uint32_t hdrB, int odd, int lane, const unsigned char* etab, float (&accA)[4],
+                                                  float (&accB)[4], const LAST& last)
+{
+    const int lane4 = lane * 4, wsel = kVlWidthByte / 4 + odd * (kVlMaxRows / 4);
+    const __amdgpu_buffer_rsrc_t bufA = value_list_buffer(lists, startA, endA, hdrA, odd), bufB = value_list_buffer(lists, startB, endB, hdrB, odd);
+    const int nA = value_list_words(hdrA, wsel, lane), nB = value_list_words(hdrB, wsel, lane);
+    const int n = nA > nB ? nA : nB;   // (a block that has ended has widths of zero: its lanes add +0)
+    int offA = 0, offB = 0;
+    KeyRowWord ra = value_list_word(bufA, hdrA, wsel, 0, offA, lane, lane4), rb = value_list_word(bufB, hdrB, wsel, 0, offB, lane, lane4);
+#pragma unroll 1
+    for (int j = 0; j < n; j++) {
+        KeyRowWord na{0u, 0u, 0u}, nb{0u, 0u, 0u};
+        if (j + 1 < n) {
+            na = value_list_word(bufA, hdrA, wsel, j + 1, offA, lane, lane4);
+            nb = value_list_word(bufB, hdrB, wsel, j + 1, offB, lane, lane4);
+        } else {
+            last();
+        }
+        uint2 ea[4], eb[4];
+        key_row_q(ra.ch, etab, ea);
+        key_row_q(rb.ch, etab + 64 * 8, eb);
+        key_row_fma(ra, ea, accA);
+        key_row_fma(rb, eb, accB);
+        ra = na;
+        rb = nb;
+    }
+}
+
+// What the LISTS instantiations of the kernel below carry besides: nothing at all in the others, whose code stays what it was.
+template <bool LISTS>
+struct ValueListState {};
+template <>
+struct ValueListState<true> {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    uint32_t vent = 0;                      // the table entries of the pair's blocks: start, end of A in lanes 0, 1; of B in lanes 2, 3
+    u32x2 hdr = {0u, 0u};                   // the headers of blocks A and B, dword `lane` of each (one variable, written whole)
+    float accB[4] = {0.f, 0.f, 0.f, 0.f};   // block B's share (its lanes own other channels than block A's, which acc then holds)
+    unsigned char* etab = nullptr;          // the pair's e tables
+    bool lists = false;                     // this workgroup reads lists (one of an appended extent reads tiles)
+};
+// LISTS: the value BASE arrives as sorted channel lists (v_nz = the blocks, v_idx = the block table).  An instantiation of its own, chosen
+// by the host: the launches that read value tiles -- two blocks per workgroup among them -- keep the code they had.
+template <int ENG, bool EXT = false, int G = 4, bool MASK = false, bool LISTS = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
                                                                      // decode_onepass_leanpair_kernel; round 5 carried an uninstantiated online form here -- removed in round 6)
 __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
@@ -2742,6 +2833,7 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     int64_t k_idx_stride, uint32_t k_nz_stride, int64_t v_bmp_stride, int64_t v_idx_stride, uint32_t v_nz_stride)
 {
     static_assert(G == 4 || ENG == 0, "dot2 and the matrix pipe work on four heads; G < 4 runs v_fma_mix");
+    static_assert(!LISTS || (G == 4 && ENG != 1), "channel lists are read by the GQA-4 launches on the vector engines");
     constexpr int HW = G >= 2 ? G / 2 : 1;   // heads a wave of the pair finishes (G = 1: the even wave its one head, the odd wave none)
     constexpr int kTabBytes = ENG == 1 ? 4 * kKeyTabStride + 2 * 2 * 4 * kValTabStride : 0;   // q rows; per pair TWO e tables (blocks A, B)
     __shared__ __attribute__((aligned(16))) unsigned char smem[kWaves * kStageBytes + kTabBytes];
@@ -2820,6 +2912,9 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     constexpr bool ROWS = G == 4 && ENG != 1;
     const bool rows = ROWS && a.key_rows && !(EXT && tb0 >= a.nb0);
     const uint32_t* ktab = k_idx + (int64_t)kvh * k_idx_stride;   // (rows: the head's block table)
+    // the value base as sorted channel lists (workgroup-uniform as `rows`, and independent of it)
+    ValueListState<LISTS> vl;
+    if constexpr (LISTS) vl.lists = !(EXT && tb0 >= a.nb0);
     // ---- one body for both waves of a pair: the odd wave's half (tiles 64..127 of every block; channels 64..127 of the q rows) is a bias
     kb += odd * 64;
     ki += odd * 64;
@@ -2867,6 +2962,18 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     // address, dead until that wave's value phase, which starts behind the barriers that end every wave's key phase.  Every wave writes
     // the whole table -- the same bytes -- before it reads it: no barrier.  Lane l holds channels 2 l, 2 l + 1 of the four heads.
     const unsigned char* qtab = smem + 2 * 64 * G * 4;
+    // lists: the table entries of the pair's two blocks (start, end of A in lanes 0, 1; of B in lanes 2, 3), requested here, read in the key
+    // phase's hook.  The pair's e tables, [block A | block B][64 tokens][4 heads] fp16, lie behind the partial scores in its EVEN wave's stage
+    // window (pair 0: the q table's place): written between the two barriers of the softmax step, when every key phase is over and nothing
+    // stages a stream; the partial scores in front of them are still read then, and are left alone.
+    if constexpr (LISTS) {
+        vl.etab = smem + (wave & ~1) * kStageBytes + 2 * 64 * G * 4;
+        if (vl.lists) {
+            const uint32_t* vtab = v_idx + (int64_t)kvh * v_idx_stride;   // the head's block table
+            const int tA = pb0 < pb_end ? pb0 : tb0, tB = pb0 + 1 < pb_end ? pb0 + 1 : tA;   // (as tAc / tBc of the trip)
+            vl.vent = vtab[((lane & 2) ? tB : tA) + (lane & 1)];
+        }
+    }
     if constexpr (ROWS) {
         if (rows) {
             const uint32_t* q32 = reinterpret_cast<const uint32_t*>(a.q + (int64_t)bh0 * kD) + lane;
@@ -2903,6 +3010,13 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         // front of the LAST chunk of the phase before it (~2-3 us ahead: sooner and the lines are gone from L2 again by the time the
         // scalar loads come for them, later and the phase starts with two dependent round trips)
         auto reqVA = [&]() {   // the value side's bounds (both blocks: they are consumed as one pipeline) and block A's metadata lines
+            if constexpr (LISTS) {
+                if (vl.lists) {   // lists: the headers of both blocks, a dword per lane
+                    vl.hdr = typename ValueListState<LISTS>::u32x2{ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 0), lane * 4u),
+                                                                   ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 2), lane * 4u)};
+                    return;
+                }
+            }
             bndV = ld_at(viA, off_bnd);
             if (actB && lanesB) bndV = ld_at(viA + kTilesPerTb, off_bnd);
             pfVA = ld_at(vbA, off_bmp);
@@ -2970,6 +3084,14 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                 if constexpr (ENG == 1) {
                     *reinterpret_cast<h16*>(ptab + (h0 + j) * kValTabStride + lane * 2) = ea;
                     *reinterpret_cast<h16*>(ptab + 4 * kValTabStride + (h0 + j) * kValTabStride + lane * 2) = eb2;
+                } else if constexpr (LISTS) {
+                    if (vl.lists) {   // (block B's table is written for an absent block too -- zeros: its lanes multiply +0 by entry 0)
+                        *reinterpret_cast<h16*>(vl.etab + lane * 8 + (h0 + j) * 2) = ea;
+                        *reinterpret_cast<h16*>(vl.etab + 64 * 8 + lane * 8 + (h0 + j) * 2) = eb2;
+                    } else {
+                        eA[(h0 + j) * 64 + lane] = ea;
+                        if (actB) eB[(h0 + j) * 64 + lane] = eb2;
+                    }
                 } else {
                     eA[(h0 + j) * 64 + lane] = ea;
                     if (actB) eB[(h0 + j) * 64 + lane] = eb2;
@@ -2977,13 +3099,26 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                 l_lane[j] += (float)ea + (float)eb2;
                 m_run[j] = m_new;
             }
-            if constexpr (ENG != 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my e stores have reached L2 before the pair's scalar loads
+            // my e stores have reached L2 before the pair's scalar loads (lists: e went to LDS, and the headers are still on their way)
+            if constexpr (LISTS) { if (!vl.lists) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+            else if constexpr (ENG != 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __syncthreads();
         MUSTAFAR_PTRACE_STAMP(3);
         if (actA) {
             // (the partner read my outgoing partial scores before the barrier above; my value phase now rewrites the window)
-            if (actB) {
+            bool in_lists = false;
+            if constexpr (LISTS) in_lists = vl.lists;
+            if (in_lists) {
+                if constexpr (LISTS) {
+                    const uint32_t hdrA = vl.hdr.x, hdrB = actB ? vl.hdr.y : 0u;   // (an absent block B was addressed as block A)
+                    auto dropPrio = [&]() { if (!late_round) __builtin_amdgcn_s_setprio(0); };
+                    const uint32_t vent = vl.vent;
+                    value_lists_phase(vn, (uint32_t)__builtin_amdgcn_readlane((int)vent, 0), (uint32_t)__builtin_amdgcn_readlane((int)vent, 1), hdrA,
+                                      (uint32_t)__builtin_amdgcn_readlane((int)vent, 2), (uint32_t)__builtin_amdgcn_readlane((int)vent, 3), hdrB, odd, lane,
+                                      vl.etab, acc, vl.accB, dropPrio);
+                }
+            } else if (actB) {
                 uint32_t pfVB = 0;
                 auto reqVB = [&]() { pfVB = ld_at(vbA + kTilesPerTb, off_bmp); };
                 auto dropPrio = [&]() { if (!late_round) __builtin_amdgcn_s_setprio(0); };   // (in front of the last chunk: the trip is nearly done)
@@ -3016,9 +3151,24 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     // a pair without blocks weighs nothing; the e scale leaves here (a power of two: exact)
     const float scale_l = (mw == -INFINITY) ? 0.f : __expf(mw - M) * (ENG == 2 ? 0x1p-15f : 1.f);
     if (has_heads && lane >= h0 && lane < h0 + HW) s_l[pair * G + lane] = (lane == h0 ? l_run[0] : l_run[HW - 1]) * scale_l;   // (the wave that finished the head)
+    bool unpermute = false;
+    if constexpr (LISTS) unpermute = vl.lists;
+    if (unpermute) {   // lists: block A's lanes store at their channels, block B's add at theirs (one wave: in order)
+        if constexpr (LISTS) {
+            const int chA = value_list_channel(vl.hdr.x, pb0 < pb_end, odd, lane), chB = value_list_channel(vl.hdr.y, pb0 + 1 < pb_end, odd, lane);
 #pragma unroll
-    for (int h = 0; h < G; h++)
-        red[(wave * G + h) * 64 + lane] = acc[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+            for (int h = 0; h < 4; h++)
+                red[(wave * G + h) * 64 + chA] = acc[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int h = 0; h < 4; h++)
+                red[(wave * G + h) * 64 + chB] += vl.accB[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+        }
+    } else {
+#pragma unroll
+        for (int h = 0; h < G; h++)
+            red[(wave * G + h) * 64 + lane] = acc[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+    }
     __syncthreads();
     float* slab_o = a.ws_o + ((int64_t)blockIdx.x * a.BH + bh0) * kD;
     for (int o = threadIdx.x; o < 2 * G * 64; o += kThreads) {
@@ -3946,7 +4096,7 @@ using OnePassKernel = void (*)(const uint64_t*, const unsigned char*, const uint
                                const uint32_t*, const uint32_t*, OneArgs, int64_t, int64_t, uint32_t, int64_t, int64_t, uint32_t);
 // eng: 0 for G < 4.  ext: the EXT instantiation.  mask: the MASK instantiation (the pair form has none: it reads a.mask at run time).
 // nullptr: no such kernel -- the MHA pair and super-block launches always run EXT (decode_attention), the matrix pipe has no small form.
-inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask)
+inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask, bool lists = false)
 {
     const int row = G == 4 ? eng : G == 2 ? 3 : 4;   // GQA-4: v_fma_mix, matrix pipe, v_dot2; GQA-2; MHA
     const int col = (ext ? 2 : 0) + (mask ? 1 : 0);  // EXT = false: MASK false, true; EXT = true: MASK false, true
@@ -3971,6 +4121,12 @@ inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mas
         {decode_onepass_small_kernel<0, false, 2, false>, decode_onepass_small_kernel<0, false, 2, true>, decode_onepass_small_kernel<0, true, 2, false>, decode_onepass_small_kernel<0, true, 2, true>},
         {decode_onepass_small_kernel<0, false, 1, false>, decode_onepass_small_kernel<0, false, 1, true>, decode_onepass_small_kernel<0, true, 1, false>, decode_onepass_small_kernel<0, true, 1, true>},
     };
+    // a value base of channel lists: the super-block form, GQA-4, v_fma_mix / v_dot2 (onepass_reads_key_rows: checked by the caller)
+    static constexpr OnePassKernel kSbLists[2][4] = {
+        {decode_onepass_sb_kernel<0, false, 4, false, true>, decode_onepass_sb_kernel<0, false, 4, true, true>, decode_onepass_sb_kernel<0, true, 4, false, true>, decode_onepass_sb_kernel<0, true, 4, true, true>},
+        {decode_onepass_sb_kernel<2, false, 4, false, true>, decode_onepass_sb_kernel<2, false, 4, true, true>, decode_onepass_sb_kernel<2, true, 4, false, true>, decode_onepass_sb_kernel<2, true, 4, true, true>},
+    };
+    if (lists) return form == kFormSb && G == 4 && eng != 1 ? kSbLists[eng == 2][col] : nullptr;
     return form == kFormSmall ? kSmall[row][col] : form == kFormSb ? kSb[row][col] : kPair[row][ext ? 1 : 0];
 }
 
@@ -4109,15 +4265,17 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
     // an LSE comes from the one-pass forms' row kernels, and appended extents are read by the one-pass launch only: a call that would
     // run two launches is refused before anything is launched
     if ((c.lse || no_window || extents) && !onepass) return MUSTAFAR_EINVAL;
-    // a key base of token rows (MUSTAFAR_VIEW_KEY_ROWS): read by the super-block launch alone (checked where the shape is known); the value
-    // side has no such form, and no other flag exists
-    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS;
-    if ((c.k.flags && !key_rows) || c.v.flags || (key_rows && (!onepass || c.T <= 0))) return MUSTAFAR_EINVAL;
-    if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || !c.v.bmp || !c.v.nz || !c.v.idx || !c.v.nz_offset)) return MUSTAFAR_EINVAL;
+    // a key base of token rows (MUSTAFAR_VIEW_KEY_ROWS), a value base of sorted channel lists (MUSTAFAR_VIEW_VALUE_LISTS): read by the
+    // super-block launch alone (checked where the shape is known); no other flag exists, and neither side takes the other's
+    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS, value_lists = c.v.flags == MUSTAFAR_VIEW_VALUE_LISTS;
+    if ((c.k.flags && !key_rows) || (c.v.flags && !value_lists) || ((key_rows || value_lists) && (!onepass || c.T <= 0))) return MUSTAFAR_EINVAL;
+    if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || (!value_lists && (!c.v.bmp || !c.v.nz_offset)) || !c.v.nz || !c.v.idx))
+        return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
     if (key_rows && (c.k.idx_head_stride < tiles / 128 || c.k.nz_head_stride <= 0 || (c.k.nz_head_stride & 15) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    if (value_lists && (c.v.idx_head_stride < tiles / 128 + 1 || c.v.nz_head_stride <= 0 || c.v.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1))) ||
-                    (c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))
+                    (!value_lists && ((c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))))
         return MUSTAFAR_EINVAL;
     hipStream_t st = c.stream;
     auto qh = static_cast<const h16*>(c.q);
@@ -4139,7 +4297,7 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
         const int eng = G == 4 ? fma_engine() : 0;
         OnePassShape s;
         if (!onepass_shape(s, c.T, gy, c.window_capacity, extents, eng, onepass_knobs())) return MUSTAFAR_EINVAL;
-        if (key_rows && !onepass_reads_key_rows(s, G, eng)) return MUSTAFAR_EINVAL;
+        if ((key_rows || value_lists) && !onepass_reads_key_rows(s, G, eng)) return MUSTAFAR_EINVAL;   // (one rule for both forms)
         float* ws_ml = ws + (int64_t)(s.NS + s.nchunks) * c.Batch_Size * kD;
         OneArgs a{qh, sc, ws, ws_ml, kwin, vwin, knew, vnew, c.window_len_extra, mask, c.T, c.groups, c.Batch_Size, s.per_wg,
                   c.ld_scores, c.window_len, c.window_capacity, s.nchunks, s.win_rows, inv_sqrt_d, s.spw == 2};
@@ -4157,7 +4315,7 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
         // launches its plain G = 1 instantiation.)
         if (!extents && G == 1) a.nb0 = c.T / 64;
         const bool ext = extents || (G == 1 && s.form != kFormSmall);
-        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr);
+        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr, value_lists);
         if (!kernel) return MUSTAFAR_EINVAL;   // (no shape selects a kernel the table leaves out)
         hipExtLaunchKernelGGL(kernel, dim3(s.S1, gy + (s.win_rows < 0 ? -s.win_rows : s.win_rows)), dim3(kThreads), 0, st, ev ? ev[0] : nullptr,
                               ev ? ev[1] : nullptr, 0, c.k.bmp, kz, c.k.idx, c.k.nz_offset, c.v.bmp, vz, c.v.idx, c.v.nz_offset, a,
@@ -4455,6 +4613,11 @@ int mustafar_decode_reads_key_rows(int num_key_value_groups, int T, int gy, int 
     // (the largest window stands in for the call's own, as in mustafar_decode_reads_extents: it only matters where slabs run short)
     if (!onepass_shape(s, T, gy, kMaxWindow, false, eng, onepass_knobs())) return 0;
     return onepass_reads_key_rows(s, G, eng) ? 1 : 0;
+}
+
+int mustafar_decode_reads_value_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
+{
+    return mustafar_decode_reads_key_rows(num_key_value_groups, T, gy, ld_scores, flags);   // the same launches read both forms
 }
 
 int mustafar_profile_begin(int max_records)

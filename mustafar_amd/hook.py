@@ -87,6 +87,9 @@ class MustafarConfig:
     # (cache.CompressedArena.to_key_rows) where the launch of the call shape reads them (mustafar_decode_reads_key_rows: the one-pass
     # super-block form).  Whatever needs tiles retiles back (CompressedArena.require_tiles).  MUSTAFAR_KEY_ROWS=0 turns it off everywhere
     key_rows: bool = True
+    # The value base as sorted channel lists (cache.CompressedArena.to_value_lists), in the same launches and by the same rules
+    # (mustafar_decode_reads_value_lists).  MUSTAFAR_VALUE_LISTS=0 turns it off everywhere
+    value_lists: bool = True
     # head_dim 64, api="fused", arena=False only: the compressed cache grows by 256-token extents (cache64.py) instead of being
     # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
     hd64_extents: bool = False
@@ -329,6 +332,18 @@ class MustafarAttention:
         return cfg.key_rows and os.environ.get("MUSTAFAR_KEY_ROWS", "1") != "0" and cfg.head_dim == 128 and \
             self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
 
+    def _reads_value_lists(self, v_c, T: int, ld: int, flags: Optional[int] = None) -> bool:
+        """`_reads_key_rows` for the value base of arena `v_c` held as sorted channel lists."""
+        groups = self.num_key_value_groups
+        if self.head_dim != 128 or groups % 4:
+            return False
+        return bool(_lib.load().mustafar_decode_reads_value_lists(groups, T, v_c.heads * (groups // 4), ld, self._flags() if flags is None else flags))
+
+    def _wants_value_lists(self) -> bool:
+        cfg = self.cfg
+        return cfg.value_lists and os.environ.get("MUSTAFAR_VALUE_LISTS", "1") != "0" and cfg.head_dim == 128 and \
+            self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
+
     def _kth(self, D: int) -> Tuple[int, int]:
         """`(kth_k, kth_v)`: the prune rule's kth (model :97) for K and V rows of D channels at the configured sparsities."""
         return compression.kth_from_sparsity(self.cfg.k_sparsity, D), compression.kth_from_sparsity(self.cfg.v_sparsity, D)
@@ -407,6 +422,12 @@ class MustafarAttention:
             T = k_c.total_tokens
             if T and self._reads_key_rows(k_c, T, _ld_scores(T + k_w.cap)):
                 k_c.to_key_rows()
+        if isinstance(v_c, CompressedArena) and not v_c.value_lists and not v_c.keep_tiles and self._wants_value_lists() and \
+                not torch.cuda.is_current_stream_capturing():
+            # the ONE place that retiles a value base into channel lists
+            T = v_c.total_tokens
+            if T and self._reads_value_lists(v_c, T, _ld_scores(T + v_w.cap)):
+                v_c.to_value_lists()
         return Past(k_c, k_w, v_c, v_w, C, L)
 
     @staticmethod
@@ -568,6 +589,8 @@ class MustafarAttention:
                 past = past._replace(k_cache=k_c, v_cache=v_c)
             if k_c.key_rows and not self._reads_key_rows(k_c, T, ops.ld, ops.flags):
                 k_c.require_tiles()   # (raises under capture: the launch form of this call reads tiles)
+            if v_c.value_lists and not self._reads_value_lists(v_c, T, ops.ld, ops.flags):
+                v_c.require_tiles()
         _call_decode(k_c, v_c, T, ops, D, t_device, lse)
         out = ops.out
         if step_counter is not None:
@@ -930,6 +953,8 @@ class MustafarAttention:
         lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
         if isinstance(k, CompressedArena) and k.key_rows and not self._reads_key_rows(k, tokens, ops.ld, ops.flags):
             k.require_tiles()   # (a key base in token rows and a launch form that reads tiles)
+        if isinstance(v, CompressedArena) and v.value_lists and not self._reads_value_lists(v, tokens, ops.ld, ops.flags):
+            v.require_tiles()
         _call_decode(k, v, tokens, ops, D, None, lse)
         return ops.out, lse
 
