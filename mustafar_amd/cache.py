@@ -39,7 +39,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -104,8 +104,36 @@ def _head_index(heads: int, device) -> torch.Tensor:
     return t
 
 
+class BaseForm(NamedTuple):
+    """A form an arena's base can be held in besides tiles: what `CompressedArena._retile()` / `require_tiles()` and the
+    hook need to know about it.  Its plan pass counts every head's storage in units (`unit_bytes` each) and fills the block table."""
+    name: str         # MustafarConfig.<name> and MUSTAFAR_<NAME> turn it off
+    which: str        # the side whose base takes the form
+    flag: int         # `flags` of its view (include/mustafar_hip.h: MUSTAFAR_VIEW_*)
+    plan: str         # the native passes: tiles -> table and the heads' units; tiles -> form; form -> tiles
+    fill: str
+    to_tiles: str
+    reads: str        # whether the launch of a call shape reads the form
+    closing: int      # 1: the table ends with an entry of the head's units
+    unit_bytes: int
+
+    def table_columns(self, nb: int) -> int:
+        return nb + self.closing
+
+    def head_bytes(self, units: int) -> int:
+        """What every head is given (the stride of the view, in whole uint4) when the fullest one holds `units`."""
+        return _round_up(units * self.unit_bytes, 16)
+
+
+KEY_ROWS = BaseForm("key_rows", "key", _lib.VIEW_KEY_ROWS, "mustafar_key_rows_plan", "mustafar_key_rows_fill", "mustafar_key_rows_to_tiles",
+                    "mustafar_decode_reads_key_rows", 0, 256)            # units: rows of 64 tokens x 4 bytes
+VALUE_LISTS = BaseForm("value_lists", "value", _lib.VIEW_VALUE_LISTS, "mustafar_value_lists_plan", "mustafar_value_lists_fill",
+                       "mustafar_value_lists_to_tiles", "mustafar_decode_reads_value_lists", 1, 4)   # units: dwords
+BASE_FORMS = (KEY_ROWS, VALUE_LISTS)
+
+
 class CompressedArena:
-    TILES_PER_TOKEN = 2   # head_dim 128 / 64
+    TILES_PER_TOKEN = 2  # head_dim 128 / 64
     MAX_EXTENTS = 512     # appended 256-token extents listed in the device table before a consolidation: 128 k tokens of generation, i.e. every
                           # length the one-pass launch serves (round 3: 64 -- a 170-ms copy of the cache every 16 k tokens at c3; the table is 28 KB)
     VIEW_BYTES = ctypes.sizeof(_lib.CacheView)
@@ -162,18 +190,29 @@ class CompressedArena:
                                     tiles, tiles + 1,
                                     nz_cap // 8 if (H * (nz_cap // 8) < 2 ** 32 and os.environ.get("MUSTAFAR_NZ_STRIDE", "1") != "0") else 0)
 
-    # ---- the arrays of the format --------------------------------------------------------------------------------------------
-    # `bmp`, `idx`, `nz` of a VALUE arena are always the tile arrays: reading them while the base is held as channel lists retiles it back
-    # first (require_tiles(): sticky, and an error under capture), as every other use of tiles does.  The lists themselves are
-    # `lists_table` / `lists_blocks`.  (A key arena in token rows shows its block table and rows under `idx` / `nz`: see key_rows.)
+    # ---- the arrays of the format, and the base forms ---------------------------------------------------------
+    @property
+    def form(self) -> Optional[BaseForm]:
+        """The form the base is held in, None in tiles.  In a form the tile arrays are released, `_idx` is the block table (int32 [H,
+        form.table_columns(tokens / 64)]), `_nz` the heads' rows / blocks (fp16 [H, nz_head_stride x 8]) and `bmp` is empty; only the GQA-4
+        one-pass super-block launch reads it, everything else calls `require_tiles()` first.  The two forms differ in what `idx` / `nz`
+        show, on purpose (the tests hold both): a KEY arena in token rows shows its table and rows there; `bmp` / `idx` / `nz` of a VALUE
+        arena are always the tile arrays -- reading them in lists is one more use of tiles and retiles back (sticky, an error under
+        capture) -- and the lists themselves are `lists_table` / `lists_blocks`."""
+        flags = self._view.flags
+        return next((f for f in BASE_FORMS if flags & f.flag), None)
+
     def _tile_array(self, name: str) -> torch.Tensor:
-        if self._view.flags & _lib.VIEW_VALUE_LISTS:
+        if self.form is VALUE_LISTS:
             self.require_tiles()
         return getattr(self, name)
 
     bmp = property(lambda self: self._tile_array("_bmp"), lambda self, x: setattr(self, "_bmp", x))
     idx = property(lambda self: self._tile_array("_idx"), lambda self, x: setattr(self, "_idx", x))
     nz = property(lambda self: self._tile_array("_nz"), lambda self, x: setattr(self, "_nz", x))
+
+    key_rows = property(lambda self: self.form is KEY_ROWS, doc="True while the base of this KEY arena is held as token rows.")
+    value_lists = property(lambda self: self.form is VALUE_LISTS, doc="True while the base of this VALUE arena is held as channel lists.")
 
     @property
     def lists_table(self) -> torch.Tensor:
@@ -187,114 +226,71 @@ class CompressedArena:
         assert self.value_lists
         return self._nz
 
-    # ---- token-row key blocks (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS) -------------------------------------
-    @property
-    def key_rows(self) -> bool:
-        """True while the base of this KEY arena is held as token rows.  Then `nz` is the rows (fp16 [H, 128 x rows per head]), `idx` the
-        block table (int32 [H, tokens / 64]) and `bmp` is empty; only the GQA-4 one-pass super-block launch reads it.  Everything else
-        calls `require_tiles()` first."""
-        return bool(self._view.flags & _lib.VIEW_KEY_ROWS)
+    def _retile(self, form: BaseForm) -> bool:
+        """Retile the base from tiles to `form` on the device, in place of the tile arrays (which are released).  One small host read
+        (the heads' counts of rows / dwords size the allocation).  False, and nothing changed, where this arena cannot take the form: an
+        arena of the other side, an empty one, one without equally spaced stream regions, or under stream capture.
+        hook.MustafarAttention.to_fused() is the only caller outside the tests."""
+        if self.form is form:
+            return True
+        if self.which != form.which or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
+            return False
+        used = self.used   # (resolves an asynchronous append still in flight)
+        H, dev = self.heads, self.device
+        columns = form.table_columns(self.tokens // 64)
+        L = _lib.load()
+        table = torch.empty((H, columns), dtype=torch.int32, device=dev)
+        head_units = torch.empty(H, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(getattr(L, form.plan)(st, ctypes.byref(self._view), H, self.tokens, table.data_ptr(), head_units.data_ptr()), form.plan)
+            counts = head_units.cpu()
+            head_bytes = form.head_bytes(int(counts.max()))
+            store = torch.empty((H, head_bytes // 2), dtype=torch.float16, device=dev)
+            view = _lib.CacheView(None, store.data_ptr(), table.data_ptr(), None, 0, columns, head_bytes // 16, form.flag)
+            _lib.check(getattr(L, form.fill)(st, ctypes.byref(self._view), ctypes.byref(view), H, self.tokens), form.fill)
+        # (the tile arrays are released behind the launch that read them: the allocator is stream-ordered)
+        self._tile_caps = (self.cap_tokens, self.nz_cap)
+        self._unit_counts = counts
+        self._buf = None
+        self.bmp = torch.empty((H, 0), dtype=torch.int64, device=dev)
+        self.idx, self.nz = table, store
+        self.nz_offset = self.nz_offset.clone()
+        self._totals, self._overflow = self._totals.clone(), self._overflow.clone()
+        self._view = view
+        self._used = used
+        return True
 
     def to_key_rows(self) -> bool:
-        """Retile the base from tiles to token rows on the device, in place of the tile arrays (which are released).  One small host
-        read (the heads' row counts size the allocation).  False, and nothing changed, where this arena cannot take the form: a value
-        arena, an empty one, one without equally spaced stream regions, or under stream capture.  hook.MustafarAttention.to_fused() is
-        the only caller outside the tests."""
-        if self.key_rows:
-            return True
-        if self.which != "key" or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
-            return False
-        used = self.used   # (resolves an asynchronous append still in flight)
-        H, nb, dev = self.heads, self.tokens // 64, self.device
-        L = _lib.load()
-        table = torch.empty((H, nb), dtype=torch.int32, device=dev)
-        head_rows = torch.empty(H, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(L.mustafar_key_rows_plan(st, ctypes.byref(self._view), H, self.tokens, table.data_ptr(), head_rows.data_ptr()),
-                       "mustafar_key_rows_plan")
-            counts = head_rows.cpu()
-            stride_rows = int(counts.max())
-            rows = torch.empty((H, stride_rows * 128), dtype=torch.float16, device=dev)
-            view = _lib.CacheView(None, rows.data_ptr(), table.data_ptr(), None, 0, nb, stride_rows * 16, _lib.VIEW_KEY_ROWS)
-            _lib.check(L.mustafar_key_rows_fill(st, ctypes.byref(self._view), ctypes.byref(view), H, self.tokens), "mustafar_key_rows_fill")
-        # (the tile arrays are released behind the launch that read them: the allocator is stream-ordered)
-        self._tile_caps = (self.cap_tokens, self.nz_cap)
-        self._row_counts = counts
-        self._buf = None
-        self.bmp = torch.empty((H, 0), dtype=torch.int64, device=dev)
-        self.idx, self.nz = table, rows
-        self.nz_offset = self.nz_offset.clone()
-        self._totals, self._overflow = self._totals.clone(), self._overflow.clone()
-        self._view = view
-        self._used = used
-        return True
-
-    # ---- sorted channel lists of a value base (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS) -----------------------------
-    @property
-    def value_lists(self) -> bool:
-        """True while the base of this VALUE arena is held as sorted channel lists (`lists_table`, `lists_blocks`; the tile arrays are
-        released); only the GQA-4 one-pass super-block launch reads it.  Everything else calls `require_tiles()` first -- reading
-        `bmp` / `idx` / `nz` included."""
-        return bool(self._view.flags & _lib.VIEW_VALUE_LISTS)
+        """`_retile()` of a key arena into token rows (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS)."""
+        return self._retile(KEY_ROWS)
 
     def to_value_lists(self) -> bool:
-        """`to_key_rows()` for a value arena: the base from tiles to sorted channel lists on the device, in place of the tile arrays.
-        One small host read (the heads' sizes).  False, and nothing changed, where this arena cannot take the form."""
-        if self.value_lists:
-            return True
-        if self.which != "value" or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
-            return False
-        used = self.used   # (resolves an asynchronous append still in flight)
-        H, nb, dev = self.heads, self.tokens // 64, self.device
-        L = _lib.load()
-        table = torch.empty((H, nb + 1), dtype=torch.int32, device=dev)
-        head_dwords = torch.empty(H, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(L.mustafar_value_lists_plan(st, ctypes.byref(self._view), H, self.tokens, table.data_ptr(), head_dwords.data_ptr()),
-                       "mustafar_value_lists_plan")
-            counts = head_dwords.cpu()
-            stride_dwords = _round_up(int(counts.max()), 4)
-            blocks = torch.empty((H, stride_dwords * 2), dtype=torch.float16, device=dev)
-            view = _lib.CacheView(None, blocks.data_ptr(), table.data_ptr(), None, 0, nb + 1, stride_dwords // 4, _lib.VIEW_VALUE_LISTS)
-            _lib.check(L.mustafar_value_lists_fill(st, ctypes.byref(self._view), ctypes.byref(view), H, self.tokens), "mustafar_value_lists_fill")
-        # (the tile arrays are released behind the launch that read them: the allocator is stream-ordered)
-        self._tile_caps = (self.cap_tokens, self.nz_cap)
-        self._row_counts = counts
-        self._buf = None
-        self.bmp = torch.empty((H, 0), dtype=torch.int64, device=dev)
-        self.idx, self.nz = table, blocks
-        self.nz_offset = self.nz_offset.clone()
-        self._totals, self._overflow = self._totals.clone(), self._overflow.clone()
-        self._view = view
-        self._used = used
-        return True
+        """`_retile()` of a value arena into sorted channel lists (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS)."""
+        return self._retile(VALUE_LISTS)
 
     keep_tiles = False   # set by require_tiles(): to_fused() does not retile this arena into rows again (no ping-pong between a caller's
                          # decode_fused and decode_multi / shared-segment calls); consolidate() clears it for its result
 
     def require_tiles(self, sticky: bool = True) -> None:
-        """Back to the tile format on the device, bit for bit what `to_key_rows()` started from (same row capacity, same stream regions;
+        """Back to the tile format on the device, bit for bit what `_retile()` started from (same row capacity, same stream regions;
         the addresses are new).  Nothing to do for an arena in tiles.  Raises under stream capture: a captured graph holds the addresses.
         sticky: the arena then stays in tiles (`keep_tiles`) -- whoever needed tiles once will need them again."""
-        if not self.key_rows and not self.value_lists:
+        form = self.form
+        if form is None:
             return
         self.keep_tiles = sticky
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("CompressedArena.require_tiles: the base is held as token rows / channel lists and this call needs tiles; the retile "
                                "cannot run under graph capture (call require_tiles() before the capture, or MustafarConfig(key_rows=False, "
                                "value_lists=False))")
-        L = _lib.load()
-        to_tiles, what = (L.mustafar_key_rows_to_tiles, "mustafar_key_rows_to_tiles") if self.key_rows else \
-            (L.mustafar_value_lists_to_tiles, "mustafar_value_lists_to_tiles")
-        used, tokens, rows_view, keep = self._used, self.tokens, self._view, (self._idx, self._nz)
+        used, tokens, form_view, keep = self._used, self.tokens, self._view, (self._idx, self._nz)
         self._alloc(*self._tile_caps)
         self._init_empty()
         with torch.cuda.device(self.device):
-            err = to_tiles(torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(rows_view),
-                           ctypes.byref(self._view), self.heads, tokens, self._totals.data_ptr())
-        _lib.check(err, what)
+            err = getattr(_lib.load(), form.to_tiles)(torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(form_view),
+                                                      ctypes.byref(self._view), self.heads, tokens, self._totals.data_ptr())
+        _lib.check(err, form.to_tiles)
         del keep
         self.used, self.tokens = used, tokens
 
@@ -369,10 +365,9 @@ class CompressedArena:
 
     def bytes_in_use(self) -> int:
         ext = sum(e.bytes_in_use() for e in self.extents)
-        if self.key_rows:   # the block table + every head's rows of 256 bytes
-            return self.heads * (self.tokens // 64) * 4 + int(self._row_counts.sum()) * 256 + ext
-        if self.value_lists:   # the block table + every head's blocks
-            return self.heads * (self.tokens // 64 + 1) * 4 + int(self._row_counts.sum()) * 4 + ext
+        form = self.form
+        if form is not None:   # the block table + every head's rows / blocks
+            return self.heads * form.table_columns(self.tokens // 64) * 4 + int(self._unit_counts.sum()) * form.unit_bytes + ext
         t = self.tokens * self.TILES_PER_TOKEN
         return self.heads * (t * 8 + (t + 1) * 4 + 4) + int(self.used.sum()) * 2 + ext
 

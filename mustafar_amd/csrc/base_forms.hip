@@ -1,0 +1,398 @@
+// base_forms.hip -- the retile passes between the tile format of an arena's base and the two forms the GQA-4 one-pass super-block launch
+// reads instead (include/mustafar_hip.h): token rows of a KEY base (MUSTAFAR_VIEW_KEY_ROWS, ABI 113; arithmetic: key_rows.h)
+// and sorted channel lists of a VALUE base (MUSTAFAR_VIEW_VALUE_LISTS; arithmetic: value_lists.h).  head_dim 128 only.
+//
+//   tiles -> form   mustafar_<form>_plan (a number per block, then the block table by one scan per head) + mustafar_<form>_fill
+//   form -> tiles   mustafar_<form>_to_tiles: bitmaps and tile lengths, the offsets of a head by one scan, the streams
+//
+// A block in tiles is 128 tiles of 64 bits; a tile's non-zeros follow in bitmap order, padded with zeros to a multiple of 8 halfs.
+//   key     tile d = channel d of the block's 64 tokens, bit 63 - t = token t.  In rows, lane t holds token t's non-zero channels in
+//           ascending order.  One wave per block, lane = token.
+//   value   tile 64 half + t = channels 64 half .. + 63 of token t, bit 63 - c = channel c of the half.  In lists, lane rank(c) of a half
+//           holds channel c's (token, value) entries in token order.  One wave per block half, lane = channel.
+// Both directions of a form walk a lane's entries in order with one running slot counter per lane, so each is the other's inverse element
+// by element.  What a view means and which views are well formed is tile_view.h's; the two scans exist once, for both forms.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/mustafar_hip.h"
+#include "key_rows.h"
+#include "tile_view.h"
+#include "value_lists.h"
+
+namespace {
+
+constexpr int kD = kBlockTiles;
+
+__device__ __forceinline__ int wave_max_i(int v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// inclusive prefix of x over the 64 lanes
+__device__ __forceinline__ uint32_t wave_scan(uint32_t x, int l)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(x, o, 64);
+        if (l >= o) x += up;
+    }
+    return x;
+}
+
+// ---- the two scans, one wave per head
+// The block table of a form.  The per-block pass left a number per block (a width, a size); F::units(raw) is what the block takes of the
+// head's storage, F::entry(start, raw) its table entry; with F::closing the table has an entry nb, the head's units.
+struct RowsTable {   // raw = w; units = rows of 256 bytes
+    static constexpr int closing = 0;
+    static __device__ uint32_t units(uint32_t w) { return (uint32_t)kr_rows((int)w); }
+    static __device__ uint32_t entry(uint32_t first_row, uint32_t w) { return kr_entry(first_row, w); }
+};
+struct ListsTable {   // raw = units = the block's dwords; an entry is the block's start
+    static constexpr int closing = 1;
+    static __device__ uint32_t units(uint32_t n) { return n; }
+    static __device__ uint32_t entry(uint32_t start, uint32_t) { return start; }
+};
+template <class F>
+__global__ __launch_bounds__(64) void block_table_scan_kernel(int nb, uint32_t* __restrict__ table, int64_t* __restrict__ head_units)
+{
+    const int h = blockIdx.x, l = threadIdx.x;
+    uint32_t* tab = table + (int64_t)h * (nb + F::closing);
+    uint32_t run = 0;
+    for (int b0 = 0; b0 < nb; b0 += 64) {
+        const int b = b0 + l;
+        const uint32_t raw = b < nb ? tab[b] : 0u;
+        const uint32_t n = b < nb ? F::units(raw) : 0u;
+        const uint32_t inc = wave_scan(n, l);
+        if (b < nb) tab[b] = F::entry(run + inc - n, raw);
+        run += __shfl(inc, 63, 64);
+    }
+    if (l == 0) {
+        if (F::closing) tab[nb] = run;
+        head_units[h] = (int64_t)run;
+    }
+}
+
+// The way back, both forms: the tile lengths in dst.idx[h][tile + 1] -> offsets (exclusive prefix, idx[h][0] = 0), the head's stream
+// length in halfs.
+__global__ __launch_bounds__(64) void tile_offsets_scan_kernel(mustafar_cache_view dst, int nb, int64_t* __restrict__ head_total)
+{
+    const int h = blockIdx.x, l = threadIdx.x;
+    const int64_t tiles = (int64_t)nb * kD;
+    uint32_t* idx = tile_idx(dst, h, nb);
+    uint32_t run = 0;
+    if (l == 0) idx[0] = 0u;
+    for (int64_t i0 = 0; i0 < tiles; i0 += 64) {   // (tiles % 64 == 0)
+        const uint32_t inc = wave_scan(idx[i0 + l + 1], l);
+        idx[i0 + l + 1] = run + inc;
+        run += __shfl(inc, 63, 64);
+    }
+    if (l == 0 && head_total) head_total[h] = 2ll * run;
+}
+// a tile of n non-zeros takes n rounded up to 8 halfs of the stream: its length in half2 units
+__device__ __forceinline__ uint32_t tile_length(uint64_t m) { return (uint32_t)(((__popcll(m) + 7) & ~7) >> 1); }
+
+__device__ __forceinline__ uint32_t table_entry(const mustafar_cache_view& v, int h, int b) { return v.idx[(int64_t)h * v.idx_head_stride + b]; }
+
+// ================================================================ key: tiles <-> token rows
+__device__ __forceinline__ unsigned char* key_block(const mustafar_cache_view& v, int h, uint32_t ent)
+{
+    return head_bytes(v, h) + (uint64_t)kKrRowBytes * kr_first_row(ent);
+}
+__device__ __forceinline__ uint16_t& key_value(unsigned char* blk, int w, int t, int c) { return *reinterpret_cast<uint16_t*>(blk + kr_value_byte(w, t, c)); }
+
+// One wave per (block, head): the width of the block -> table[h][b] (the scan turns it into a table entry).
+__global__ __launch_bounds__(64) void key_rows_width_kernel(mustafar_cache_view src, int nb, uint32_t* __restrict__ table)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + (int64_t)b * kD;
+    int n = 0;
+    for (int d = 0; d < kD; d++) n += tile_bit(bmp[d], t);
+    const int w = max(2, (wave_max_i(n) + 1) & ~1);
+    if (t == 0) table[(int64_t)h * nb + b] = (uint32_t)w;
+}
+
+// One wave per (block, head), lane = token: the rows of the block.
+__global__ __launch_bounds__(64) void key_rows_fill_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const int64_t tile0 = (int64_t)b * kD;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(src, h, nb) + tile0;
+    const uint16_t* nz = head_stream(src, h);
+    const uint32_t ent = table_entry(dst, h, b);
+    const int w = kr_width(ent);
+    unsigned char* blk = key_block(dst, h, ent);
+    int c = 0;
+    for (int d = 0; d < kD; d++) {
+        const uint64_t m = bmp[d];
+        if (tile_bit(m, t)) {
+            key_value(blk, w, t, c) = nz[2ull * idx[d] + tile_rank(m, t)];
+            blk[kr_chan_byte(t, c)] = (unsigned char)d;
+            c++;
+        }
+    }
+    for (int p = c; p < 2 * (w >> 1); p++) key_value(blk, w, t, p) = 0;
+    for (int p = c; p < 4 * kr_words(w); p++) blk[kr_chan_byte(t, p)] = 0;
+}
+
+// One wave per (block, head): the 128 bitmaps of the block and every tile's length -> dst.idx[h][tile + 1].
+__global__ __launch_bounds__(64) void key_tiles_bitmap_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned long long bits[kD];
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    bits[t] = 0ull;
+    bits[t + 64] = 0ull;
+    __syncthreads();
+    const uint32_t ent = table_entry(src, h, b);
+    const int w = kr_width(ent);
+    unsigned char* blk = key_block(src, h, ent);
+    for (int c = 0; c < w; c++) {
+        if ((key_value(blk, w, t, c) & 0x7fffu) == 0) break;   // the slots behind a token's non-zeros hold +0
+        atomicOr(&bits[blk[kr_chan_byte(t, c)] & (kD - 1)], 1ull << (63 - t));   // (& 127: a channel byte is below 128)
+    }
+    __syncthreads();
+    const int64_t tile0 = (int64_t)b * kD;
+    uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    for (int d = t; d < kD; d += 64) {
+        const uint64_t m = bits[d];
+        bmp[d] = m;
+        idx[d + 1] = tile_length(m);
+    }
+}
+
+// One wave per (block, head), lane = token: the streams of the block's 128 tiles, padding included.
+__global__ __launch_bounds__(64) void key_tiles_stream_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const uint32_t ent = table_entry(src, h, b);
+    const int w = kr_width(ent);
+    unsigned char* blk = key_block(src, h, ent);
+    const int64_t tile0 = (int64_t)b * kD;
+    const uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    uint16_t* nz = head_stream(dst, h);
+    int c = 0;
+    for (int d = 0; d < kD; d++) {
+        const uint64_t m = bmp[d];
+        uint16_t* tile = nz + 2ull * idx[d];
+        if (tile_bit(m, t)) {
+            tile[tile_rank(m, t)] = key_value(blk, w, t, c);
+            c++;
+        }
+        const int n = __popcll(m), n8 = (n + 7) & ~7;
+        if (n + t < n8) tile[n + t] = 0;   // (at most 7 halfs of padding)
+    }
+}
+
+// ================================================================ value: tiles <-> sorted channel lists
+__device__ __forceinline__ unsigned char* list_block(const mustafar_cache_view& v, int h, int b) { return head_bytes(v, h) + 4ull * table_entry(v, h, b); }
+
+// The lists of one half (64 tiles at bmp), lane = channel c: cnt, the lane the channel's list lives in, and the row widths m[0..31] in LDS.
+struct HalfPlan {
+    int cnt, rank;
+};
+__device__ __forceinline__ HalfPlan half_plan(const uint64_t* __restrict__ bmp, int c, unsigned char* m)
+{
+    HalfPlan p{0, 0};
+    for (int t = 0; t < 64; t++) p.cnt += tile_bit(bmp[t], c);
+    for (int o = 0; o < 64; o++) {   // rank by comparison: cnt descending, ties by channel ascending
+        const int other = __shfl(p.cnt, o, 64);
+        p.rank += other > p.cnt || (other == p.cnt && o < c);
+    }
+    for (int r = 0; r < kVlMaxRows; r++) {
+        const int w = __popcll(__ballot(p.cnt > 2 * r));
+        if (c == 0) m[r] = (unsigned char)w;
+    }
+    __syncthreads();
+    return p;
+}
+
+// One wave per (block, head): the block's size in dwords -> table[h][b] (the scan turns it into the block's start).
+__global__ __launch_bounds__(64) void value_lists_size_kernel(mustafar_cache_view src, int nb, uint32_t* __restrict__ table)
+{
+    __shared__ unsigned char m[2][kVlMaxRows];
+    const int b = blockIdx.x, h = blockIdx.y, c = threadIdx.x;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + (int64_t)b * kD;
+    half_plan(bmp, c, m[0]);
+    half_plan(bmp + 64, c, m[1]);
+    if (c == 0) table[(int64_t)h * (nb + 1) + b] = (uint32_t)vl_block_dwords(vl_word_offset(m[0], kVlMaxWords), vl_word_offset(m[1], kVlMaxWords));
+}
+
+// One wave per (block half, head), lane = channel: the half's part of the header and its words.
+__global__ __launch_bounds__(64) void value_lists_fill_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned char m_first[kVlMaxRows], m[kVlMaxRows];
+    __shared__ int woff[kVlMaxWords + 1];
+    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, c = threadIdx.x;
+    const int64_t tile0 = (int64_t)b * kD + half * 64;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(src, h, nb) + tile0;
+    const uint16_t* nz = head_stream(src, h);
+    unsigned char* blk = list_block(dst, h, b);
+    int half0 = 0;
+    if (half) {   // (the second half lies behind the first: its size again)
+        half_plan(bmp - 64, c, m_first);
+        half0 = vl_word_offset(m_first, kVlMaxWords);
+    }
+    const HalfPlan p = half_plan(bmp, c, m);
+    if (c <= kVlMaxWords) woff[c] = vl_word_offset(m, c);
+    __syncthreads();
+    const int mine = woff[kVlMaxWords];
+    // header
+    blk[kVlPermByte + half * 64 + p.rank] = (unsigned char)c;
+    if (c < kVlMaxRows) blk[kVlWidthByte + half * kVlMaxRows + c] = m[c];
+    uint32_t* blk32 = reinterpret_cast<uint32_t*>(blk);
+    if (!half) {
+        if (c == 0) blk32[kVlHalf1Dword] = (uint32_t)(kVlHeaderDwords + mine);
+        if (c > 0 && c < kVlHeaderDwords - kVlHalf1Dword) blk32[kVlHalf1Dword + c] = 0u;
+    } else {
+        const int used = kVlHeaderDwords + half0 + mine;
+        if (used + c < vl_block_dwords(half0, mine)) blk32[used + c] = 0u;   // (at most three dwords of padding)
+    }
+    // lists
+    unsigned char* base = blk + 4 * (kVlHeaderDwords + half0);
+    const int i = p.rank;
+    int s = 0;
+    for (int t = 0; t < 64; t++) {
+        const uint64_t bits = bmp[t];
+        if (tile_bit(bits, c)) {
+            const int w = woff[s >> 2];
+            base[vl_token_byte(w, i, s)] = (unsigned char)t;
+            *reinterpret_cast<uint16_t*>(base + vl_value_byte(m, w, i, s)) = nz[2ull * idx[t] + tile_rank(bits, c)];
+            s++;
+        }
+    }
+    if (s & 1) *reinterpret_cast<uint16_t*>(base + vl_value_byte(m, woff[s >> 2], i, s)) = 0;
+    for (int q = s; q < vl_token_slots(s); q++) base[vl_token_byte(woff[q >> 2], i, q)] = 0;
+}
+
+// A lane's entries: slot s of lane i is an entry if the lane takes part in its rows and s == 0 or its token is not 0 (tokens ascend).
+struct HalfLists {
+    const unsigned char* base;   // the half's words
+    const unsigned char* m;      // its row widths (header bytes)
+    int chan;                    // the channel lane i owns
+};
+__device__ __forceinline__ HalfLists half_lists(const unsigned char* blk, int half, int i, int* woff)
+{
+    HalfLists L;
+    L.m = blk + kVlWidthByte + half * kVlMaxRows;
+    L.base = blk + (half ? 4ull * reinterpret_cast<const uint32_t*>(blk)[kVlHalf1Dword] : 4ull * kVlHeaderDwords);
+    L.chan = blk[kVlPermByte + half * 64 + i] & 63;
+    if (i <= kVlMaxWords) woff[i] = vl_word_offset(L.m, i);
+    __syncthreads();
+    return L;
+}
+// token of slot s of lane i, or -1 behind the lane's last entry
+__device__ __forceinline__ int list_token(const HalfLists& L, const int* woff, int i, int s)
+{
+    if (s >= 2 * kVlMaxRows || i >= L.m[s >> 1]) return -1;
+    const int t = L.base[vl_token_byte(woff[s >> 2], i, s)];
+    return (s == 0 || t != 0) ? (t & 63) : -1;
+}
+
+// One wave per (block half, head): the 64 bitmaps of the half and every tile's length -> dst.idx[h][tile + 1].
+__global__ __launch_bounds__(64) void value_tiles_bitmap_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned long long bits[64];
+    __shared__ int woff[kVlMaxWords + 1];
+    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, i = threadIdx.x;
+    bits[i] = 0ull;
+    const HalfLists L = half_lists(list_block(src, h, b), half, i, woff);
+    for (int s = 0;; s++) {
+        const int t = list_token(L, woff, i, s);
+        if (t < 0) break;
+        atomicOr(&bits[t], 1ull << (63 - L.chan));
+    }
+    __syncthreads();
+    const int64_t tile0 = (int64_t)b * kD + half * 64;
+    const uint64_t mt = bits[i];
+    tile_bmp(dst, h, nb)[tile0 + i] = mt;
+    tile_idx(dst, h, nb)[tile0 + i + 1] = tile_length(mt);
+}
+
+// One wave per (block half, head): the streams of the half's 64 tiles, padding included.
+__global__ __launch_bounds__(64) void value_tiles_stream_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ int woff[kVlMaxWords + 1];
+    const int b = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, i = threadIdx.x;
+    const HalfLists L = half_lists(list_block(src, h, b), half, i, woff);
+    const int64_t tile0 = (int64_t)b * kD + half * 64;
+    const uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    uint16_t* nz = head_stream(dst, h);
+    for (int s = 0;; s++) {
+        const int t = list_token(L, woff, i, s);
+        if (t < 0) break;
+        nz[2ull * idx[t] + tile_rank(bmp[t], L.chan)] = *reinterpret_cast<const uint16_t*>(L.base + vl_value_byte(L.m, woff[s >> 2], i, s));
+    }
+    const int n = __popcll(bmp[i]), n8 = (n + 7) & ~7;   // lane = token: its tile's padding
+    for (int p = n; p < n8; p++) nz[2ull * idx[i] + p] = 0;
+}
+
+}  // namespace
+
+// ================================================================ the entry points (include/mustafar_hip.h); every refusal is tile_view.h's
+extern "C" {
+
+int mustafar_key_rows_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_rows)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !table || !head_rows) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    key_rows_width_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, nb, table);
+    block_table_scan_kernel<RowsTable><<<Bp, 64, 0, st>>>(nb, table, head_rows);
+    return (int)hipGetLastError();
+}
+
+int mustafar_key_rows_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !key_rows_view_ok(dst, tokens) || dst->idx_head_stride != tokens / 64) return MUSTAFAR_EINVAL;
+    const int nb = tokens / 64;
+    key_rows_fill_kernel<<<dim3(nb, Bp), 64, 0, static_cast<hipStream_t>(stream)>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_key_rows_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total)
+{
+    if (!retile_shape_ok(Bp, tokens) || !key_rows_view_ok(src, tokens) || !tile_view_ok(dst, tokens) || !dst->nz_head_stride) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    key_tiles_bitmap_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
+    key_tiles_stream_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_lists_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_dwords)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !table || !head_dwords) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    value_lists_size_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, nb, table);
+    block_table_scan_kernel<ListsTable><<<Bp, 64, 0, st>>>(nb, table, head_dwords);
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_lists_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !value_lists_view_ok(dst, tokens) || dst->idx_head_stride != tokens / 64 + 1) return MUSTAFAR_EINVAL;
+    const int nb = tokens / 64;
+    value_lists_fill_kernel<<<dim3(2 * nb, Bp), 64, 0, static_cast<hipStream_t>(stream)>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_lists_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total)
+{
+    if (!retile_shape_ok(Bp, tokens) || !value_lists_view_ok(src, tokens) || !tile_view_ok(dst, tokens) || !dst->nz_head_stride) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    value_tiles_bitmap_kernel<<<dim3(2 * nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
+    value_tiles_stream_kernel<<<dim3(2 * nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -30,6 +30,8 @@
 
 #include "../../include/mustafar_hip.h"
 #include "headdim64.h"
+#include "key_rows.h"
+#include "tile_view.h"
 #include "value_lists.h"
 
 namespace {
@@ -2620,13 +2622,13 @@ __device__ __forceinline__ uint32_t ld_at(const void* __restrict__ sbase, uint32
 struct KeyRowWord {
     uint32_t ch, v0, v1;   // four channel bytes; slots 0, 1 and slots 2, 3 as half2
 };
-// A block as a buffer of its own (rows_of(w) x 256 bytes: channel rows, then value rows): a load is scalar row offset + lane offset, no
+// A block as a buffer of its own (key_rows.h: kr_rows(w) x 256 bytes, channel rows, then value rows): a load is scalar row offset + lane offset, no
 // address arithmetic.  Non-temporal as the tile stream's loads: every byte is read once.  A width that is no multiple of four (42 is
 // the common one at 70 %: 40 kept channels and one magnitude tie among a block's 64 tokens) ends in a HALF word: one value row, two slots.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t key_row_block(const unsigned char* __restrict__ rows, uint32_t ent)
 {
-    const int w = ent & 0xffu;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(rows + 256ull * (ent >> 8)), (short)0, 256 * ((w >> 1) + ((w + 3) >> 2)), 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(rows + (uint64_t)kKrRowBytes * kr_first_row(ent)), (short)0,
+                                             kKrRowBytes * kr_rows(kr_width(ent)), 0x00020000);
 }
 template <bool HALF = false>
 __device__ __forceinline__ KeyRowWord key_row_word(__amdgpu_buffer_rsrc_t blk, int nword, int wd, int lane4)
@@ -2676,7 +2678,7 @@ struct KeyRowShare {
 };
 __device__ __forceinline__ KeyRowShare key_row_share(uint32_t ent, int odd, bool active)
 {
-    const int w = ent & 0xffu, nword = (w + 3) >> 2;
+    const int w = kr_width(ent), nword = kr_words(w);
     const bool tail = (w & 3) != 0;   // (w is even: w % 4 == 2)
     const int h = nword == 1 ? 1 : tail ? nword >> 1 : (nword + 1) >> 1;
     KeyRowShare s;
@@ -4272,8 +4274,9 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
     if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || (!value_lists && (!c.v.bmp || !c.v.nz_offset)) || !c.v.nz || !c.v.idx))
         return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
-    if (key_rows && (c.k.idx_head_stride < tiles / 128 || c.k.nz_head_stride <= 0 || (c.k.nz_head_stride & 15) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
-    if (value_lists && (c.v.idx_head_stride < tiles / 128 + 1 || c.v.nz_head_stride <= 0 || c.v.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    // the form rules are tile_view.h's; here on top: the launch takes the head stride in 32 bits
+    if (key_rows && (!key_rows_view_ok(&c.k, (int)(tiles / 2)) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    if (value_lists && (!value_lists_view_ok(&c.v, (int)(tiles / 2)) || c.v.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1))) ||
                     (!value_lists && ((c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))))
         return MUSTAFAR_EINVAL;

@@ -1,5 +1,5 @@
 // value_lists.h -- the index arithmetic of sorted channel lists (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS), shared
-// by the retile kernels (value_lists.hip), the decode launch (spmv.hip) and a host program (tools/value_lists_check.cpp): plain C++, no
+// by the retile kernels (base_forms.hip), the decode launch (spmv.hip) and a host program (tools/value_lists_check.cpp): plain C++, no
 // device builtins, so that a CPU build under a sanitizer walks the same offsets the kernels do.
 //
 // A block: a 256-byte header, then half 0 (channels 0..63), then half 1 (channels 64..127), padded with zeros to 16 bytes.

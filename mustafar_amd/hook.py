@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, compression, mustafar_package
-from .cache import CompressedArena
+from .cache import KEY_ROWS, VALUE_LISTS, BaseForm, CompressedArena
 from .cache64 import ExtentCache64, compress_raw_pair_hd64
 from .compression import _compress                                                                          # noqa: F401  (re-exported)
 from .reflayout import FlatStreams, _flat_stream, append_compressed, as_cache, nz_offset_from_idxs         # noqa: F401  (re-exported)
@@ -319,30 +319,34 @@ class MustafarAttention:
         window capacity)."""
         return bool(_lib.load().mustafar_decode_reads_extents(self.num_key_value_groups, _ld_scores(columns), self._flags()))
 
-    def _reads_key_rows(self, k_c, T: int, ld: int, flags: Optional[int] = None) -> bool:
-        """Whether the launch of a fused call sized for `T` compressed tokens, with scores of pitch `ld`, reads the key base of arena
-        `k_c` as token rows."""
+    # ---- the base forms of an arena (cache.BaseForm: token rows of a key base, channel lists of a value base; DESIGN.md 3) ----------
+    def _reads_form(self, cache, T: int, ld: int, flags: Optional[int] = None, form: Optional[BaseForm] = None) -> bool:
+        """Whether the launch of a fused call sized for `T` compressed tokens, with scores of pitch `ld`, reads the base of arena `cache`
+        in `form` (default: the form it is held in)."""
         groups = self.num_key_value_groups
         if self.head_dim != 128 or groups % 4:
             return False
-        return bool(_lib.load().mustafar_decode_reads_key_rows(groups, T, k_c.heads * (groups // 4), ld, self._flags() if flags is None else flags))
+        reads = getattr(_lib.load(), (form or cache.form).reads)
+        return bool(reads(groups, T, cache.heads * (groups // 4), ld, self._flags() if flags is None else flags))
 
-    def _wants_key_rows(self) -> bool:
+    def _wants_form(self, form: BaseForm) -> bool:
         cfg = self.cfg
-        return cfg.key_rows and os.environ.get("MUSTAFAR_KEY_ROWS", "1") != "0" and cfg.head_dim == 128 and \
+        return getattr(cfg, form.name) and os.environ.get("MUSTAFAR_" + form.name.upper(), "1") != "0" and cfg.head_dim == 128 and \
             self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
 
-    def _reads_value_lists(self, v_c, T: int, ld: int, flags: Optional[int] = None) -> bool:
-        """`_reads_key_rows` for the value base of arena `v_c` held as sorted channel lists."""
-        groups = self.num_key_value_groups
-        if self.head_dim != 128 or groups % 4:
-            return False
-        return bool(_lib.load().mustafar_decode_reads_value_lists(groups, T, v_c.heads * (groups // 4), ld, self._flags() if flags is None else flags))
+    def _retile_where_read(self, cache, window, form: BaseForm) -> None:
+        """The ONE place that retiles a base into a form (to_fused()): where the launch of this cache's call shape reads it."""
+        if isinstance(cache, CompressedArena) and cache.form is None and not cache.keep_tiles and self._wants_form(form) and \
+                not torch.cuda.is_current_stream_capturing():
+            T = cache.total_tokens
+            if T and self._reads_form(cache, T, _ld_scores(T + window.cap), form=form):
+                cache._retile(form)
 
-    def _wants_value_lists(self) -> bool:
-        cfg = self.cfg
-        return cfg.value_lists and os.environ.get("MUSTAFAR_VALUE_LISTS", "1") != "0" and cfg.head_dim == 128 and \
-            self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
+    def _tiles_unless_read(self, cache, T: int, ops) -> None:
+        """Tiles, unless the launch of the call at hand (`ops`, sized for `T` compressed tokens) reads the form `cache` is held in.
+        (`require_tiles()` raises under capture.)"""
+        if isinstance(cache, CompressedArena) and cache.form is not None and not self._reads_form(cache, T, ops.ld, ops.flags):
+            cache.require_tiles()
 
     def _kth(self, D: int) -> Tuple[int, int]:
         """`(kth_k, kth_v)`: the prune rule's kth (model :97) for K and V rows of D channels at the configured sparsities."""
@@ -416,18 +420,8 @@ class MustafarAttention:
         if not isinstance(k_w, Window):
             cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
             k_w, v_w = Window(k_w, cap), Window(v_w, cap)
-        if isinstance(k_c, CompressedArena) and not k_c.key_rows and not k_c.keep_tiles and self._wants_key_rows() and \
-                not torch.cuda.is_current_stream_capturing():
-            # the ONE place that retiles a key base into token rows: where the launch of this cache's call shape reads them
-            T = k_c.total_tokens
-            if T and self._reads_key_rows(k_c, T, _ld_scores(T + k_w.cap)):
-                k_c.to_key_rows()
-        if isinstance(v_c, CompressedArena) and not v_c.value_lists and not v_c.keep_tiles and self._wants_value_lists() and \
-                not torch.cuda.is_current_stream_capturing():
-            # the ONE place that retiles a value base into channel lists
-            T = v_c.total_tokens
-            if T and self._reads_value_lists(v_c, T, _ld_scores(T + v_w.cap)):
-                v_c.to_value_lists()
+        self._retile_where_read(k_c, k_w, KEY_ROWS)
+        self._retile_where_read(v_c, v_w, VALUE_LISTS)
         return Past(k_c, k_w, v_c, v_w, C, L)
 
     @staticmethod
@@ -587,10 +581,8 @@ class MustafarAttention:
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()   # (T == their base tokens now: the view form)
                 k_c.ext_table, v_c.ext_table
                 past = past._replace(k_cache=k_c, v_cache=v_c)
-            if k_c.key_rows and not self._reads_key_rows(k_c, T, ops.ld, ops.flags):
-                k_c.require_tiles()   # (raises under capture: the launch form of this call reads tiles)
-            if v_c.value_lists and not self._reads_value_lists(v_c, T, ops.ld, ops.flags):
-                v_c.require_tiles()
+            self._tiles_unless_read(k_c, T, ops)
+            self._tiles_unless_read(v_c, T, ops)
         _call_decode(k_c, v_c, T, ops, D, t_device, lse)
         out = ops.out
         if step_counter is not None:
@@ -951,10 +943,8 @@ class MustafarAttention:
         # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
         ops = self._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
         lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-        if isinstance(k, CompressedArena) and k.key_rows and not self._reads_key_rows(k, tokens, ops.ld, ops.flags):
-            k.require_tiles()   # (a key base in token rows and a launch form that reads tiles)
-        if isinstance(v, CompressedArena) and v.value_lists and not self._reads_value_lists(v, tokens, ops.ld, ops.flags):
-            v.require_tiles()
+        self._tiles_unless_read(k, tokens, ops)
+        self._tiles_unless_read(v, tokens, ops)
         _call_decode(k, v, tokens, ops, D, None, lse)
         return ops.out, lse
 

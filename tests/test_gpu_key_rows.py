@@ -84,7 +84,7 @@ def _golden(golden_dir):
     return np.load(os.path.join(golden_dir, "compress_reference.npz"))["rand_B2_t256_s0.7__x"].view(np.float16)
 
 
-@pytest.mark.parametrize("data", ["special_256", "special_1280", "golden"])
+@pytest.mark.parametrize("data", ["special_256", "special_1280", "special_4160", "golden"])   # 4160: 65 blocks, a second trip of the table scan
 def test_retile_round_trip_is_bit_exact_and_rows_equal_the_reference(data, golden_dir):
     from mustafar_amd.cache import CompressedArena
     x = _golden(golden_dir) if data == "golden" else _special(int(data.split("_")[1]))

@@ -73,7 +73,7 @@ def _special(T):
     return x
 
 
-@pytest.mark.parametrize("data", ["special_256", "special_1280", "golden"])
+@pytest.mark.parametrize("data", ["special_256", "special_1280", "special_4160", "golden"])   # 4160: 65 blocks, a second trip of the table scan
 def test_retile_round_trip_is_bit_exact_and_lists_equal_the_reference(data, golden_dir):
     from mustafar_amd.cache import CompressedArena
     x = _golden(golden_dir) if data == "golden" else _special(int(data.split("_")[1]))

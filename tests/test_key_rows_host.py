@@ -88,6 +88,24 @@ def test_round_trip_across_sparsities(sparsity):
     assert np.array_equal(b2, bmp) and np.array_equal(i2, idx) and np.array_equal(n2[0], nzs[0])
 
 
+def test_a_table_of_65_blocks_continues_behind_entry_63():
+    """The 4160-token input of tests/test_gpu_key_rows.py (special_4160: two heads, 65 blocks -- one more than a 64-lane trip of the
+    device's table scan): entry 64 of each head's table is entry 63's first row + its rows, and the round trip is bit exact."""
+    from tests.test_gpu_key_rows import _special
+    T = 4160
+    bmp, idx, nzs = reference_key_cache(_special(T))
+    table, rows = ref.tiles_to_rows(bmp, idx, nzs, T)
+    assert table.shape == (2, 65)
+    for h in range(2):
+        first, w = table[h].astype(np.int64) >> 8, table[h].astype(np.int64) & 0xFF
+        assert first[64] == first[63] + ref.rows_of(int(w[63])) and first[64] > 64 * ref.rows_of(2)
+        assert rows[h].size == 256 * (first[64] + ref.rows_of(int(w[64])))
+    assert table[0, 64] != table[1, 64]   # (the heads' tables differ: a wrong pitch between them would show)
+    b2, i2, n2 = ref.rows_to_tiles(table, rows, T)
+    assert np.array_equal(b2, bmp) and np.array_equal(i2, idx)
+    assert all(np.array_equal(a, b) for a, b in zip(n2, nzs))
+
+
 # (name, q heads, kv heads, L, batch) of bench.py's configurations; R = 32 rows stay in the window
 _SHAPES = {"c1": (32, 32, 1024, 1), "c2": (32, 32, 4096, 1), "c3": (32, 8, 8192, 8), "c4": (32, 8, 32768, 4), "c5": (32, 8, 16384, 16),
            "b1": (32, 8, 8192, 1), "4k_b1": (32, 8, 4096, 1), "mha": (32, 32, 8192, 8), "gqa2": (32, 16, 8192, 8)}

@@ -113,6 +113,29 @@ def test_round_trip_and_size_across_sparsities(sparsity):
     assert np.array_equal(b2, bmp) and np.array_equal(i2, idx) and np.array_equal(n2[0], nzs[0])
 
 
+def test_a_table_of_65_blocks_continues_behind_entry_63():
+    """The 4160-token input of tests/test_gpu_value_lists.py (special_4160: two heads, 65 blocks -- one more than a 64-lane trip of the
+    device's table scan; 66 table entries per head): entries 64 and 65 of each head's table continue entry 63 by the sizes of blocks 63
+    and 64, read from the blocks' own headers, and the round trip is bit exact."""
+    T = 4160
+    bmp, idx, nzs = keep_zeros(*reference_value_cache(special_rows(seed=T, T=T)))
+    table, blocks = ref.tiles_to_lists(bmp, idx, nzs, T)
+    assert table.shape == (2, 66)
+
+    def dwords(h, b):   # header, half 0 (up to the offset of half 1), half 1, padded to 16 bytes
+        blk = blocks[h][4 * int(table[h, b]):]
+        half1, m1 = int(blk[192:196].view(np.uint32)[0]), blk[128 + 32:192]
+        return (half1 + ref.half_dwords(m1) + 3) // 4 * 4
+
+    for h in range(2):
+        assert int(table[h, 64]) == int(table[h, 63]) + dwords(h, 63) and int(table[h, 65]) == int(table[h, 64]) + dwords(h, 64)
+        assert blocks[h].size == 4 * int(table[h, 65]) and int(table[h, 64]) > 64 * 64
+    assert table[0, 64] != table[1, 64]   # (the heads' tables differ: a wrong pitch between them would show)
+    b2, i2, n2 = ref.lists_to_tiles(table, blocks, T)
+    assert np.array_equal(b2, bmp) and np.array_equal(i2, idx)
+    assert all(np.array_equal(a, b) for a, b in zip(n2, nzs))
+
+
 def test_reads_value_lists_equals_reads_key_rows_over_a_grid_of_shapes():
     L = _lib.load()
     flags = [0, _lib.ENGINE_FLAGS["valu"], _lib.ENGINE_FLAGS["dot2"], _lib.ENGINE_FLAGS["mfma"], _lib.STRUCTURE_FLAGS["two_launch"],

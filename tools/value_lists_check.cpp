@@ -1,5 +1,5 @@
 // value_lists_check.cpp -- the index arithmetic of sorted channel lists (mustafar_amd/csrc/value_lists.h) walked on the host: special blocks
-// go tiles -> lists -> tiles through the same offset functions the kernels of value_lists.hip use, every access bounds-checked by the
+// go tiles -> lists -> tiles through the same offset functions the kernels of base_forms.hip use, every access bounds-checked by the
 // containers' sizes.  No GPU, no Python:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o value_lists_check tools/value_lists_check.cpp && ./value_lists_check
 #include <algorithm>
@@ -22,7 +22,7 @@ struct Half {
     unsigned char perm[64], m[kVlMaxRows];
 };
 
-Half plan(const uint64_t* bmp)   // as half_plan of value_lists.hip
+Half plan(const uint64_t* bmp)   // as half_plan of base_forms.hip
 {
     Half h;
     for (int c = 0; c < 64; c++) {
