@@ -194,7 +194,8 @@ typedef struct mustafar_cache_view {
     int64_t   nz_head_stride;   /* != 0: nz_offset[h] == h * nz_head_stride (uint4 units, < 2^32): the SpMV kernels then compute
                                    the head's stream start instead of loading it (one memory latency less per wave) */
     uint32_t  flags;            /* 0: the tile format above.  MUSTAFAR_VIEW_KEY_ROWS (ABI 113): a KEY cache held as token rows;
-                                   MUSTAFAR_VIEW_VALUE_LISTS: a VALUE cache held as sorted channel lists, see below */
+                                   MUSTAFAR_VIEW_VALUE_LISTS: a VALUE cache held as sorted channel lists; MUSTAFAR_VIEW_VALUE_PAIR_LISTS:
+                                   the same over pairs of blocks, see below */
 } mustafar_cache_view;
 
 /*
@@ -261,6 +262,32 @@ int mustafar_value_lists_fill(void* stream, const mustafar_cache_view* src, cons
 int mustafar_value_lists_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total);
 /* Whether the launch that a fused call of this shape runs reads a value base of lists: the rule of mustafar_decode_reads_key_rows. */
 int mustafar_decode_reads_value_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
+
+/*
+ * Sorted channel lists over PAIRS of blocks: the value BASE with one list per channel over the 128 tokens of blocks 2p, 2p + 1 (DESIGN.md
+ * 3.3).  The longest list of a half sets the issue time of the value phase, and the longest of 64 lists over 128 tokens is relatively
+ * shorter than over 64.  The ABI version stays 115: callers find these symbols by name.  Per kv head, pair p and 64-channel half:
+ *   cnt[c]    the number of the pair's tokens whose bitmap has channel c set (0..128; a kept +-0 is an entry)
+ *   perm[i]   the half's channels sorted by cnt descending, ties by channel ascending: lane i owns channel perm[i]; its list is that
+ *             channel's (token in pair u8: 0..63 block 2p, 64..127 block 2p + 1; value fp16) entries, tokens ascending
+ *   rows and words as in MUSTAFAR_VIEW_VALUE_LISTS (m_r = #{c : cnt[c] > 2r}, r = 0..63; up to 32 words); slots behind a list's end inside
+ *             a row hold token 0 / value +0
+ * A pair is a 256-byte header, half 0's words, half 1's words, and zeros up to the next multiple of 16 bytes.  Header: bytes 0..127 perm
+ * of half 0, of half 1; bytes 128..255 m_0..m_63 of half 0, of half 1.  A base of an odd number of blocks ends in a pair of tokens 0..63.
+ * A view with MUSTAFAR_VIEW_VALUE_PAIR_LISTS in `flags` names such a cache (P = (tokens / 64 + 1) / 2 pairs):
+ *   nz               the pairs; head h starts at h * nz_head_stride uint4 units (nz_head_stride != 0)
+ *   idx              u32 [B', idx_head_stride] block table, dword offsets from the head's start: entry 2p = pair p's header, entry
+ *                    2p + 1 = its half 1, entry 2P = the head's dwords (idx_head_stride >= 2P + 1)
+ *   bmp, nz_offset   unused (may be NULL)
+ * Read where MUSTAFAR_VIEW_VALUE_LISTS is, by the same rule (mustafar_decode_reads_value_pair_lists); MUSTAFAR_EINVAL everywhere else.
+ */
+#define MUSTAFAR_VIEW_VALUE_PAIR_LISTS 4u
+/* Pass 1: table u32 [Bp][2P + 1] and head_dwords i64 [Bp].  Pass 2: dst's idx is the table of pass 1 (idx_head_stride == 2P + 1).  Back to
+ * tiles bit for bit.  As the three passes of MUSTAFAR_VIEW_VALUE_LISTS. */
+int mustafar_value_pair_lists_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_dwords);
+int mustafar_value_pair_lists_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens);
+int mustafar_value_pair_lists_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total);
+int mustafar_decode_reads_value_pair_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
 
 /*
  * mustafar_decode_attention over a cache that GROWS BY EXTENTS (the 256-token trigger of models/llama_mustafar_kernel.py:324-398

@@ -116,9 +116,10 @@ class BaseForm(NamedTuple):
     reads: str        # whether the launch of a call shape reads the form
     closing: int      # 1: the table ends with an entry of the head's units
     unit_bytes: int
+    pairs: int = 0    # 1: the table has two entries per PAIR of blocks (a trailing odd block makes a pair of its own)
 
     def table_columns(self, nb: int) -> int:
-        return nb + self.closing
+        return (2 * ((nb + 1) // 2) if self.pairs else nb) + self.closing
 
     def head_bytes(self, units: int) -> int:
         """What every head is given (the stride of the view, in whole uint4) when the fullest one holds `units`."""
@@ -129,7 +130,10 @@ KEY_ROWS = BaseForm("key_rows", "key", _lib.VIEW_KEY_ROWS, "mustafar_key_rows_pl
                     "mustafar_decode_reads_key_rows", 0, 256)            # units: rows of 64 tokens x 4 bytes
 VALUE_LISTS = BaseForm("value_lists", "value", _lib.VIEW_VALUE_LISTS, "mustafar_value_lists_plan", "mustafar_value_lists_fill",
                        "mustafar_value_lists_to_tiles", "mustafar_decode_reads_value_lists", 1, 4)   # units: dwords
-BASE_FORMS = (KEY_ROWS, VALUE_LISTS)
+VALUE_PAIR_LISTS = BaseForm("value_pair_lists", "value", _lib.VIEW_VALUE_PAIR_LISTS, "mustafar_value_pair_lists_plan", "mustafar_value_pair_lists_fill",
+                            "mustafar_value_pair_lists_to_tiles", "mustafar_decode_reads_value_pair_lists", 1, 4, 1)   # units: dwords
+BASE_FORMS = (KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS)
+LIST_FORMS = (VALUE_LISTS, VALUE_PAIR_LISTS)   # the value base in channel lists: per 64-token block, per pair of blocks
 
 
 class CompressedArena:
@@ -203,7 +207,7 @@ class CompressedArena:
         return next((f for f in BASE_FORMS if flags & f.flag), None)
 
     def _tile_array(self, name: str) -> torch.Tensor:
-        if self.form is VALUE_LISTS:
+        if self.form in LIST_FORMS:
             self.require_tiles()
         return getattr(self, name)
 
@@ -212,11 +216,15 @@ class CompressedArena:
     nz = property(lambda self: self._tile_array("_nz"), lambda self, x: setattr(self, "_nz", x))
 
     key_rows = property(lambda self: self.form is KEY_ROWS, doc="True while the base of this KEY arena is held as token rows.")
-    value_lists = property(lambda self: self.form is VALUE_LISTS, doc="True while the base of this VALUE arena is held as channel lists.")
+    value_lists = property(lambda self: self.form in LIST_FORMS,
+                           doc="True while the base of this VALUE arena is held as channel lists, per block or per pair of blocks.")
+    value_pair_lists = property(lambda self: self.form is VALUE_PAIR_LISTS,
+                                doc="True while the base of this VALUE arena is held as channel lists over pairs of blocks.")
 
     @property
     def lists_table(self) -> torch.Tensor:
-        """The block table of a value base held as channel lists: int32 [H, tokens / 64 + 1], dword offsets."""
+        """The block table of a value base held as channel lists, dword offsets: int32 [H, tokens / 64 + 1] (lists per block), [H, 2 pairs +
+        1] (per pair of blocks: header and half 1 of every pair)."""
         assert self.value_lists
         return self._idx
 
@@ -233,6 +241,8 @@ class CompressedArena:
         hook.MustafarAttention.to_fused() is the only caller outside the tests."""
         if self.form is form:
             return True
+        if self.form is not None:   # (one form at a time: the way to another leads through tiles, and is the caller's to take)
+            return False
         if self.which != form.which or not self.tokens or self._view.nz_head_stride == 0 or torch.cuda.is_current_stream_capturing():
             return False
         used = self.used   # (resolves an asynchronous append still in flight)
@@ -268,6 +278,10 @@ class CompressedArena:
     def to_value_lists(self) -> bool:
         """`_retile()` of a value arena into sorted channel lists (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS)."""
         return self._retile(VALUE_LISTS)
+
+    def to_value_pair_lists(self) -> bool:
+        """`_retile()` of a value arena into sorted channel lists over pairs of blocks (MUSTAFAR_VIEW_VALUE_PAIR_LISTS)."""
+        return self._retile(VALUE_PAIR_LISTS)
 
     keep_tiles = False   # set by require_tiles(): to_fused() does not retile this arena into rows again (no ping-pong between a caller's
                          # decode_fused and decode_multi / shared-segment calls); consolidate() clears it for its result

@@ -1,6 +1,7 @@
-// base_forms.hip -- the retile passes between the tile format of an arena's base and the two forms the GQA-4 one-pass super-block launch
-// reads instead (include/mustafar_hip.h): token rows of a KEY base (MUSTAFAR_VIEW_KEY_ROWS, ABI 113; arithmetic: key_rows.h)
-// and sorted channel lists of a VALUE base (MUSTAFAR_VIEW_VALUE_LISTS; arithmetic: value_lists.h).  head_dim 128 only.
+// base_forms.hip -- the retile passes between the tile format of an arena's base and the forms the GQA-4 one-pass super-block launch
+// reads instead (include/mustafar_hip.h): token rows of a KEY base (MUSTAFAR_VIEW_KEY_ROWS, ABI 113; arithmetic: key_rows.h),
+// sorted channel lists of a VALUE base per block (MUSTAFAR_VIEW_VALUE_LISTS; arithmetic: value_lists.h) or per pair of blocks
+// (MUSTAFAR_VIEW_VALUE_PAIR_LISTS; arithmetic: value_pair_lists.h).  head_dim 128 only.
 //
 //   tiles -> form   mustafar_<form>_plan (a number per block, then the block table by one scan per head) + mustafar_<form>_fill
 //   form -> tiles   mustafar_<form>_to_tiles: bitmaps and tile lengths, the offsets of a head by one scan, the streams
@@ -19,6 +20,7 @@
 #include "key_rows.h"
 #include "tile_view.h"
 #include "value_lists.h"
+#include "value_pair_lists.h"
 
 namespace {
 
@@ -332,6 +334,160 @@ __global__ __launch_bounds__(64) void value_tiles_stream_kernel(mustafar_cache_v
     for (int p = n; p < n8; p++) nz[2ull * idx[i] + p] = 0;
 }
 
+// ================================================================ value: tiles <-> sorted channel lists over pairs of blocks
+// Pair p of a head = blocks 2p, 2p + 1 (the last pair of an odd base: block 2p alone); token u of the pair = token u & 63 of block
+// 2p + (u >> 6).  The block table has two entries per pair (its header, its half 1) and the closing one: value_pair_lists.h.
+__device__ __forceinline__ int pair_tokens(int nb, int p) { return 64 * vpl_pair_blocks(nb, p); }
+// tile of token u of a pair, counted from the tile of the pair's token 0 in the same half
+__device__ __forceinline__ int pair_tile(int u) { return (u >> 6) * kD + (u & 63); }
+
+// half_plan over a pair's ntok tokens (bmp: the half's tile of the pair's token 0): the row widths m[0..63] in LDS
+__device__ __forceinline__ HalfPlan pair_half_plan(const uint64_t* __restrict__ bmp, int ntok, int c, unsigned char* m)
+{
+    HalfPlan p{0, 0};
+    for (int u = 0; u < ntok; u++) p.cnt += tile_bit(bmp[pair_tile(u)], c);
+    for (int o = 0; o < 64; o++) {
+        const int other = __shfl(p.cnt, o, 64);
+        p.rank += other > p.cnt || (other == p.cnt && o < c);
+    }
+    for (int r = 0; r < kVplMaxRows; r++) {
+        const int w = __popcll(__ballot(p.cnt > 2 * r));
+        if (c == 0) m[r] = (unsigned char)w;
+    }
+    __syncthreads();
+    return p;
+}
+
+// One wave per (pair, head): the dwords of the pair's two table entries -> table[h][2p], [2p + 1] (the scan turns them into starts).
+__global__ __launch_bounds__(64) void value_pair_lists_size_kernel(mustafar_cache_view src, int nb, uint32_t* __restrict__ table)
+{
+    __shared__ unsigned char m[2][kVplMaxRows];
+    const int p = blockIdx.x, h = blockIdx.y, c = threadIdx.x;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + (int64_t)(2 * p) * kD;
+    const int ntok = pair_tokens(nb, p);
+    pair_half_plan(bmp, ntok, c, m[0]);
+    pair_half_plan(bmp + 64, ntok, c, m[1]);
+    if (c == 0) {
+        const int half0 = vpl_word_offset(m[0], kVplMaxWords), half1 = vpl_word_offset(m[1], kVplMaxWords);
+        uint32_t* tab = table + (int64_t)h * vpl_table_columns(nb) + 2 * p;
+        tab[0] = (uint32_t)vpl_front_dwords(half0);
+        tab[1] = (uint32_t)vpl_back_dwords(half0, half1);
+    }
+}
+
+// where a pair's header and the words of one of its halves start
+__device__ __forceinline__ unsigned char* pair_header(const mustafar_cache_view& v, int h, int p) { return head_bytes(v, h) + 4ull * table_entry(v, h, 2 * p); }
+__device__ __forceinline__ unsigned char* pair_half(const mustafar_cache_view& v, int h, int p, int half)
+{
+    return head_bytes(v, h) + 4ull * (half ? table_entry(v, h, 2 * p + 1) : table_entry(v, h, 2 * p) + kVplHeaderDwords);
+}
+
+// One wave per (pair half, head), lane = channel: the half's part of the header and its words.
+__global__ __launch_bounds__(64) void value_pair_lists_fill_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned char m[kVplMaxRows];
+    __shared__ int woff[kVplMaxWords + 1];
+    const int p = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, c = threadIdx.x;
+    const int64_t tile0 = (int64_t)(2 * p) * kD + half * 64;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(src, h, nb) + tile0;
+    const uint16_t* nz = head_stream(src, h);
+    const int ntok = pair_tokens(nb, p);
+    const HalfPlan pl = pair_half_plan(bmp, ntok, c, m);
+    if (c <= kVplMaxWords) woff[c] = vpl_word_offset(m, c);
+    __syncthreads();
+    unsigned char* hdr = pair_header(dst, h, p);
+    hdr[kVplPermByte + half * 64 + pl.rank] = (unsigned char)c;
+    hdr[kVplWidthByte + half * kVplMaxRows + c] = m[c];
+    unsigned char* base = pair_half(dst, h, p, half);
+    if (half) {   // the zeros between this pair and the next (at most three dwords)
+        const uint32_t used = table_entry(dst, h, 2 * p + 1) + (uint32_t)woff[kVplMaxWords], end = table_entry(dst, h, 2 * p + 2);
+        if (used + c < end) reinterpret_cast<uint32_t*>(head_bytes(dst, h))[used + c] = 0u;
+    }
+    const int i = pl.rank;
+    int s = 0;
+    for (int u = 0; u < ntok; u++) {
+        const int tl = pair_tile(u);
+        const uint64_t bits = bmp[tl];
+        if (tile_bit(bits, c)) {
+            const int w = woff[s >> 2];
+            base[vpl_token_byte(w, i, s)] = (unsigned char)u;
+            *reinterpret_cast<uint16_t*>(base + vpl_value_byte(m, w, i, s)) = nz[2ull * idx[tl] + tile_rank(bits, c)];
+            s++;
+        }
+    }
+    if (s & 1) *reinterpret_cast<uint16_t*>(base + vpl_value_byte(m, woff[s >> 2], i, s)) = 0;
+    for (int q = s; q < vpl_token_slots(s); q++) base[vpl_token_byte(woff[q >> 2], i, q)] = 0;
+}
+
+// A lane's entries, as HalfLists: slot s of lane i is an entry if the lane takes part in its rows and s == 0 or its token is not 0.
+__device__ __forceinline__ HalfLists pair_half_lists(const mustafar_cache_view& v, int h, int p, int half, int i, int* woff)
+{
+    const unsigned char* hdr = pair_header(v, h, p);
+    HalfLists L;
+    L.m = hdr + kVplWidthByte + half * kVplMaxRows;
+    L.base = pair_half(v, h, p, half);
+    L.chan = hdr[kVplPermByte + half * 64 + i] & 63;
+    if (i <= kVplMaxWords) woff[i] = vpl_word_offset(L.m, i);
+    __syncthreads();
+    return L;
+}
+// token of slot s of lane i (below ntok, a power of two), or -1 behind the lane's last entry
+__device__ __forceinline__ int pair_list_token(const HalfLists& L, const int* woff, int i, int s, int ntok)
+{
+    if (s >= 2 * kVplMaxRows || i >= L.m[s >> 1]) return -1;
+    const int t = L.base[vpl_token_byte(woff[s >> 2], i, s)];
+    return (s == 0 || t != 0) ? (t & (ntok - 1)) : -1;
+}
+
+// One wave per (pair half, head): the bitmaps of the half's tiles and every tile's length -> dst.idx[h][tile + 1].
+__global__ __launch_bounds__(64) void value_pair_tiles_bitmap_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned long long bits[128];
+    __shared__ int woff[kVplMaxWords + 1];
+    const int p = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, i = threadIdx.x;
+    const int ntok = pair_tokens(nb, p);
+    bits[i] = 0ull;
+    bits[i + 64] = 0ull;
+    const HalfLists L = pair_half_lists(src, h, p, half, i, woff);
+    for (int s = 0;; s++) {
+        const int t = pair_list_token(L, woff, i, s, ntok);
+        if (t < 0) break;
+        atomicOr(&bits[t], 1ull << (63 - L.chan));
+    }
+    __syncthreads();
+    const int64_t tile0 = (int64_t)(2 * p) * kD + half * 64;
+    for (int u = i; u < ntok; u += 64) {
+        const uint64_t mt = bits[u];
+        tile_bmp(dst, h, nb)[tile0 + pair_tile(u)] = mt;
+        tile_idx(dst, h, nb)[tile0 + pair_tile(u) + 1] = tile_length(mt);
+    }
+}
+
+// One wave per (pair half, head): the streams of the half's tiles, padding included.
+__global__ __launch_bounds__(64) void value_pair_tiles_stream_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ int woff[kVplMaxWords + 1];
+    const int p = blockIdx.x >> 1, half = blockIdx.x & 1, h = blockIdx.y, i = threadIdx.x;
+    const int ntok = pair_tokens(nb, p);
+    const HalfLists L = pair_half_lists(src, h, p, half, i, woff);
+    const int64_t tile0 = (int64_t)(2 * p) * kD + half * 64;
+    const uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    uint16_t* nz = head_stream(dst, h);
+    for (int s = 0;; s++) {
+        const int t = pair_list_token(L, woff, i, s, ntok);
+        if (t < 0) break;
+        const int tl = pair_tile(t);
+        nz[2ull * idx[tl] + tile_rank(bmp[tl], L.chan)] = *reinterpret_cast<const uint16_t*>(L.base + vpl_value_byte(L.m, woff[s >> 2], i, s));
+    }
+    for (int u = i; u < ntok; u += 64) {   // lane = token: its tiles' padding
+        const int tl = pair_tile(u);
+        const int n = __popcll(bmp[tl]), n8 = (n + 7) & ~7;
+        for (int q = n; q < n8; q++) nz[2ull * idx[tl] + q] = 0;
+    }
+}
+
 }  // namespace
 
 // ================================================================ the entry points (include/mustafar_hip.h); every refusal is tile_view.h's
@@ -392,6 +548,37 @@ int mustafar_value_lists_to_tiles(void* stream, const mustafar_cache_view* src, 
     value_tiles_bitmap_kernel<<<dim3(2 * nb, Bp), 64, 0, st>>>(*src, *dst, nb);
     tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
     value_tiles_stream_kernel<<<dim3(2 * nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_pair_lists_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_dwords)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !table || !head_dwords) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64, np = vpl_pairs(nb);
+    value_pair_lists_size_kernel<<<dim3(np, Bp), 64, 0, st>>>(*src, nb, table);
+    block_table_scan_kernel<ListsTable><<<Bp, 64, 0, st>>>(2 * np, table, head_dwords);   // (two entries per pair)
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_pair_lists_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !value_pair_lists_view_ok(dst, tokens) ||
+        dst->idx_head_stride != vpl_table_columns(tokens / 64))
+        return MUSTAFAR_EINVAL;
+    const int nb = tokens / 64;
+    value_pair_lists_fill_kernel<<<dim3(2 * vpl_pairs(nb), Bp), 64, 0, static_cast<hipStream_t>(stream)>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_value_pair_lists_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total)
+{
+    if (!retile_shape_ok(Bp, tokens) || !value_pair_lists_view_ok(src, tokens) || !tile_view_ok(dst, tokens) || !dst->nz_head_stride) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64, np = vpl_pairs(nb);
+    value_pair_tiles_bitmap_kernel<<<dim3(2 * np, Bp), 64, 0, st>>>(*src, *dst, nb);
+    tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
+    value_pair_tiles_stream_kernel<<<dim3(2 * np, Bp), 64, 0, st>>>(*src, *dst, nb);
     return (int)hipGetLastError();
 }
 

@@ -33,6 +33,7 @@
 #include "key_rows.h"
 #include "tile_view.h"
 #include "value_lists.h"
+#include "value_pair_lists.h"
 
 namespace {
 
@@ -2753,11 +2754,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t value_list_buffer(const unsign
     const bool any = half1 >= (uint32_t)kVlHeaderDwords && last >= first;   // (a header that is none: an empty buffer)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(lists + 4ull * (start + first)), (short)0, any ? (int)(4u * (last - first)) : 0, 0x00020000);
 }
-// wsel: the lane of hdr that holds the widths of the half's rows 0..3 (the seven behind it: the rows up to 31)
+// wsel: the lane of hdr that holds the widths of the half's rows 0..3 (the ROWS / 4 - 1 behind it: the rows up to ROWS - 1; 32 rows in
+// a block's lists, 64 in a pair's)
+template <int ROWS = kVlMaxRows>
 __device__ __forceinline__ int value_list_words(uint32_t hdr, int wsel, int lane)
 {
-    // a word exists where its token row has lanes: bytes 0 and 2 of the eight width dwords
-    const bool mine = lane >= wsel && lane < wsel + kVlMaxRows / 4;
+    // a word exists where its token row has lanes: bytes 0 and 2 of the ROWS / 4 width dwords
+    const bool mine = lane >= wsel && lane < wsel + ROWS / 4;
     return __popcll(__ballot(mine && (hdr & 0xffu))) + __popcll(__ballot(mine && (hdr & 0xff0000u)));
 }
 // word j of the half at dword `off` (advanced): lanes beyond a row's width read nothing
@@ -2812,6 +2815,55 @@ __device__ __forceinline__ void value_lists_phase(const unsigned char* __restric
     }
 }
 
+// ---- value phase over channel lists of a PAIR of blocks (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_PAIR_LISTS; value_pair_lists.h).  As
+// above with ONE list per channel over the pair's 128 tokens: a token byte indexes the pair's two e tables, which lie back to back
+// ([128 tokens][4 heads] fp16), so the lookup is the key phase's against its q table of 128 channels.  The issue time of the phase follows the
+// half's longest list, and the longest of 64 lists over 128 tokens is relatively shorter than over 64 (max / mean ~1.33 against ~1.56 at
+// 70 %).  One buffer, one header, one set of accumulators, one un-permute at the merge.  Two words per trip on two sets of registers: the
+// next word is on its way while the current one is multiplied.
+// start / half1 / end: the pair's table entries (dwords from the head's start: header, half 1, the next pair)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t value_pair_buffer(const unsigned char* __restrict__ lists, uint32_t start, uint32_t half1, uint32_t end, int odd)
+{
+    // (readfirstlane: wave-uniform all of it, and the resource has to be built in scalar registers -- left to the compiler it lands in vector
+    // registers and every load of the phase is wrapped in a loop over the lanes' values)
+    const uint32_t first = odd ? half1 : start + (uint32_t)kVplHeaderDwords, last = odd ? end : half1;
+    const int bytes = __builtin_amdgcn_readfirstlane(last >= first ? (int)(4u * (last - first)) : 0);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(uniform_ptr(lists + 4ull * first)), (short)0, bytes, 0x00020000);
+}
+__device__ __forceinline__ void value_pair_step(const KeyRowWord& r, const unsigned char* etab, float (&acc)[4])
+{
+    uint2 e[4];
+    key_row_q(r.ch, etab, e);
+    key_row_fma(r, e, acc);
+}
+// hdr: the pair's header, dword `lane`; etab: the pair's e table, 128 tokens; last: called in front of the last word
+template <class LAST>
+__device__ __forceinline__ void value_pair_lists_phase(const unsigned char* __restrict__ lists, uint32_t start, uint32_t half1, uint32_t end, uint32_t hdr,
+                                                       int odd, int lane, const unsigned char* etab, float (&acc)[4], const LAST& last)
+{
+    const int lane4 = lane * 4, wsel = kVplWidthByte / 4 + odd * (kVplMaxRows / 4);
+    const __amdgpu_buffer_rsrc_t buf = value_pair_buffer(lists, start, half1, end, odd);
+    const int n = value_list_words<kVplMaxRows>(hdr, wsel, lane);   // (at most kVplMaxWords: value_list_word reads the width dwords wsel .. wsel + 15)
+    int off = 0;
+    KeyRowWord ra = value_list_word(buf, hdr, wsel, 0, off, lane, lane4);
+    int j = 0;
+#pragma unroll 1
+    for (; j + 2 < n; j += 2) {
+        const KeyRowWord na = value_list_word(buf, hdr, wsel, j + 1, off, lane, lane4);
+        value_pair_step(ra, etab, acc);
+        ra = value_list_word(buf, hdr, wsel, j + 2, off, lane, lane4);
+        value_pair_step(na, etab, acc);
+    }
+#pragma unroll 1
+    for (; j < n; j++) {
+        KeyRowWord na{0u, 0u, 0u};
+        if (j + 1 < n) na = value_list_word(buf, hdr, wsel, j + 1, off, lane, lane4);
+        else last();
+        value_pair_step(ra, etab, acc);
+        ra = na;
+    }
+}
+
 // What the LISTS instantiations of the kernel below carry besides: nothing at all in the others, whose code stays what it was.
 template <bool LISTS>
 struct ValueListState {};
@@ -2819,14 +2871,18 @@ template <>
 struct ValueListState<true> {
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     uint32_t vent = 0;                      // the table entries of the pair's blocks: start, end of A in lanes 0, 1; of B in lanes 2, 3
-    u32x2 hdr = {0u, 0u};                   // the headers of blocks A and B, dword `lane` of each (one variable, written whole)
-    float accB[4] = {0.f, 0.f, 0.f, 0.f};   // block B's share (its lanes own other channels than block A's, which acc then holds)
+                                            // (PAIRS: of the pair of blocks -- its header, its half 1, the next pair -- in lanes 0, 1, 2)
+    u32x2 hdr = {0u, 0u};                   // the headers of blocks A and B, dword `lane` of each (one variable, written whole; PAIRS: the
+                                            // pair's one header in x, y unused)
+    float accB[4] = {0.f, 0.f, 0.f, 0.f};   // block B's share (its lanes own other channels than block A's, which acc then holds; PAIRS:
+                                            // unused -- one list per channel, one set of accumulators)
     unsigned char* etab = nullptr;          // the pair's e tables
     bool lists = false;                     // this workgroup reads lists (one of an appended extent reads tiles)
 };
 // LISTS: the value BASE arrives as sorted channel lists (v_nz = the blocks, v_idx = the block table).  An instantiation of its own, chosen
 // by the host: the launches that read value tiles -- two blocks per workgroup among them -- keep the code they had.
-template <int ENG, bool EXT = false, int G = 4, bool MASK = false, bool LISTS = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
+// PAIRS (with LISTS): the lists run over pairs of blocks (MUSTAFAR_VIEW_VALUE_PAIR_LISTS) -- instantiations of their own again.
+template <int ENG, bool EXT = false, int G = 4, bool MASK = false, bool LISTS = false, bool PAIRS = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
                                                                      // decode_onepass_leanpair_kernel; round 5 carried an uninstantiated online form here -- removed in round 6)
 __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
@@ -2836,6 +2892,7 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
 {
     static_assert(G == 4 || ENG == 0, "dot2 and the matrix pipe work on four heads; G < 4 runs v_fma_mix");
     static_assert(!LISTS || (G == 4 && ENG != 1), "channel lists are read by the GQA-4 launches on the vector engines");
+    static_assert(!PAIRS || LISTS, "pair lists are channel lists");
     constexpr int HW = G >= 2 ? G / 2 : 1;   // heads a wave of the pair finishes (G = 1: the even wave its one head, the odd wave none)
     constexpr int kTabBytes = ENG == 1 ? 4 * kKeyTabStride + 2 * 2 * 4 * kValTabStride : 0;   // q rows; per pair TWO e tables (blocks A, B)
     __shared__ __attribute__((aligned(16))) unsigned char smem[kWaves * kStageBytes + kTabBytes];
@@ -2973,7 +3030,9 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         if (vl.lists) {
             const uint32_t* vtab = v_idx + (int64_t)kvh * v_idx_stride;   // the head's block table
             const int tA = pb0 < pb_end ? pb0 : tb0, tB = pb0 + 1 < pb_end ? pb0 + 1 : tA;   // (as tAc / tBc of the trip)
-            vl.vent = vtab[((lane & 2) ? tB : tA) + (lane & 1)];
+            // pair lists: the three entries of the pair block A lies in -- header, half 1, the next pair -- in lanes 0, 1, 2
+            if constexpr (PAIRS) vl.vent = vtab[(tA & ~1) + ((lane & 3) < 2 ? (lane & 3) : 2)];
+            else vl.vent = vtab[((lane & 2) ? tB : tA) + (lane & 1)];
         }
     }
     if constexpr (ROWS) {
@@ -3014,8 +3073,11 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         auto reqVA = [&]() {   // the value side's bounds (both blocks: they are consumed as one pipeline) and block A's metadata lines
             if constexpr (LISTS) {
                 if (vl.lists) {   // lists: the headers of both blocks, a dword per lane
-                    vl.hdr = typename ValueListState<LISTS>::u32x2{ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 0), lane * 4u),
-                                                                   ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 2), lane * 4u)};
+                    if constexpr (PAIRS)
+                        vl.hdr = typename ValueListState<LISTS>::u32x2{ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 0), lane * 4u), 0u};
+                    else
+                        vl.hdr = typename ValueListState<LISTS>::u32x2{ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 0), lane * 4u),
+                                                                       ld_at(vn + 4ull * (uint32_t)__builtin_amdgcn_readlane((int)vl.vent, 2), lane * 4u)};
                     return;
                 }
             }
@@ -3088,8 +3150,11 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                     *reinterpret_cast<h16*>(ptab + 4 * kValTabStride + (h0 + j) * kValTabStride + lane * 2) = eb2;
                 } else if constexpr (LISTS) {
                     if (vl.lists) {   // (block B's table is written for an absent block too -- zeros: its lanes multiply +0 by entry 0)
-                        *reinterpret_cast<h16*>(vl.etab + lane * 8 + (h0 + j) * 2) = ea;
-                        *reinterpret_cast<h16*>(vl.etab + 64 * 8 + lane * 8 + (h0 + j) * 2) = eb2;
+                        // (pair lists: a token byte of 0..63 is the pair's EVEN block -- block A, unless a pair of waves holds the odd block
+                        // of a pair alone; a block that is absent or not in use weighs zero: its entries add +-0)
+                        const int atA = PAIRS ? (tAc & 1) * (64 * 8) : 0;
+                        *reinterpret_cast<h16*>(vl.etab + atA + lane * 8 + (h0 + j) * 2) = ea;
+                        *reinterpret_cast<h16*>(vl.etab + (64 * 8 - atA) + lane * 8 + (h0 + j) * 2) = eb2;
                     } else {
                         eA[(h0 + j) * 64 + lane] = ea;
                         if (actB) eB[(h0 + j) * 64 + lane] = eb2;
@@ -3116,9 +3181,14 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                     const uint32_t hdrA = vl.hdr.x, hdrB = actB ? vl.hdr.y : 0u;   // (an absent block B was addressed as block A)
                     auto dropPrio = [&]() { if (!late_round) __builtin_amdgcn_s_setprio(0); };
                     const uint32_t vent = vl.vent;
-                    value_lists_phase(vn, (uint32_t)__builtin_amdgcn_readlane((int)vent, 0), (uint32_t)__builtin_amdgcn_readlane((int)vent, 1), hdrA,
-                                      (uint32_t)__builtin_amdgcn_readlane((int)vent, 2), (uint32_t)__builtin_amdgcn_readlane((int)vent, 3), hdrB, odd, lane,
-                                      vl.etab, acc, vl.accB, dropPrio);
+                    if constexpr (PAIRS) {
+                        value_pair_lists_phase(vn, (uint32_t)__builtin_amdgcn_readlane((int)vent, 0), (uint32_t)__builtin_amdgcn_readlane((int)vent, 1),
+                                               (uint32_t)__builtin_amdgcn_readlane((int)vent, 2), hdrA, odd, lane, vl.etab, acc, dropPrio);
+                    } else {
+                        value_lists_phase(vn, (uint32_t)__builtin_amdgcn_readlane((int)vent, 0), (uint32_t)__builtin_amdgcn_readlane((int)vent, 1), hdrA,
+                                          (uint32_t)__builtin_amdgcn_readlane((int)vent, 2), (uint32_t)__builtin_amdgcn_readlane((int)vent, 3), hdrB, odd,
+                                          lane, vl.etab, acc, vl.accB, dropPrio);
+                    }
                 }
             } else if (actB) {
                 uint32_t pfVB = 0;
@@ -3157,14 +3227,17 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     if constexpr (LISTS) unpermute = vl.lists;
     if (unpermute) {   // lists: block A's lanes store at their channels, block B's add at theirs (one wave: in order)
         if constexpr (LISTS) {
-            const int chA = value_list_channel(vl.hdr.x, pb0 < pb_end, odd, lane), chB = value_list_channel(vl.hdr.y, pb0 + 1 < pb_end, odd, lane);
+            // (chB up here, ahead of block A's stores, as the instantiations without PAIRS had it: their code stays what it was)
+            const int chA = value_list_channel(vl.hdr.x, pb0 < pb_end, odd, lane), chB = PAIRS ? 0 : value_list_channel(vl.hdr.y, pb0 + 1 < pb_end, odd, lane);
 #pragma unroll
             for (int h = 0; h < 4; h++)
                 red[(wave * G + h) * 64 + chA] = acc[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
-            __builtin_amdgcn_wave_barrier();
+            if constexpr (!PAIRS) {   // (pair lists: one list per channel over both blocks, one store)
+                __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int h = 0; h < 4; h++)
-                red[(wave * G + h) * 64 + chB] += vl.accB[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+                for (int h = 0; h < 4; h++)
+                    red[(wave * G + h) * 64 + chB] += vl.accB[h] * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, scale_l), h));
+            }
         }
     } else {
 #pragma unroll
@@ -4098,7 +4171,7 @@ using OnePassKernel = void (*)(const uint64_t*, const unsigned char*, const uint
                                const uint32_t*, const uint32_t*, OneArgs, int64_t, int64_t, uint32_t, int64_t, int64_t, uint32_t);
 // eng: 0 for G < 4.  ext: the EXT instantiation.  mask: the MASK instantiation (the pair form has none: it reads a.mask at run time).
 // nullptr: no such kernel -- the MHA pair and super-block launches always run EXT (decode_attention), the matrix pipe has no small form.
-inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask, bool lists = false)
+inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask, bool lists = false, bool pairs = false)
 {
     const int row = G == 4 ? eng : G == 2 ? 3 : 4;   // GQA-4: v_fma_mix, matrix pipe, v_dot2; GQA-2; MHA
     const int col = (ext ? 2 : 0) + (mask ? 1 : 0);  // EXT = false: MASK false, true; EXT = true: MASK false, true
@@ -4128,6 +4201,12 @@ inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mas
         {decode_onepass_sb_kernel<0, false, 4, false, true>, decode_onepass_sb_kernel<0, false, 4, true, true>, decode_onepass_sb_kernel<0, true, 4, false, true>, decode_onepass_sb_kernel<0, true, 4, true, true>},
         {decode_onepass_sb_kernel<2, false, 4, false, true>, decode_onepass_sb_kernel<2, false, 4, true, true>, decode_onepass_sb_kernel<2, true, 4, false, true>, decode_onepass_sb_kernel<2, true, 4, true, true>},
     };
+    // the same over pairs of blocks (pairs: with lists)
+    static constexpr OnePassKernel kSbPairs[2][4] = {
+        {decode_onepass_sb_kernel<0, false, 4, false, true, true>, decode_onepass_sb_kernel<0, false, 4, true, true, true>, decode_onepass_sb_kernel<0, true, 4, false, true, true>, decode_onepass_sb_kernel<0, true, 4, true, true, true>},
+        {decode_onepass_sb_kernel<2, false, 4, false, true, true>, decode_onepass_sb_kernel<2, false, 4, true, true, true>, decode_onepass_sb_kernel<2, true, 4, false, true, true>, decode_onepass_sb_kernel<2, true, 4, true, true, true>},
+    };
+    if (lists && pairs) return form == kFormSb && G == 4 && eng != 1 ? kSbPairs[eng == 2][col] : nullptr;
     if (lists) return form == kFormSb && G == 4 && eng != 1 ? kSbLists[eng == 2][col] : nullptr;
     return form == kFormSmall ? kSmall[row][col] : form == kFormSb ? kSb[row][col] : kPair[row][ext ? 1 : 0];
 }
@@ -4269,14 +4348,17 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
     if ((c.lse || no_window || extents) && !onepass) return MUSTAFAR_EINVAL;
     // a key base of token rows (MUSTAFAR_VIEW_KEY_ROWS), a value base of sorted channel lists (MUSTAFAR_VIEW_VALUE_LISTS): read by the
     // super-block launch alone (checked where the shape is known); no other flag exists, and neither side takes the other's
-    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS, value_lists = c.v.flags == MUSTAFAR_VIEW_VALUE_LISTS;
+    // (value_lists: either list form; value_pairs: MUSTAFAR_VIEW_VALUE_PAIR_LISTS)
+    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS, value_pairs = c.v.flags == MUSTAFAR_VIEW_VALUE_PAIR_LISTS;
+    const bool value_lists = c.v.flags == MUSTAFAR_VIEW_VALUE_LISTS || value_pairs;
     if ((c.k.flags && !key_rows) || (c.v.flags && !value_lists) || ((key_rows || value_lists) && (!onepass || c.T <= 0))) return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || (!value_lists && (!c.v.bmp || !c.v.nz_offset)) || !c.v.nz || !c.v.idx))
         return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
     // the form rules are tile_view.h's; here on top: the launch takes the head stride in 32 bits
     if (key_rows && (!key_rows_view_ok(&c.k, (int)(tiles / 2)) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
-    if (value_lists && (!value_lists_view_ok(&c.v, (int)(tiles / 2)) || c.v.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    if (value_lists && (!(value_pairs ? value_pair_lists_view_ok(&c.v, (int)(tiles / 2)) : value_lists_view_ok(&c.v, (int)(tiles / 2))) || c.v.nz_head_stride >> 32))
+        return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1))) ||
                     (!value_lists && ((c.v.bmp_head_stride && c.v.bmp_head_stride < tiles) || (c.v.idx_head_stride && c.v.idx_head_stride < tiles + 1)))))
         return MUSTAFAR_EINVAL;
@@ -4318,7 +4400,7 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
         // launches its plain G = 1 instantiation.)
         if (!extents && G == 1) a.nb0 = c.T / 64;
         const bool ext = extents || (G == 1 && s.form != kFormSmall);
-        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr, value_lists);
+        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr, value_lists, value_pairs);
         if (!kernel) return MUSTAFAR_EINVAL;   // (no shape selects a kernel the table leaves out)
         hipExtLaunchKernelGGL(kernel, dim3(s.S1, gy + (s.win_rows < 0 ? -s.win_rows : s.win_rows)), dim3(kThreads), 0, st, ev ? ev[0] : nullptr,
                               ev ? ev[1] : nullptr, 0, c.k.bmp, kz, c.k.idx, c.k.nz_offset, c.v.bmp, vz, c.v.idx, c.v.nz_offset, a,
@@ -4621,6 +4703,11 @@ int mustafar_decode_reads_key_rows(int num_key_value_groups, int T, int gy, int 
 int mustafar_decode_reads_value_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
 {
     return mustafar_decode_reads_key_rows(num_key_value_groups, T, gy, ld_scores, flags);   // the same launches read both forms
+}
+
+int mustafar_decode_reads_value_pair_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
+{
+    return mustafar_decode_reads_key_rows(num_key_value_groups, T, gy, ld_scores, flags);   // and the lists over pairs of blocks
 }
 
 int mustafar_profile_begin(int max_records)

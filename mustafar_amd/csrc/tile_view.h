@@ -1,6 +1,6 @@
 // tile_view.h -- what a mustafar_cache_view (include/mustafar_hip.h) means, once: where a head's bitmaps, offsets and stream start in a
 // tile-format view, the bit and rank of a position in a tile's bitmap, and -- on the host -- which views are well formed: the tile view
-// of a retile entry point and the two base forms.  Plain inline functions, no kernels; the retile passes
+// of a retile entry point and the base forms.  Plain inline functions, no kernels; the retile passes
 // (base_forms.hip) and decode_attention (spmv.hip) hold their views to these rules.
 #pragma once
 #include <stdint.h>
@@ -55,4 +55,10 @@ inline bool key_rows_view_ok(const mustafar_cache_view* v, int tokens)
 inline bool value_lists_view_ok(const mustafar_cache_view* v, int tokens)
 {
     return v && v->flags == MUSTAFAR_VIEW_VALUE_LISTS && v->idx && v->nz && v->nz_head_stride > 0 && v->idx_head_stride >= tokens / 64 + 1;
+}
+// MUSTAFAR_VIEW_VALUE_PAIR_LISTS: two table entries per pair of blocks and the closing one
+inline bool value_pair_lists_view_ok(const mustafar_cache_view* v, int tokens)
+{
+    return v && v->flags == MUSTAFAR_VIEW_VALUE_PAIR_LISTS && v->idx && v->nz && v->nz_head_stride > 0 &&
+           v->idx_head_stride >= 2 * ((tokens / 64 + 1) / 2) + 1;
 }

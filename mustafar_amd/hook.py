@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, compression, mustafar_package
-from .cache import KEY_ROWS, VALUE_LISTS, BaseForm, CompressedArena
+from .cache import KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS, BaseForm, CompressedArena
 from .cache64 import ExtentCache64, compress_raw_pair_hd64
 from .compression import _compress                                                                          # noqa: F401  (re-exported)
 from .reflayout import FlatStreams, _flat_stream, append_compressed, as_cache, nz_offset_from_idxs         # noqa: F401  (re-exported)
@@ -90,6 +90,9 @@ class MustafarConfig:
     # The value base as sorted channel lists (cache.CompressedArena.to_value_lists), in the same launches and by the same rules
     # (mustafar_decode_reads_value_lists).  MUSTAFAR_VALUE_LISTS=0 turns it off everywhere
     value_lists: bool = True
+    # The lists over PAIRS of 64-token blocks (cache.CompressedArena.to_value_pair_lists): what to_fused() prefers for the value base.
+    # False / MUSTAFAR_VALUE_PAIR_LISTS=0 falls back to the lists per block; value_lists=False / MUSTAFAR_VALUE_LISTS=0 turns both off
+    value_pair_lists: bool = True
     # head_dim 64, api="fused", arena=False only: the compressed cache grows by 256-token extents (cache64.py) instead of being
     # re-copied by every trigger, and one captured graph of the step with a device-side T serves every cache length up to its capacity
     hd64_extents: bool = False
@@ -331,6 +334,8 @@ class MustafarAttention:
 
     def _wants_form(self, form: BaseForm) -> bool:
         cfg = self.cfg
+        if form is VALUE_PAIR_LISTS and not self._wants_form(VALUE_LISTS):   # (the knob of the lists rules both list forms)
+            return False
         return getattr(cfg, form.name) and os.environ.get("MUSTAFAR_" + form.name.upper(), "1") != "0" and cfg.head_dim == 128 and \
             self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
 
@@ -421,6 +426,11 @@ class MustafarAttention:
             cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
             k_w, v_w = Window(k_w, cap), Window(v_w, cap)
         self._retile_where_read(k_c, k_w, KEY_ROWS)
+        # the lists over pairs of blocks are preferred where key rows are wanted too, the configuration they were measured in:
+        # a matter of the configuration and the knobs, not of the state of this key arena; an arena that took them is no longer in tiles
+        # for the line below
+        if self._wants_form(KEY_ROWS):
+            self._retile_where_read(v_c, v_w, VALUE_PAIR_LISTS)
         self._retile_where_read(v_c, v_w, VALUE_LISTS)
         return Past(k_c, k_w, v_c, v_w, C, L)
 
