@@ -290,6 +290,25 @@ int mustafar_value_pair_lists_to_tiles(void* stream, const mustafar_cache_view* 
 int mustafar_decode_reads_value_pair_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
 
 /*
+ * NIBBLE ROWS of a key cache (head_dim 128; arithmetic: mustafar_amd/csrc/key_nibble_rows.h): token rows whose channel
+ * numbers are 4-bit steps.  Per kv head and 64-token block, lane = token; a slot is an fp16 value and a step.  A block of width w (even,
+ * 2..128) is two shares back to back, one per wave of a pair: the front, slots [0, F), F = ((w / 2 + 1) & ~1), holds a token's first
+ * non-zeros as a chain ascending from channel -1; the back, slots [F, w), the rest as a chain descending from channel 128.  A share of n
+ * slots is ceil(n / 8) step rows (64 dwords: the steps of slots 8j .. 8j + 7, slot s in bits 4 (s & 7) ..) and n / 2 value rows (64 half2).
+ * Step 0: no entry, stay (padding, value +0); 1..14: an entry that many channels on; 15: no entry, 14 channels on (a spacer, value +0).
+ * Whether a slot is an entry is told by its step alone: a kept +-0 comes back.  The front takes a token's entries while they fit (greedy);
+ * w is the smallest even width at which every token of the block fits.  The view is that of MUSTAFAR_VIEW_KEY_ROWS (table entry b = first
+ * row of block b << 8 | w).  Read by the launches for which mustafar_decode_reads_key_nibble_rows() is 1 (the rule of the token rows),
+ * and only next to a value base of MUSTAFAR_VIEW_VALUE_PAIR_LISTS; MUSTAFAR_EINVAL everywhere else.  The three passes are those of the
+ * token rows; back to tiles bit for bit.
+ */
+#define MUSTAFAR_VIEW_KEY_NIBBLE_ROWS 8u
+int mustafar_key_nibble_rows_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_rows);
+int mustafar_key_nibble_rows_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens);
+int mustafar_key_nibble_rows_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total);
+int mustafar_decode_reads_key_nibble_rows(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags);
+
+/*
  * mustafar_decode_attention over a cache that GROWS BY EXTENTS (the 256-token trigger of models/llama_mustafar_kernel.py:324-398
  * without copying or moving what is already compressed): tokens [0, T_base) live in the two base views, tokens
  * [T_base + 256 i, T_base + 256 (i + 1)) in entry i of `k_extents` / `v_extents` -- arrays of mustafar_cache_view in DEVICE memory,

@@ -23,6 +23,7 @@ class CacheView(ctypes.Structure):
 VIEW_KEY_ROWS = 1      # MUSTAFAR_VIEW_KEY_ROWS: a key base held as token rows (cache.CompressedArena.to_key_rows)
 VIEW_VALUE_LISTS = 2   # MUSTAFAR_VIEW_VALUE_LISTS: a value base held as sorted channel lists (cache.CompressedArena.to_value_lists)
 VIEW_VALUE_PAIR_LISTS = 4   # MUSTAFAR_VIEW_VALUE_PAIR_LISTS: the lists over pairs of blocks (cache.CompressedArena.to_value_pair_lists)
+VIEW_KEY_NIBBLE_ROWS = 8    # MUSTAFAR_VIEW_KEY_NIBBLE_ROWS: token rows with 4-bit channel steps (cache.CompressedArena.to_key_nibble_rows)
 
 
 _view_p = ctypes.POINTER(CacheView)
@@ -95,6 +96,11 @@ SIGNATURES = {
     "mustafar_value_pair_lists_plan": (_i32, [_vp, _view_p, _i32, _i32, _vp, _vp]),
     "mustafar_value_pair_lists_fill": (_i32, [_vp, _view_p, _view_p, _i32, _i32]),
     "mustafar_value_pair_lists_to_tiles": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _vp]),
+    # nibble rows of a key base: likewise
+    "mustafar_decode_reads_key_nibble_rows": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_uint32]),
+    "mustafar_key_nibble_rows_plan": (_i32, [_vp, _view_p, _i32, _i32, _vp, _vp]),
+    "mustafar_key_nibble_rows_fill": (_i32, [_vp, _view_p, _view_p, _i32, _i32]),
+    "mustafar_key_nibble_rows_to_tiles": (_i32, [_vp, _view_p, _view_p, _i32, _i32, _vp]),
     "mustafar_cache_append_bitmap_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_bitmap_value": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32, _vp]),
     "mustafar_cache_append_pack_key": (_i32, [_vp, _vp, _i32, _i32, _i32, _view_p, _i32]),

@@ -132,7 +132,10 @@ VALUE_LISTS = BaseForm("value_lists", "value", _lib.VIEW_VALUE_LISTS, "mustafar_
                        "mustafar_value_lists_to_tiles", "mustafar_decode_reads_value_lists", 1, 4)   # units: dwords
 VALUE_PAIR_LISTS = BaseForm("value_pair_lists", "value", _lib.VIEW_VALUE_PAIR_LISTS, "mustafar_value_pair_lists_plan", "mustafar_value_pair_lists_fill",
                             "mustafar_value_pair_lists_to_tiles", "mustafar_decode_reads_value_pair_lists", 1, 4, 1)   # units: dwords
-BASE_FORMS = (KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS)
+KEY_NIBBLE_ROWS = BaseForm("key_nibble_rows", "key", _lib.VIEW_KEY_NIBBLE_ROWS, "mustafar_key_nibble_rows_plan", "mustafar_key_nibble_rows_fill",
+                           "mustafar_key_nibble_rows_to_tiles", "mustafar_decode_reads_key_nibble_rows", 0, 256)   # units: rows of 256 bytes
+BASE_FORMS = (KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS, KEY_NIBBLE_ROWS)
+ROW_FORMS = (KEY_ROWS, KEY_NIBBLE_ROWS)        # the key base in token rows: channel bytes, 4-bit channel steps
 LIST_FORMS = (VALUE_LISTS, VALUE_PAIR_LISTS)   # the value base in channel lists: per 64-token block, per pair of blocks
 
 
@@ -215,7 +218,10 @@ class CompressedArena:
     idx = property(lambda self: self._tile_array("_idx"), lambda self, x: setattr(self, "_idx", x))
     nz = property(lambda self: self._tile_array("_nz"), lambda self, x: setattr(self, "_nz", x))
 
-    key_rows = property(lambda self: self.form is KEY_ROWS, doc="True while the base of this KEY arena is held as token rows.")
+    key_rows = property(lambda self: self.form in ROW_FORMS,
+                        doc="True while the base of this KEY arena is held as token rows, with channel bytes or with 4-bit steps.")
+    key_nibble_rows = property(lambda self: self.form is KEY_NIBBLE_ROWS,
+                               doc="True while the base of this KEY arena is held as token rows with 4-bit channel steps.")
     value_lists = property(lambda self: self.form in LIST_FORMS,
                            doc="True while the base of this VALUE arena is held as channel lists, per block or per pair of blocks.")
     value_pair_lists = property(lambda self: self.form is VALUE_PAIR_LISTS,
@@ -274,6 +280,10 @@ class CompressedArena:
     def to_key_rows(self) -> bool:
         """`_retile()` of a key arena into token rows (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_ROWS)."""
         return self._retile(KEY_ROWS)
+
+    def to_key_nibble_rows(self) -> bool:
+        """`_retile()` of a key arena into token rows with 4-bit channel steps (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_NIBBLE_ROWS)."""
+        return self._retile(KEY_NIBBLE_ROWS)
 
     def to_value_lists(self) -> bool:
         """`_retile()` of a value arena into sorted channel lists (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS)."""

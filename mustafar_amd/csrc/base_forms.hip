@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/mustafar_hip.h"
+#include "key_nibble_rows.h"
 #include "key_rows.h"
 #include "tile_view.h"
 #include "value_lists.h"
@@ -50,6 +51,11 @@ struct RowsTable {   // raw = w; units = rows of 256 bytes
     static constexpr int closing = 0;
     static __device__ uint32_t units(uint32_t w) { return (uint32_t)kr_rows((int)w); }
     static __device__ uint32_t entry(uint32_t first_row, uint32_t w) { return kr_entry(first_row, w); }
+};
+struct NibbleRowsTable {   // raw = w; units = rows of 256 bytes
+    static constexpr int closing = 0;
+    static __device__ uint32_t units(uint32_t w) { return (uint32_t)nr_rows((int)w); }
+    static __device__ uint32_t entry(uint32_t first_row, uint32_t w) { return nr_entry(first_row, w); }
 };
 struct ListsTable {   // raw = units = the block's dwords; an entry is the block's start
     static constexpr int closing = 1;
@@ -186,6 +192,144 @@ __global__ __launch_bounds__(64) void key_tiles_stream_kernel(mustafar_cache_vie
         }
         const int n = __popcll(m), n8 = (n + 7) & ~7;
         if (n + t < n8) tile[n + t] = 0;   // (at most 7 halfs of padding)
+    }
+}
+
+// ================================================================ key: tiles <-> nibble rows (key_nibble_rows.h)
+// lane t's kept channels of a block in tiles
+__device__ __forceinline__ NrMask nibble_mask(const uint64_t* __restrict__ bmp, int t)
+{
+    NrMask m{0ull, 0ull};
+    for (int d = 0; d < 64; d++) {
+        m.lo |= (uint64_t)tile_bit(bmp[d], t) << d;
+        m.hi |= (uint64_t)tile_bit(bmp[64 + d], t) << d;
+    }
+    return m;
+}
+// One share of one token, written slot by slot: steps gathered in a dword per step row, values stored as they come.
+struct NibbleShareWriter {
+    unsigned char* share;   // the share's first row
+    int n, t, s;            // its slots, the token, the next slot
+    uint32_t word;
+    __device__ void put(int step, uint16_t value)
+    {
+        if (s >= n) return;   // (a chain never outgrows the width the plan pass gave its block)
+        word |= (uint32_t)step << nr_step_shift(s);
+        *reinterpret_cast<uint16_t*>(share + nr_value_byte(n, t, s)) = value;
+        if ((s & 7) == 7) flush();
+        s++;
+    }
+    __device__ void flush()
+    {
+        *reinterpret_cast<uint32_t*>(share + nr_step_dword_byte(t, s)) = word;
+        word = 0u;
+    }
+    __device__ void gap(int g, uint16_t value)   // the spacers of a gap of g channels, then its entry
+    {
+        for (; g > kNrSpacerStep; g -= kNrSpacerStep) put(kNrSpacer, 0);
+        put(g, value);
+    }
+    __device__ void pad()   // the slots behind the last entry: step 0, value +0
+    {
+        while (s < n) put(0, 0);
+        if (s & 7) flush();
+    }
+};
+
+// One wave per (block, head): the width of the block -> table[h][b] (the scan turns it into a table entry).
+__global__ __launch_bounds__(64) void key_nibble_rows_width_kernel(mustafar_cache_view src, int nb, uint32_t* __restrict__ table)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const NrMask m = nibble_mask(tile_bmp(src, h, nb) + (int64_t)b * kD, t);
+    const int w = wave_max_i(nr_token_width(m, nr_count(m)));
+    if (t == 0) table[(int64_t)h * nb + b] = (uint32_t)w;
+}
+
+// One wave per (block, head), lane = token: the two shares of the block.
+__global__ __launch_bounds__(64) void key_nibble_rows_fill_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const int64_t tile0 = (int64_t)b * kD;
+    const uint64_t* bmp = tile_bmp(src, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(src, h, nb) + tile0;
+    const uint16_t* nz = head_stream(src, h);
+    const uint32_t ent = table_entry(dst, h, b);
+    const int w = nr_width(ent);
+    unsigned char* blk = head_bytes(dst, h) + (uint64_t)kNrRowBytes * nr_first_row(ent);
+    const NrMask m = nibble_mask(bmp, t);
+    const int last = nr_front_last(m, nr_front(w));
+    auto value = [&](int d) { return nz[2ull * idx[d] + tile_rank(bmp[d], t)]; };
+    NibbleShareWriter front{blk, nr_front(w), t, 0, 0u};
+    for (int d = 0, prev = -1; d <= last; d++) {
+        if (nr_kept(m, d)) {
+            front.gap(d - prev, value(d));
+            prev = d;
+        }
+    }
+    front.pad();
+    NibbleShareWriter back{blk + kNrRowBytes * nr_share_first(w, 1), nr_back(w), t, 0, 0u};
+    for (int d = 127, prev = 128; d > last; d--) {
+        if (nr_kept(m, d)) {
+            back.gap(prev - d, value(d));
+            prev = d;
+        }
+    }
+    back.pad();
+}
+
+// The entries of token t of a block in nibble rows, front chain then back chain: f(channel, value)
+template <class F>
+__device__ __forceinline__ void nibble_entries(const unsigned char* blk, int w, int t, const F& f)
+{
+    for (int part = 0; part < 2; part++) {
+        const unsigned char* share = blk + kNrRowBytes * nr_share_first(w, part);
+        const int n = nr_share_slots(w, part);
+        int pos = part ? 128 : -1;
+        for (int s = 0; s < n; s++) {
+            const int step = (*reinterpret_cast<const uint32_t*>(share + nr_step_dword_byte(t, s)) >> nr_step_shift(s)) & 15;
+            if (!step) break;   // (padding: nothing behind it)
+            pos += part ? -nr_advance(step) : nr_advance(step);
+            if (step != kNrSpacer) f(pos & (kD - 1), *reinterpret_cast<const uint16_t*>(share + nr_value_byte(n, t, s)));   // (& 127: an entry lies in 0 .. 127)
+        }
+    }
+}
+
+// One wave per (block, head): the 128 bitmaps of the block and every tile's length -> dst.idx[h][tile + 1].
+__global__ __launch_bounds__(64) void key_nibble_tiles_bitmap_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    __shared__ unsigned long long bits[kD];
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    bits[t] = 0ull;
+    bits[t + 64] = 0ull;
+    __syncthreads();
+    const uint32_t ent = table_entry(src, h, b);
+    const unsigned char* blk = head_bytes(src, h) + (uint64_t)kNrRowBytes * nr_first_row(ent);
+    nibble_entries(blk, nr_width(ent), t, [&](int d, uint16_t) { atomicOr(&bits[d], 1ull << (63 - t)); });
+    __syncthreads();
+    const int64_t tile0 = (int64_t)b * kD;
+    uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    for (int d = t; d < kD; d += 64) {
+        const uint64_t m = bits[d];
+        bmp[d] = m;
+        idx[d + 1] = tile_length(m);
+    }
+}
+
+// One wave per (block, head), lane = token: the streams of the block's 128 tiles, padding included.
+__global__ __launch_bounds__(64) void key_nibble_tiles_stream_kernel(mustafar_cache_view src, mustafar_cache_view dst, int nb)
+{
+    const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
+    const uint32_t ent = table_entry(src, h, b);
+    const unsigned char* blk = head_bytes(src, h) + (uint64_t)kNrRowBytes * nr_first_row(ent);
+    const int64_t tile0 = (int64_t)b * kD;
+    const uint64_t* bmp = tile_bmp(dst, h, nb) + tile0;
+    const uint32_t* idx = tile_idx(dst, h, nb) + tile0;
+    uint16_t* nz = head_stream(dst, h);
+    nibble_entries(blk, nr_width(ent), t, [&](int d, uint16_t v) { nz[2ull * idx[d] + tile_rank(bmp[d], t)] = v; });
+    for (int d = 0; d < kD; d++) {
+        const int n = __popcll(bmp[d]), n8 = (n + 7) & ~7;
+        if (n + t < n8) nz[2ull * idx[d] + n + t] = 0;   // (at most 7 halfs of padding)
     }
 }
 
@@ -519,6 +663,36 @@ int mustafar_key_rows_to_tiles(void* stream, const mustafar_cache_view* src, con
     key_tiles_bitmap_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
     tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
     key_tiles_stream_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_key_nibble_rows_plan(void* stream, const mustafar_cache_view* src, int Bp, int tokens, uint32_t* table, int64_t* head_rows)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !table || !head_rows) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    key_nibble_rows_width_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, nb, table);
+    block_table_scan_kernel<NibbleRowsTable><<<Bp, 64, 0, st>>>(nb, table, head_rows);
+    return (int)hipGetLastError();
+}
+
+int mustafar_key_nibble_rows_fill(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens)
+{
+    if (!retile_shape_ok(Bp, tokens) || !tile_view_ok(src, tokens) || !key_nibble_rows_view_ok(dst, tokens) || dst->idx_head_stride != tokens / 64)
+        return MUSTAFAR_EINVAL;
+    const int nb = tokens / 64;
+    key_nibble_rows_fill_kernel<<<dim3(nb, Bp), 64, 0, static_cast<hipStream_t>(stream)>>>(*src, *dst, nb);
+    return (int)hipGetLastError();
+}
+
+int mustafar_key_nibble_rows_to_tiles(void* stream, const mustafar_cache_view* src, const mustafar_cache_view* dst, int Bp, int tokens, int64_t* head_total)
+{
+    if (!retile_shape_ok(Bp, tokens) || !key_nibble_rows_view_ok(src, tokens) || !tile_view_ok(dst, tokens) || !dst->nz_head_stride) return MUSTAFAR_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nb = tokens / 64;
+    key_nibble_tiles_bitmap_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
+    tile_offsets_scan_kernel<<<Bp, 64, 0, st>>>(*dst, nb, head_total);
+    key_nibble_tiles_stream_kernel<<<dim3(nb, Bp), 64, 0, st>>>(*src, *dst, nb);
     return (int)hipGetLastError();
 }
 

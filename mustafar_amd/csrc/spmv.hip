@@ -30,6 +30,7 @@
 
 #include "../../include/mustafar_hip.h"
 #include "headdim64.h"
+#include "key_nibble_rows.h"
 #include "key_rows.h"
 #include "tile_view.h"
 #include "value_lists.h"
@@ -2737,6 +2738,91 @@ __device__ __forceinline__ void key_rows_phase(const unsigned char* __restrict__
     }
 }
 
+// ---- key phase over NIBBLE ROWS (include/mustafar_hip.h: MUSTAFAR_VIEW_KEY_NIBBLE_ROWS; key_nibble_rows.h).  Lane = token.  A wave of the pair
+// walks ONE share of a block -- the even wave the front chain, ascending from channel -1, the odd wave the back chain, descending from
+// channel 128 -- so that its chain starts from a constant.  A WORD is one step row and the four value rows that go with it: five
+// coalesced 256-byte loads for eight slots (token rows: six for eight), then per slot one field extract, one clamp (step 15 moves 14) and
+// one multiply-add into the running byte offset into the q table, one ds_read_b64 and four v_fma_mix.  The table is [130][4 heads] fp16 at
+// a FIXED LDS address: a zero guard entry at each end (positions -1 and 128: where a chain stands before its first step), so that every
+// lookup lands inside it.  A share is a buffer of its own: the value rows a last word lacks lie beyond it and load +0, under steps of 0.
+// The words of blocks A and B alternate, each requested a word ahead.  Exact fp16 x fp16 products.
+struct KeyNibbleWord {
+    uint32_t st, v[4];   // eight steps; slots 2k, 2k + 1 as half2
+};
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t key_nibble_share(const unsigned char* __restrict__ rows, uint32_t ent, int odd, bool active)
+{
+    const int w = nr_width(ent);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(rows + (uint64_t)kNrRowBytes * (nr_first_row(ent) + nr_share_first(w, odd))), (short)0,
+                                             active ? kNrRowBytes * nr_share_rows(nr_share_slots(w, odd)) : 0, 0x00020000);
+}
+__device__ __forceinline__ KeyNibbleWord key_nibble_word(__amdgpu_buffer_rsrc_t share, int nstep, int wd, int lane4)
+{
+    constexpr int kStreamAux = 2;
+    KeyNibbleWord r;
+    r.st = __builtin_amdgcn_raw_buffer_load_b32(share, lane4, 256 * wd, kStreamAux);
+#pragma unroll
+    for (int k = 0; k < 4; k++) r.v[k] = __builtin_amdgcn_raw_buffer_load_b32(share, lane4, 256 * (nstep + 4 * wd + k), kStreamAux);
+    return r;
+}
+// one word: eight table reads along the chain (pos: the running byte offset into the table; stride: +-8), then 32 products
+__device__ __forceinline__ void key_nibble_step(const KeyNibbleWord& r, int& pos, int stride, const unsigned char* qtab, float (&s)[4])
+{
+    uint2 q[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int step = min((int)((r.st >> (4 * k)) & 15u), kNrSpacerStep);
+        pos += step * stride;   // (both within 24 bits: one v_mad_i32_i24)
+        q[k] = *reinterpret_cast<const uint2*>(qtab + pos);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const h16x2 v = __builtin_bit_cast(h16x2, r.v[k >> 1]);
+        const h16x2 q01 = __builtin_bit_cast(h16x2, q[k].x), q23 = __builtin_bit_cast(h16x2, q[k].y);
+        const float x = (float)v[k & 1];
+        s[0] = __builtin_fmaf(x, (float)q01[0], s[0]);
+        s[1] = __builtin_fmaf(x, (float)q01[1], s[1]);
+        s[2] = __builtin_fmaf(x, (float)q23[0], s[2]);
+        s[3] = __builtin_fmaf(x, (float)q23[1], s[3]);
+    }
+}
+// rows: the head's rows; entA / entB: the table entries of the two blocks; qtab: the guarded table (entry 0 = position -1); mid: called
+// behind the first requests
+template <class MID>
+__device__ __forceinline__ void key_nibble_rows_phase(const unsigned char* __restrict__ rows, uint32_t entA, uint32_t entB, bool actB, int odd, int lane,
+                                                      const unsigned char* qtab, float (&sA)[4], float (&sB)[4], const MID& mid)
+{
+    const int lane4 = lane * 4;
+    const int nstepA = nr_step_rows(nr_share_slots(nr_width(entA), odd)), nstepB = actB ? nr_step_rows(nr_share_slots(nr_width(entB), odd)) : 0;
+    const __amdgpu_buffer_rsrc_t shA = key_nibble_share(rows, entA, odd, true), shB = key_nibble_share(rows, entB, odd, actB);
+    const int stride = odd ? -8 : 8;
+    int posA = odd ? 8 * 129 : 0, posB = posA;
+    auto request = [&](__amdgpu_buffer_rsrc_t sh, int nstep, int i) {   // word i of the share, or nothing beyond it
+        KeyNibbleWord r{0u, {0u, 0u, 0u, 0u}};
+        if (i < nstep) r = key_nibble_word(sh, nstep, i, lane4);
+        return r;
+    };
+    KeyNibbleWord ra = request(shA, nstepA, 0), rb = request(shB, nstepB, 0);
+    mid();
+    const int both = nstepA < nstepB ? nstepA : nstepB, n = nstepA > nstepB ? nstepA : nstepB;
+    int i = 0;
+    // the words both blocks have but their last: no condition inside
+#pragma unroll 1
+    for (; i + 1 < both; i++) {
+        key_nibble_step(ra, posA, stride, qtab, sA);
+        ra = key_nibble_word(shA, nstepA, i + 1, lane4);
+        key_nibble_step(rb, posB, stride, qtab, sB);
+        rb = key_nibble_word(shB, nstepB, i + 1, lane4);
+    }
+    // the last positions: a block may have a word more than the other, or be absent
+#pragma unroll 1
+    for (; i < n; i++) {
+        if (i < nstepA) key_nibble_step(ra, posA, stride, qtab, sA);
+        ra = request(shA, nstepA, i + 1);
+        if (i < nstepB) key_nibble_step(rb, posB, stride, qtab, sB);
+        rb = request(shB, nstepB, i + 1);
+    }
+}
+
 // ---- value phase over SORTED CHANNEL LISTS (include/mustafar_hip.h: MUSTAFAR_VIEW_VALUE_LISTS; value_lists.h).  Lane i = the channel perm[i]
 // of the wave's half; a WORD is a token row (4 token bytes per lane) and the two value rows that go with it (a half2 per lane each): three
 // loads per wave at scalar word offset + lane offset, then per slot one shift of its token byte, one ds_read_b64 of the pair's e table
@@ -2882,7 +2968,8 @@ struct ValueListState<true> {
 // LISTS: the value BASE arrives as sorted channel lists (v_nz = the blocks, v_idx = the block table).  An instantiation of its own, chosen
 // by the host: the launches that read value tiles -- two blocks per workgroup among them -- keep the code they had.
 // PAIRS (with LISTS): the lists run over pairs of blocks (MUSTAFAR_VIEW_VALUE_PAIR_LISTS) -- instantiations of their own again.
-template <int ENG, bool EXT = false, int G = 4, bool MASK = false, bool LISTS = false, bool PAIRS = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
+// NIBBLE (with PAIRS): the key BASE arrives as nibble rows (MUSTAFAR_VIEW_KEY_NIBBLE_ROWS) -- instantiations of their own once more.
+template <int ENG, bool EXT = false, int G = 4, bool MASK = false, bool LISTS = false, bool PAIRS = false, bool NIBBLE = false>   // (a pair walks ONE super-block: launches of more than four blocks per workgroup run
                                                                      // decode_onepass_leanpair_kernel; round 5 carried an uninstantiated online form here -- removed in round 6)
 __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     const uint64_t* __restrict__ k_bmp, const unsigned char* __restrict__ k_nz, const uint32_t* __restrict__ k_idx,
@@ -2893,6 +2980,7 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     static_assert(G == 4 || ENG == 0, "dot2 and the matrix pipe work on four heads; G < 4 runs v_fma_mix");
     static_assert(!LISTS || (G == 4 && ENG != 1), "channel lists are read by the GQA-4 launches on the vector engines");
     static_assert(!PAIRS || LISTS, "pair lists are channel lists");
+    static_assert(!NIBBLE || PAIRS, "nibble rows are read next to pair lists");
     constexpr int HW = G >= 2 ? G / 2 : 1;   // heads a wave of the pair finishes (G = 1: the even wave its one head, the odd wave none)
     constexpr int kTabBytes = ENG == 1 ? 4 * kKeyTabStride + 2 * 2 * 4 * kValTabStride : 0;   // q rows; per pair TWO e tables (blocks A, B)
     __shared__ __attribute__((aligned(16))) unsigned char smem[kWaves * kStageBytes + kTabBytes];
@@ -3020,6 +3108,7 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
     // rows: the q table of the key phase, [128 channels][4 heads] fp16, behind the partial scores in the FIRST wave's stage window: a fixed
     // address, dead until that wave's value phase, which starts behind the barriers that end every wave's key phase.  Every wave writes
     // the whole table -- the same bytes -- before it reads it: no barrier.  Lane l holds channels 2 l, 2 l + 1 of the four heads.
+    // NIBBLE: [130][4 heads] -- positions -1 .. 128, the two ends zeros -- at the same place (16 bytes longer, still inside the window)
     const unsigned char* qtab = smem + 2 * 64 * G * 4;
     // lists: the table entries of the pair's two blocks (start, end of A in lanes 0, 1; of B in lanes 2, 3), requested here, read in the key
     // phase's hook.  The pair's e tables, [block A | block B][64 tokens][4 heads] fp16, lie behind the partial scores in its EVEN wave's stage
@@ -3039,7 +3128,10 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
         if (rows) {
             const uint32_t* q32 = reinterpret_cast<const uint32_t*>(a.q + (int64_t)bh0 * kD) + lane;
             const uint32_t q0 = q32[0], q1 = q32[64], q2 = q32[128], q3 = q32[192];
-            *reinterpret_cast<uint4*>(smem + 2 * 64 * G * 4 + lane * 16) =
+            if constexpr (NIBBLE) {
+                if (lane < 2) *reinterpret_cast<uint2*>(smem + 2 * 64 * G * 4 + lane * (8 * 129)) = make_uint2(0u, 0u);
+            }
+            *reinterpret_cast<uint4*>(smem + 2 * 64 * G * 4 + (NIBBLE ? 8 : 0) + lane * 16) =
                 make_uint4((q0 & 0xffffu) | (q1 << 16), (q2 & 0xffffu) | (q3 << 16), (q0 >> 16) | (q1 & 0xffff0000u), (q2 >> 16) | (q3 & 0xffff0000u));
             __builtin_amdgcn_wave_barrier();
         }
@@ -3094,7 +3186,8 @@ __global__ __launch_bounds__(kThreads, kLpWaves) void decode_onepass_sb_kernel(
                 }
                 // (readfirstlane: the entries are wave-uniform, and the phase builds buffer resources -- scalar registers -- from them)
                 const uint32_t entA = __builtin_amdgcn_readfirstlane(ktab[tAc]), entB = __builtin_amdgcn_readfirstlane(ktab[tBc]);
-                key_rows_phase(kn, entA, entB, actB, odd, lane, qtab, sA, sB, reqVA);
+                if constexpr (NIBBLE) key_nibble_rows_phase(kn, entA, entB, actB, odd, lane, qtab, sA, sB, reqVA);
+                else key_rows_phase(kn, entA, entB, actB, odd, lane, qtab, sA, sB, reqVA);
             }
           } else {
             const uint64_t* kbA = kb + (int64_t)tAc * kTilesPerTb;
@@ -4171,7 +4264,7 @@ using OnePassKernel = void (*)(const uint64_t*, const unsigned char*, const uint
                                const uint32_t*, const uint32_t*, OneArgs, int64_t, int64_t, uint32_t, int64_t, int64_t, uint32_t);
 // eng: 0 for G < 4.  ext: the EXT instantiation.  mask: the MASK instantiation (the pair form has none: it reads a.mask at run time).
 // nullptr: no such kernel -- the MHA pair and super-block launches always run EXT (decode_attention), the matrix pipe has no small form.
-inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask, bool lists = false, bool pairs = false)
+inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mask, bool lists = false, bool pairs = false, bool nibble = false)
 {
     const int row = G == 4 ? eng : G == 2 ? 3 : 4;   // GQA-4: v_fma_mix, matrix pipe, v_dot2; GQA-2; MHA
     const int col = (ext ? 2 : 0) + (mask ? 1 : 0);  // EXT = false: MASK false, true; EXT = true: MASK false, true
@@ -4206,6 +4299,12 @@ inline OnePassKernel onepass_select(int form, int G, int eng, bool ext, bool mas
         {decode_onepass_sb_kernel<0, false, 4, false, true, true>, decode_onepass_sb_kernel<0, false, 4, true, true, true>, decode_onepass_sb_kernel<0, true, 4, false, true, true>, decode_onepass_sb_kernel<0, true, 4, true, true, true>},
         {decode_onepass_sb_kernel<2, false, 4, false, true, true>, decode_onepass_sb_kernel<2, false, 4, true, true, true>, decode_onepass_sb_kernel<2, true, 4, false, true, true>, decode_onepass_sb_kernel<2, true, 4, true, true, true>},
     };
+    // and with a key base of nibble rows (nibble: with pairs)
+    static constexpr OnePassKernel kSbNibble[2][4] = {
+        {decode_onepass_sb_kernel<0, false, 4, false, true, true, true>, decode_onepass_sb_kernel<0, false, 4, true, true, true, true>, decode_onepass_sb_kernel<0, true, 4, false, true, true, true>, decode_onepass_sb_kernel<0, true, 4, true, true, true, true>},
+        {decode_onepass_sb_kernel<2, false, 4, false, true, true, true>, decode_onepass_sb_kernel<2, false, 4, true, true, true, true>, decode_onepass_sb_kernel<2, true, 4, false, true, true, true>, decode_onepass_sb_kernel<2, true, 4, true, true, true, true>},
+    };
+    if (nibble) return lists && pairs && form == kFormSb && G == 4 && eng != 1 ? kSbNibble[eng == 2][col] : nullptr;
     if (lists && pairs) return form == kFormSb && G == 4 && eng != 1 ? kSbPairs[eng == 2][col] : nullptr;
     if (lists) return form == kFormSb && G == 4 && eng != 1 ? kSbLists[eng == 2][col] : nullptr;
     return form == kFormSmall ? kSmall[row][col] : form == kFormSb ? kSb[row][col] : kPair[row][ext ? 1 : 0];
@@ -4349,14 +4448,18 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
     // a key base of token rows (MUSTAFAR_VIEW_KEY_ROWS), a value base of sorted channel lists (MUSTAFAR_VIEW_VALUE_LISTS): read by the
     // super-block launch alone (checked where the shape is known); no other flag exists, and neither side takes the other's
     // (value_lists: either list form; value_pairs: MUSTAFAR_VIEW_VALUE_PAIR_LISTS)
-    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS, value_pairs = c.v.flags == MUSTAFAR_VIEW_VALUE_PAIR_LISTS;
+    // (key_rows: either row form; key_nibble: MUSTAFAR_VIEW_KEY_NIBBLE_ROWS, read next to pair lists only)
+    const bool key_nibble = c.k.flags == MUSTAFAR_VIEW_KEY_NIBBLE_ROWS;
+    const bool key_rows = c.k.flags == MUSTAFAR_VIEW_KEY_ROWS || key_nibble, value_pairs = c.v.flags == MUSTAFAR_VIEW_VALUE_PAIR_LISTS;
     const bool value_lists = c.v.flags == MUSTAFAR_VIEW_VALUE_LISTS || value_pairs;
-    if ((c.k.flags && !key_rows) || (c.v.flags && !value_lists) || ((key_rows || value_lists) && (!onepass || c.T <= 0))) return MUSTAFAR_EINVAL;
+    if ((c.k.flags && !key_rows) || (c.v.flags && !value_lists) || ((key_rows || value_lists) && (!onepass || c.T <= 0)) ||
+        (key_nibble && !value_pairs))
+        return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && (!c.k.bmp || !c.k.nz_offset)) || !c.k.nz || !c.k.idx || (!value_lists && (!c.v.bmp || !c.v.nz_offset)) || !c.v.nz || !c.v.idx))
         return MUSTAFAR_EINVAL;
     const int64_t tiles = (int64_t)(extents ? c.T_base : c.T) * 2;   // (the base views hold T_base of the T tokens when the cache grew by extents)
     // the form rules are tile_view.h's; here on top: the launch takes the head stride in 32 bits
-    if (key_rows && (!key_rows_view_ok(&c.k, (int)(tiles / 2)) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
+    if (key_rows && (!(key_nibble ? key_nibble_rows_view_ok(&c.k, (int)(tiles / 2)) : key_rows_view_ok(&c.k, (int)(tiles / 2))) || c.k.nz_head_stride >> 32)) return MUSTAFAR_EINVAL;
     if (value_lists && (!(value_pairs ? value_pair_lists_view_ok(&c.v, (int)(tiles / 2)) : value_lists_view_ok(&c.v, (int)(tiles / 2))) || c.v.nz_head_stride >> 32))
         return MUSTAFAR_EINVAL;
     if (c.T > 0 && ((!key_rows && ((c.k.bmp_head_stride && c.k.bmp_head_stride < tiles) || (c.k.idx_head_stride && c.k.idx_head_stride < tiles + 1))) ||
@@ -4400,7 +4503,7 @@ int decode_attention(const DecodeCall& c, hipEvent_t* ev, int* choice)
         // launches its plain G = 1 instantiation.)
         if (!extents && G == 1) a.nb0 = c.T / 64;
         const bool ext = extents || (G == 1 && s.form != kFormSmall);
-        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr, value_lists, value_pairs);
+        const OnePassKernel kernel = onepass_select(s.form, G, eng, ext, mask.ptr != nullptr, value_lists, value_pairs, key_nibble);
         if (!kernel) return MUSTAFAR_EINVAL;   // (no shape selects a kernel the table leaves out)
         hipExtLaunchKernelGGL(kernel, dim3(s.S1, gy + (s.win_rows < 0 ? -s.win_rows : s.win_rows)), dim3(kThreads), 0, st, ev ? ev[0] : nullptr,
                               ev ? ev[1] : nullptr, 0, c.k.bmp, kz, c.k.idx, c.k.nz_offset, c.v.bmp, vz, c.v.idx, c.v.nz_offset, a,
@@ -4708,6 +4811,11 @@ int mustafar_decode_reads_value_lists(int num_key_value_groups, int T, int gy, i
 int mustafar_decode_reads_value_pair_lists(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
 {
     return mustafar_decode_reads_key_rows(num_key_value_groups, T, gy, ld_scores, flags);   // and the lists over pairs of blocks
+}
+
+int mustafar_decode_reads_key_nibble_rows(int num_key_value_groups, int T, int gy, int ld_scores, uint32_t flags)
+{
+    return mustafar_decode_reads_key_rows(num_key_value_groups, T, gy, ld_scores, flags);   // and the nibble rows of a key base
 }
 
 int mustafar_profile_begin(int max_records)

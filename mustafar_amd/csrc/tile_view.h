@@ -51,6 +51,12 @@ inline bool key_rows_view_ok(const mustafar_cache_view* v, int tokens)
     return v && v->flags == MUSTAFAR_VIEW_KEY_ROWS && v->idx && v->nz && v->nz_head_stride > 0 && (v->nz_head_stride & 15) == 0 &&
            v->idx_head_stride >= tokens / 64;
 }
+// MUSTAFAR_VIEW_KEY_NIBBLE_ROWS: as the token rows -- rows of 256 bytes from the head's start, a table entry per block
+inline bool key_nibble_rows_view_ok(const mustafar_cache_view* v, int tokens)
+{
+    return v && v->flags == MUSTAFAR_VIEW_KEY_NIBBLE_ROWS && v->idx && v->nz && v->nz_head_stride > 0 && (v->nz_head_stride & 15) == 0 &&
+           v->idx_head_stride >= tokens / 64;
+}
 // MUSTAFAR_VIEW_VALUE_LISTS: a table entry per block and the closing one
 inline bool value_lists_view_ok(const mustafar_cache_view* v, int tokens)
 {

@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, compression, mustafar_package
-from .cache import KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS, BaseForm, CompressedArena
+from .cache import KEY_NIBBLE_ROWS, KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS, BaseForm, CompressedArena
 from .cache64 import ExtentCache64, compress_raw_pair_hd64
 from .compression import _compress                                                                          # noqa: F401  (re-exported)
 from .reflayout import FlatStreams, _flat_stream, append_compressed, as_cache, nz_offset_from_idxs         # noqa: F401  (re-exported)
@@ -87,6 +87,12 @@ class MustafarConfig:
     # (cache.CompressedArena.to_key_rows) where the launch of the call shape reads them (mustafar_decode_reads_key_rows: the one-pass
     # super-block form).  Whatever needs tiles retiles back (CompressedArena.require_tiles).  MUSTAFAR_KEY_ROWS=0 turns it off everywhere
     key_rows: bool = True
+    # The token rows with 4-bit channel steps (cache.CompressedArena.to_key_nibble_rows): what to_fused() prefers for the key base next to a
+    # value base that took the lists over pairs of blocks.  None: from NIBBLE_ROWS_FROM compressed tokens per head on (the form saves
+    # bytes, and was measured where the bytes are the time: DESIGN.md 5; a small cache keeps the channel bytes); True: wherever the launch
+    # reads it.  False / MUSTAFAR_KEY_NIBBLE_ROWS=0 falls back to the rows with channel bytes; key_rows=False / MUSTAFAR_KEY_ROWS=0 turns
+    # both off
+    key_nibble_rows: Optional[bool] = None
     # The value base as sorted channel lists (cache.CompressedArena.to_value_lists), in the same launches and by the same rules
     # (mustafar_decode_reads_value_lists).  MUSTAFAR_VALUE_LISTS=0 turns it off everywhere
     value_lists: bool = True
@@ -336,7 +342,9 @@ class MustafarAttention:
         cfg = self.cfg
         if form is VALUE_PAIR_LISTS and not self._wants_form(VALUE_LISTS):   # (the knob of the lists rules both list forms)
             return False
-        return getattr(cfg, form.name) and os.environ.get("MUSTAFAR_" + form.name.upper(), "1") != "0" and cfg.head_dim == 128 and \
+        if form is KEY_NIBBLE_ROWS and not (self._wants_form(KEY_ROWS) and self._wants_form(VALUE_PAIR_LISTS)):   # (read next to pair lists only)
+            return False
+        return getattr(cfg, form.name) is not False and os.environ.get("MUSTAFAR_" + form.name.upper(), "1") != "0" and cfg.head_dim == 128 and \
             self.num_key_value_groups % 4 == 0 and cfg.engine in ("valu", "fma_mix", "dot2", None, "default")
 
     def _retile_where_read(self, cache, window, form: BaseForm) -> None:
@@ -352,6 +360,13 @@ class MustafarAttention:
         (`require_tiles()` raises under capture.)"""
         if isinstance(cache, CompressedArena) and cache.form is not None and not self._reads_form(cache, T, ops.ld, ops.flags):
             cache.require_tiles()
+
+    def _tiles_unless_read_pair(self, k, v, T: int, ops) -> None:
+        """`_tiles_unless_read()` of both sides; nibble rows of a key base are read next to a value base in pair lists only."""
+        self._tiles_unless_read(k, T, ops)
+        self._tiles_unless_read(v, T, ops)
+        if isinstance(k, CompressedArena) and k.form is KEY_NIBBLE_ROWS and getattr(v, "form", None) is not VALUE_PAIR_LISTS:
+            k.require_tiles()
 
     def _kth(self, D: int) -> Tuple[int, int]:
         """`(kth_k, kth_v)`: the prune rule's kth (model :97) for K and V rows of D channels at the configured sparsities."""
@@ -411,6 +426,8 @@ class MustafarAttention:
     # ---- fused decode (extension) ---------------------------------------------------------------------------
     EXTENT_CACHE_64 = ExtentCache64   # the cache class of hd64_extents (tests subclass it with a small table)
 
+    NIBBLE_ROWS_FROM = 2048   # compressed tokens per head from which MustafarConfig(key_nibble_rows=None) prefers nibble rows
+
     def to_fused(self, past):
         """Wrap the two local windows of a reference-layout `past` into appendable buffers."""
         k_c, k_w, v_c, v_w, C, L = past
@@ -425,13 +442,16 @@ class MustafarAttention:
         if not isinstance(k_w, Window):
             cap = self.cfg.residual_length + 256   # the longest window: the step that fires the trigger (model :324) holds R + 256 rows
             k_w, v_w = Window(k_w, cap), Window(v_w, cap)
-        self._retile_where_read(k_c, k_w, KEY_ROWS)
         # the lists over pairs of blocks are preferred where key rows are wanted too, the configuration they were measured in:
         # a matter of the configuration and the knobs, not of the state of this key arena; an arena that took them is no longer in tiles
         # for the line below
         if self._wants_form(KEY_ROWS):
             self._retile_where_read(v_c, v_w, VALUE_PAIR_LISTS)
         self._retile_where_read(v_c, v_w, VALUE_LISTS)
+        # the key base: nibble rows next to a value base that took the pair lists (the measured configuration), else rows with channel bytes
+        if getattr(v_c, "form", None) is VALUE_PAIR_LISTS and (self.cfg.key_nibble_rows or k_c.total_tokens >= self.NIBBLE_ROWS_FROM):
+            self._retile_where_read(k_c, k_w, KEY_NIBBLE_ROWS)
+        self._retile_where_read(k_c, k_w, KEY_ROWS)
         return Past(k_c, k_w, v_c, v_w, C, L)
 
     @staticmethod
@@ -591,8 +611,7 @@ class MustafarAttention:
                 k_c, v_c = k_c.consolidate(), v_c.consolidate()   # (T == their base tokens now: the view form)
                 k_c.ext_table, v_c.ext_table
                 past = past._replace(k_cache=k_c, v_cache=v_c)
-            self._tiles_unless_read(k_c, T, ops)
-            self._tiles_unless_read(v_c, T, ops)
+            self._tiles_unless_read_pair(k_c, v_c, T, ops)
         _call_decode(k_c, v_c, T, ops, D, t_device, lse)
         out = ops.out
         if step_counter is not None:
@@ -953,8 +972,7 @@ class MustafarAttention:
         # no window argument at all: the window-less form of the entry points with an LSE; an arena's tables only when it has extents
         ops = self._decode_operands(query_states, tokens, mask=mask_args(attention_mask, bsz, tokens, dev))
         lse = torch.empty((bsz, H), dtype=torch.float32, device=dev)
-        self._tiles_unless_read(k, tokens, ops)
-        self._tiles_unless_read(v, tokens, ops)
+        self._tiles_unless_read_pair(k, v, tokens, ops)
         _call_decode(k, v, tokens, ops, D, None, lse)
         return ops.out, lse
 
