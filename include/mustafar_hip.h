@@ -745,6 +745,74 @@ int mustafar_decode_multi_segment(void* stream, const mustafar_cache_view* k_bas
                                   const void* mask, int64_t mask_batch_stride, int64_t mask_row_stride, int mask_rows, int heads_per_mask);
 
 /*
+ * Ragged batches: independent per-sequence caches decoded in one call (ragged_batch.hip).  These three symbols were added
+ * WITHOUT a change of mustafar_abi_version(), which stays 115: nothing that existed changed its behaviour or its bits, and a caller
+ * detects the new entry points by symbol (dlsym), not by version.
+ *
+ * mustafar_sequence: one sequence of a ragged batch -- a cache of `kv_heads` heads, its two windows and its lengths --, an entry of a
+ *   DEVICE table that mustafar_ragged_set_sequences alone writes (it stores the row strides of the base views resolved; what else it
+ *   stores is its business).  176 bytes: k_base at 0, v_base at 64, k_extents at 128, v_extents at 136, k_window at 144, v_window at 152,
+ *   T_base at 160, T at 164, window_len at 168, window_capacity at 172.
+ *
+ * mustafar_ragged_set_sequences: entries [first, first + n) of `table` (DEVICE, 8-byte aligned, the caller's allocation of at least
+ *   first + n entries) <- `items` (a HOST array), through small launches that carry the items in their kernel arguments (16 entries per
+ *   launch), as mustafar_trigger_finish_batch lists views in table slots: no host-to-device copy, nothing allocated, nothing read back; in
+ *   stream order with the decode calls that read the table.  Every item is validated before the first launch, by the rules of
+ *   mustafar_decode_multi_query: T % 64 == 0, T > 0 needs T_base > 0, T_base % 64 == 0 and T_base <= T; T > T_base needs both tables,
+ *   T_base % 256 == 0, (T - T_base) % 256 == 0 and at most 512 entries; with T_base > 0 both base views are what
+ *   mustafar_decode_shared_segment accepts for `kv_heads` heads (flags == 0: tiles); the windows are 16-byte aligned and not NULL;
+ *   n_q <= window_len <= window_capacity <= 1024.  window_len == 0 marks an EMPTY slot: nothing else of such an item is looked at, every
+ *   pointer may be NULL.  With T == 0 the base views, and with T == T_base the tables, are not looked at.
+ *   MUSTAFAR_EINVAL before any launch for an item that breaks a rule, n < 1, first < 0, a NULL or misaligned (8 B) table, NULL items,
+ *   kv_heads outside 1..65535, head_dim not 64 or 128, n_q < 1.
+ *
+ * mustafar_decode_ragged: mustafar_decode_multi_query for n_seqs sequences that share nothing but the head geometry and n_q.  Query token
+ *   j of sequence s attends to the compressed tokens [0, T_s) of its own cache and to rows [0, window_len_s - n_q + j] of its own window,
+ *   the causal limit of that call; there is no mask (a ragged batch has no padding to hide).  Three launches (two with k_new == NULL):
+ *   the n_q new rows of sequence s go to rows [window_len_s - n_q, window_len_s) of its windows; a workgroup of (sequence, kv head) loads
+ *   its entry with scalar loads and serves a run of blocks or 64 window rows as in mustafar_decode_multi_query; the row kernel folds the
+ *   slabs of a row in the sequence's own numbering.
+ *   table               DEVICE, n_seqs entries written by mustafar_ragged_set_sequences with the same kv_heads, n_q and head_dim; read at
+ *                       every launch, so one captured graph of this call serves whatever the table holds at replay
+ *   q, out              fp16 [n_seqs, kv_heads * num_key_value_groups, n_q, head_dim], contiguous, 16-byte aligned
+ *   lse                 fp32 [n_seqs, kv_heads * num_key_value_groups, n_q], REQUIRED
+ *   k_new / v_new       [n_seqs, kv_heads, n_q, head_dim], 16-byte aligned, or both NULL: the rows are already stored
+ *   T_max, window_capacity_max   size the grid (ceil(T_max / 64 / run length) + ceil(window_capacity_max / 64), n_seqs * kv_heads), the slabs
+ *                       and the workspace; run length: the rule of mustafar_decode_multi_query (R = n_q * groups and head_dim alone)
+ *   clamps              the kernels clamp every length they load: blocks in use T_s / 64 into [0, T_max / 64]; blocks from the base
+ *                       min(T_base_s / 64, blocks in use); the window capacity into [0, min(window_capacity_max, 1024)]; the window length
+ *                       into [n_q, capacity]; an entry without both tables reads its base alone.  A stale or wrong entry gives a wrong
+ *                       row, never an address outside a window
+ *   dead workgroups     a run with no block in use for its sequence, a window chunk at or beyond its sequence's window and every workgroup
+ *                       of an empty slot touch no byte of any cache or window and write no slab; table entries of a sequence's extents
+ *                       at or beyond (T_s - T_base_s) / 256 are never read
+ *   empty slot          reads nothing, appends nothing; out = 0 and lse = -inf, as mustafar_merge_attention_states gives an all-empty row
+ *   bits                out and lse of sequence s are bit for bit those of mustafar_decode_multi_query on that sequence alone (Bp = kv_heads,
+ *                       its own T, T_base, tables, window length and capacity), whatever else the batch holds and in whatever slot
+ *   MUSTAFAR_EINVAL before any launch for: n_seqs < 1, kv_heads < 1, n_seqs * kv_heads > 65535, n_q * num_key_value_groups outside 1..64,
+ *   num_key_value_groups outside 1..8, head_dim not 64 or 128, T_max < 0 or T_max % 64 != 0, window_capacity_max outside n_q..1024, exactly
+ *   one of k_new / v_new NULL, a NULL or misaligned table (8 B), q / out / workspace / new rows (16 B) or lse (4 B).  Nothing is allocated
+ *   and nothing is read back.
+ * mustafar_decode_ragged_workspace_bytes: mustafar_decode_multi_query_workspace_bytes(T_max, window_capacity_max, n_seqs * kv_heads,
+ *   num_key_value_groups, n_q, head_dim); 0 for the shapes the call refuses.
+ */
+typedef struct mustafar_sequence {           /* 176 bytes; an entry of a DEVICE table, written by mustafar_ragged_set_sequences only */
+    mustafar_cache_view k_base, v_base;      /* tokens [0, T_base) of kv_heads heads, TILE format (flags == 0), any strides */
+    const mustafar_cache_view* k_extents;    /* DEVICE tables as in mustafar_decode_multi_query; NULL when T == T_base */
+    const mustafar_cache_view* v_extents;
+    void* k_window;  void* v_window;         /* [kv_heads, window_capacity, head_dim] fp16, 16-byte aligned */
+    int32_t T_base, T, window_len, window_capacity;   /* window_len counts the rows AFTER this call's append; 0 = the slot is empty */
+} mustafar_sequence;
+
+int64_t mustafar_decode_ragged_workspace_bytes(int T_max, int window_capacity_max, int n_seqs, int kv_heads,
+                                               int num_key_value_groups, int n_q, int head_dim);
+int mustafar_ragged_set_sequences(void* stream, mustafar_sequence* table, int first, int n, const mustafar_sequence* items,
+                                  int kv_heads, int n_q, int head_dim);
+int mustafar_decode_ragged(void* stream, const mustafar_sequence* table, int n_seqs, int kv_heads, int num_key_value_groups, int n_q,
+                           int T_max, int window_capacity_max, const void* q, const void* k_new, const void* v_new,
+                           void* out, float* lse, void* workspace, float sqrt_d, int head_dim);
+
+/*
  * head_dim 64 (ABI 109): a prefill compressed from the RAW rows, and 256-token pieces gathered into one reference-layout cache.  D must
  * be 64 in both (MUSTAFAR_EINVAL otherwise); both validate before they launch.
  *

@@ -37,6 +37,15 @@ class TriggerItem(ctypes.Structure):
 
 _item_p = ctypes.POINTER(TriggerItem)
 
+
+class Sequence(ctypes.Structure):
+    """`mustafar_sequence` of include/mustafar_hip.h: one sequence of a ragged batch (an entry of the device table, 176 bytes)."""
+    _fields_ = [("k_base", CacheView), ("v_base", CacheView), ("k_extents", _vp), ("v_extents", _vp), ("k_window", _vp), ("v_window", _vp),
+                ("T_base", ctypes.c_int32), ("T", ctypes.c_int32), ("window_len", ctypes.c_int32), ("window_capacity", ctypes.c_int32)]
+
+
+_seq_p = ctypes.POINTER(Sequence)
+
 # The seven fused decode entry points share one run of arguments (q ... flags: what hook.py builds as one tuple); each adds its own
 # head (the stream and how the cache arrives) and tail (T_device, head_dim, lse).
 _DECODE_TAIL = [_vp] * 5 + [_i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i32, ctypes.c_uint32]
@@ -75,6 +84,10 @@ SIGNATURES = {
     "mustafar_decode_multi_segment_workspace_bytes": (_i64, [_i32] * 5),
     "mustafar_decode_multi_segment": (_i32, [_vp, _view_p, _view_p, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
                                              _i32, _vp, _i64, _i64, _i32, _i32]),
+    # ragged batches (independent per-sequence caches in one call): likewise added at ABI 115, detected by symbol
+    "mustafar_decode_ragged_workspace_bytes": (_i64, [_i32] * 7),
+    "mustafar_ragged_set_sequences": (_i32, [_vp, _vp, _i32, _i32, _seq_p, _i32, _i32, _i32]),
+    "mustafar_decode_ragged": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i32]),
     "mustafar_window_keep_rows":(_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "mustafar_trigger_compress_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "mustafar_trigger_finish_batch_hd": (_i32, [_vp, _i32, _item_p, _i64, _i32, _i32, _i32, _i32]),

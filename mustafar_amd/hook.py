@@ -36,6 +36,7 @@ import torch.nn.functional as F
 from . import _lib, compression, mustafar_package
 from .cache import KEY_NIBBLE_ROWS, KEY_ROWS, VALUE_LISTS, VALUE_PAIR_LISTS, BaseForm, CompressedArena
 from .cache64 import ExtentCache64, compress_raw_pair_hd64
+from .ragged import RaggedBatch
 from .compression import _compress                                                                          # noqa: F401  (re-exported)
 from .reflayout import FlatStreams, _flat_stream, append_compressed, as_cache, nz_offset_from_idxs         # noqa: F401  (re-exported)
 
@@ -868,6 +869,24 @@ class MustafarAttention:
             return out, lse, past   # lengths advance with the device counter
         k_w.len = v_w.len = w_len
         return out, lse, past._replace(kv_seq_len=past.kv_seq_len + n)
+
+    # ---- ragged batches: independent bsz-1 pasts in one call (ragged.py, ragged_batch.hip) ------------------------------
+    def decode_ragged(self, query_states, key_states, value_states, pasts, return_lse: bool = False, batch: Optional[RaggedBatch] = None):
+        """n_q consecutive tokens of each of n sequences that share nothing but this attention object: q [n, H, n_q, D], their new k / v
+        [n, Hkv, n_q, D] and `pasts`, a list of n bsz-1 pasts (any cache kind decode_multi serves, mixed freely) -> (out [n, H, n_q, D],
+        pasts'), or (out, lse fp32 [n, H, n_q], pasts') with `return_lse`.  One library call reads only the tokens that exist: no
+        padding, no mask; sequence s gets bit for bit what decode_multi on its past alone returns.  Close the call per sequence with
+        `accept(pasts'[s], rejected=r_s)` or `accept(pasts'[s], keep=, n_q=)`: each sequence drops its own number of drafts and runs its
+        own 256-token trigger when it is due.  `batch`: the `ragged.RaggedBatch` whose device table the call uses; None: one of this
+        object's own, made at the first call (outside any graph capture) and grown when a call brings more sequences.  ValueError as
+        `RaggedBatch.decode` lists them; n_q is limited to 64 // groups, one library call.  INTEGRATION.md 5."""
+        if batch is None:
+            if self.cfg.api != "fused":
+                raise ValueError("decode_ragged needs MustafarConfig(api='fused')")
+            batch = self.__dict__.get("_ragged_batch")
+            if batch is None or batch.capacity < len(pasts):
+                batch = self._ragged_batch = RaggedBatch(self, max(len(pasts), 8))
+        return batch.decode(query_states, key_states, value_states, pasts, return_lse)
 
     def accept(self, past, rejected: int = 0, defer_trigger: bool = False, keep=None, n_q: Optional[int] = None):
         """Close a decode_multi call: drop the `rejected` newest rows (0 <= rejected < the rows the window holds) -- only the host lengths
