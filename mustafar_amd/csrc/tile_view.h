@@ -45,26 +45,23 @@ inline bool tile_view_ok(const mustafar_cache_view* v, int tokens)
     return v && !v->flags && v->bmp && v->idx && v->nz && (v->nz_head_stride || v->nz_offset) && (!v->bmp_head_stride || v->bmp_head_stride >= tiles) &&
            (!v->idx_head_stride || v->idx_head_stride >= tiles + 1);
 }
-// MUSTAFAR_VIEW_KEY_ROWS: rows of 256 bytes = 16 uint4 from the head's start, a table entry per block
-inline bool key_rows_view_ok(const mustafar_cache_view* v, int tokens)
+// a key base in token rows (flag: MUSTAFAR_VIEW_KEY_ROWS, channel bytes; MUSTAFAR_VIEW_KEY_NIBBLE_ROWS, 4-bit channel steps): rows of 256
+// bytes = 16 uint4 from the head's start, a table entry per block
+inline bool row_view_ok(const mustafar_cache_view* v, int tokens, uint32_t flag)
 {
-    return v && v->flags == MUSTAFAR_VIEW_KEY_ROWS && v->idx && v->nz && v->nz_head_stride > 0 && (v->nz_head_stride & 15) == 0 &&
-           v->idx_head_stride >= tokens / 64;
+    return v && v->flags == flag && v->idx && v->nz && v->nz_head_stride > 0 && (v->nz_head_stride & 15) == 0 && v->idx_head_stride >= tokens / 64;
 }
-// MUSTAFAR_VIEW_KEY_NIBBLE_ROWS: as the token rows -- rows of 256 bytes from the head's start, a table entry per block
-inline bool key_nibble_rows_view_ok(const mustafar_cache_view* v, int tokens)
+// a value base in channel lists (flag: MUSTAFAR_VIEW_VALUE_LISTS, a table entry per block; MUSTAFAR_VIEW_VALUE_PAIR_LISTS, two per pair of
+// blocks): `columns` table entries, the closing one among them
+inline bool list_view_ok(const mustafar_cache_view* v, uint32_t flag, int columns)
 {
-    return v && v->flags == MUSTAFAR_VIEW_KEY_NIBBLE_ROWS && v->idx && v->nz && v->nz_head_stride > 0 && (v->nz_head_stride & 15) == 0 &&
-           v->idx_head_stride >= tokens / 64;
+    return v && v->flags == flag && v->idx && v->nz && v->nz_head_stride > 0 && v->idx_head_stride >= columns;
 }
-// MUSTAFAR_VIEW_VALUE_LISTS: a table entry per block and the closing one
-inline bool value_lists_view_ok(const mustafar_cache_view* v, int tokens)
-{
-    return v && v->flags == MUSTAFAR_VIEW_VALUE_LISTS && v->idx && v->nz && v->nz_head_stride > 0 && v->idx_head_stride >= tokens / 64 + 1;
-}
-// MUSTAFAR_VIEW_VALUE_PAIR_LISTS: two table entries per pair of blocks and the closing one
+// the four forms by name (decode_attention)
+inline bool key_rows_view_ok(const mustafar_cache_view* v, int tokens) { return row_view_ok(v, tokens, MUSTAFAR_VIEW_KEY_ROWS); }
+inline bool key_nibble_rows_view_ok(const mustafar_cache_view* v, int tokens) { return row_view_ok(v, tokens, MUSTAFAR_VIEW_KEY_NIBBLE_ROWS); }
+inline bool value_lists_view_ok(const mustafar_cache_view* v, int tokens) { return list_view_ok(v, MUSTAFAR_VIEW_VALUE_LISTS, tokens / 64 + 1); }
 inline bool value_pair_lists_view_ok(const mustafar_cache_view* v, int tokens)
 {
-    return v && v->flags == MUSTAFAR_VIEW_VALUE_PAIR_LISTS && v->idx && v->nz && v->nz_head_stride > 0 &&
-           v->idx_head_stride >= 2 * ((tokens / 64 + 1) / 2) + 1;
+    return list_view_ok(v, MUSTAFAR_VIEW_VALUE_PAIR_LISTS, 2 * ((tokens / 64 + 1) / 2) + 1);
 }

@@ -23,17 +23,11 @@ constexpr int kVlPermByte = 0, kVlWidthByte = 128, kVlHalf1Dword = 48;
 constexpr int kVlMaxRows = 32, kVlMaxWords = 16;
 constexpr int kVlBlockAlignDwords = 4;
 
-// bit of channel c (inside the half) in a value tile's bitmap, and the number of the tile's non-zeros in front of it
-VL_FN bool vl_bit(uint64_t m, int c) { return (m >> (63 - c)) & 1ull; }
-VL_FN int vl_rank(uint64_t m, int c)
-{
-    int n = 0;
-    for (int k = 0; k < c; k++) n += (int)((m >> (63 - k)) & 1ull);
-    return n;
-}
-// dwords of word j of a half with row widths m[0..31]
+// A word is the same object in the lists over pairs of blocks (value_pair_lists.h: tokens of 0..127, up to 64 rows): the functions of a
+// word exist here, once, for both forms.
+// dwords of word j of a half with row widths m[0..]
 VL_FN int vl_word_dwords(const unsigned char* m, int j) { return 2 * m[2 * j] + m[2 * j + 1]; }
-// dword offset of word j from the half's start (j = kVlMaxWords: the half's size)
+// dword offset of word j from the half's start (j = the form's MaxWords: the half's size)
 VL_FN int vl_word_offset(const unsigned char* m, int j)
 {
     int o = 0;

@@ -16,44 +16,18 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define VPL_FN __host__ __device__ inline
-#else
-#define VPL_FN inline
-#endif
+#include "value_lists.h"
 
-constexpr int kVplHeaderDwords = 64;
-constexpr int kVplPermByte = 0, kVplWidthByte = 128;
+constexpr int kVplHeaderDwords = kVlHeaderDwords;
+constexpr int kVplPermByte = kVlPermByte, kVplWidthByte = kVlWidthByte;
 constexpr int kVplMaxRows = 64, kVplMaxWords = 32;
-constexpr int kVplAlignDwords = 4;
+constexpr int kVplAlignDwords = kVlBlockAlignDwords;
 
-VPL_FN int vpl_pairs(int blocks) { return (blocks + 1) >> 1; }
-VPL_FN int vpl_table_columns(int blocks) { return 2 * vpl_pairs(blocks) + 1; }
+VL_FN int vpl_pairs(int blocks) { return (blocks + 1) >> 1; }
+VL_FN int vpl_table_columns(int blocks) { return 2 * vpl_pairs(blocks) + 1; }
 // the 64-token blocks pair p of a base of `blocks` holds: 2, or 1 for the trailing half pair
-VPL_FN int vpl_pair_blocks(int blocks, int p) { return 2 * p + 1 < blocks ? 2 : 1; }
-// dwords of word j of a half with row widths m[0..63]
-VPL_FN int vpl_word_dwords(const unsigned char* m, int j) { return 2 * m[2 * j] + m[2 * j + 1]; }
-// dword offset of word j from the half's start (j = kVplMaxWords: the half's size)
-VPL_FN int vpl_word_offset(const unsigned char* m, int j)
-{
-    int o = 0;
-    for (int k = 0; k < j; k++) o += vpl_word_dwords(m, k);
-    return o;
-}
-// byte offsets, from the half's start, of slot s of lane i: its token byte and its fp16 value (woff = vpl_word_offset(m, s >> 2))
-VPL_FN int vpl_token_byte(int woff, int i, int s) { return 4 * (woff + i) + (s & 3); }
-VPL_FN int vpl_value_byte(const unsigned char* m, int woff, int i, int s)
-{
-    const int m0 = m[2 * (s >> 2)];
-    return 4 * (woff + m0 + ((s & 2) ? m0 : 0) + i) + 2 * (s & 1);
-}
-// the slots lane i holds, padding included, when its list has cnt entries: whole token rows
-VPL_FN int vpl_token_slots(int cnt) { return (cnt + 3) & ~3; }
+VL_FN int vpl_pair_blocks(int blocks, int p) { return 2 * p + 1 < blocks ? 2 : 1; }
 // what the two table entries of a pair stand for before the scan: the header with half 0, and half 1 with the padding that keeps the
 // next pair 16-byte aligned
-VPL_FN int vpl_front_dwords(int half0) { return kVplHeaderDwords + half0; }
-VPL_FN int vpl_back_dwords(int half0, int half1)
-{
-    const int all = (kVplHeaderDwords + half0 + half1 + kVplAlignDwords - 1) & ~(kVplAlignDwords - 1);
-    return all - kVplHeaderDwords - half0;
-}
+VL_FN int vpl_front_dwords(int half0) { return kVplHeaderDwords + half0; }
+VL_FN int vpl_back_dwords(int half0, int half1) { return vl_block_dwords(half0, half1) - vpl_front_dwords(half0); }

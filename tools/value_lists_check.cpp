@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../mustafar_amd/csrc/tile_view.h"
 #include "../mustafar_amd/csrc/value_lists.h"
 
 namespace {
@@ -27,7 +28,7 @@ Half plan(const uint64_t* bmp)   // as half_plan of base_forms.hip
     Half h;
     for (int c = 0; c < 64; c++) {
         h.cnt[c] = 0;
-        for (int t = 0; t < 64; t++) h.cnt[c] += vl_bit(bmp[t], c);
+        for (int t = 0; t < 64; t++) h.cnt[c] += tile_bit(bmp[t], c);
     }
     for (int c = 0; c < 64; c++) {
         h.rank[c] = 0;
@@ -91,10 +92,10 @@ std::vector<unsigned char> fill(const Tiles& t)   // as value_lists_fill_kernel,
             int s = 0;
             for (int tok = 0; tok < 64; tok++) {
                 const uint64_t bits = t.bmp[64 * half + tok];
-                if (!vl_bit(bits, c)) continue;
+                if (!tile_bit(bits, c)) continue;
                 const int w = vl_word_offset(h.m, s >> 2);
                 blk.at(base + vl_token_byte(w, i, s)) = (unsigned char)tok;
-                const uint16_t v = t.nz[64 * half + tok].at(vl_rank(bits, c));
+                const uint16_t v = t.nz[64 * half + tok].at(tile_rank(bits, c));
                 std::memcpy(&blk.at(base + vl_value_byte(h.m, w, i, s)), &v, 2);
                 s++;
             }
@@ -127,7 +128,7 @@ Tiles back(const std::vector<unsigned char>& blk)   // as the three kernels of m
                     else {
                         uint16_t v;
                         std::memcpy(&v, &blk.at(base + vl_value_byte(m, w, i, s)), 2);
-                        t.nz[64 * half + (tok & 63)].at(vl_rank(t.bmp[64 * half + (tok & 63)], c)) = v;
+                        t.nz[64 * half + (tok & 63)].at(tile_rank(t.bmp[64 * half + (tok & 63)], c)) = v;
                     }
                 }
             }

@@ -42,7 +42,7 @@ struct Tiles {
     }
 };
 
-Half plan(const uint64_t* bmp, int ntok)   // as pair_half_plan of base_forms.hip
+Half plan(const uint64_t* bmp, int ntok)   // as half_plan of base_forms.hip
 {
     Half h;
     for (int c = 0; c < 64; c++) {
@@ -87,10 +87,10 @@ struct Stored {
     uint32_t front, back;   // header + half 0; half 1 + padding
 };
 
-Stored fill(const Tiles& t)   // as value_pair_lists_size_kernel + value_pair_lists_fill_kernel, both halves
+Stored fill(const Tiles& t)   // as value_lists_size_kernel + value_lists_fill_kernel over PairLists, both halves
 {
     const Half h0 = plan(t.bmp[0], t.ntok), h1 = plan(t.bmp[1], t.ntok);
-    const int d0 = vpl_word_offset(h0.m, kVplMaxWords), d1 = vpl_word_offset(h1.m, kVplMaxWords);
+    const int d0 = vl_word_offset(h0.m, kVplMaxWords), d1 = vl_word_offset(h1.m, kVplMaxWords);
     Stored s;
     s.front = (uint32_t)vpl_front_dwords(d0);
     s.back = (uint32_t)vpl_back_dwords(d0, d1);
@@ -108,14 +108,14 @@ Stored fill(const Tiles& t)   // as value_pair_lists_size_kernel + value_pair_li
             for (int tok = 0; tok < t.ntok; tok++) {
                 const uint64_t bits = t.bmp[half][tok];
                 if (!bit(bits, c)) continue;
-                const int w = vpl_word_offset(h.m, n >> 2);
-                blk.at(base + vpl_token_byte(w, i, n)) = (unsigned char)tok;
+                const int w = vl_word_offset(h.m, n >> 2);
+                blk.at(base + vl_token_byte(w, i, n)) = (unsigned char)tok;
                 const uint16_t v = t.nz[half][tok].at(rank_of(bits, c));
-                std::memcpy(&blk.at(base + vpl_value_byte(h.m, w, i, n)), &v, 2);
+                std::memcpy(&blk.at(base + vl_value_byte(h.m, w, i, n)), &v, 2);
                 n++;
             }
-            if (n & 1) std::memset(&blk.at(base + vpl_value_byte(h.m, vpl_word_offset(h.m, n >> 2), i, n)), 0, 2);
-            for (int q = n; q < vpl_token_slots(n); q++) blk.at(base + vpl_token_byte(vpl_word_offset(h.m, q >> 2), i, q)) = 0;
+            if (n & 1) std::memset(&blk.at(base + vl_value_byte(h.m, vl_word_offset(h.m, n >> 2), i, n)), 0, 2);
+            for (int q = n; q < vl_token_slots(n); q++) blk.at(base + vl_token_byte(vl_word_offset(h.m, q >> 2), i, q)) = 0;
         }
     }
     return s;
@@ -137,14 +137,14 @@ Tiles back(const Stored& st, int ntok)   // as the kernels of mustafar_value_pai
             for (int i = 0; i < 64; i++) {
                 const int c = blk.at(kVplPermByte + half * 64 + i) & 63;
                 for (int s = 0; s < 2 * kVplMaxRows && i < m[s >> 1]; s++) {
-                    const int w = vpl_word_offset(m, s >> 2);
-                    int tok = blk.at(base + vpl_token_byte(w, i, s));
+                    const int w = vl_word_offset(m, s >> 2);
+                    int tok = blk.at(base + vl_token_byte(w, i, s));
                     if (s && !tok) break;
                     tok &= ntok - 1;
                     if (!pass) t.bmp[half][tok] |= 1ull << (63 - c);
                     else {
                         uint16_t v;
-                        std::memcpy(&v, &blk.at(base + vpl_value_byte(m, w, i, s)), 2);
+                        std::memcpy(&v, &blk.at(base + vl_value_byte(m, w, i, s)), 2);
                         t.nz[half][tok].at(rank_of(t.bmp[half][tok], c)) = v;
                     }
                 }
